@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the batched multi-rate MPC solve path (BASELINE.json metric: MPC solves/s).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,6 +12,12 @@ the Monte-Carlo batch sharded over the GPUs, 4096 instances with 4x wider scatte
 GLOBAL index (1234 + index: the batch does not depend on the number of ranks), no data-path collective (weak scaling) --
 and the 256-per-GPU figure moves into `extra_configs`.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, roofline from the same K
+launches).  --full adds what takes runs or work of its own: the oracle parity sample, batch-1 latencies, the CPU
+baselines and BASELINE.json configs[2..4] (`extra_configs`).  --dump-outputs DIR writes what the last timed step handed
+back (solutions, first moves, status, iterations) as float64 .npy files; the inputs are seeded, so two builds can be
+compared output for output.
 """
 from __future__ import annotations
 
@@ -240,17 +246,42 @@ def measure_extra(spec, pkg, synth, solver, sharding, dev, local_rank, rank, wor
     return rec
 
 
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this much in all; above it a fixed, seeded sample of instances
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """Writes `arrays` (name -> per-instance array of this rank's slice) as float64 DIR/<name>.npy, or
+    DIR/<name>_rank<r>.npy with N > 1 ranks.  When they exceed this rank's share of DUMP_BYTES, the same seeded sample of
+    instances is taken from every array and its indices go to sample_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    budget = DUMP_BYTES // world - 4096 * (len(arrays) + 1)        # room for the .npy headers
+    if n * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(0).choice(n, budget // (row_bytes + 8), replace=False))   # + its index
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; 60 on the N > 1 configs[3] line)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps (default 20; 6 on the N > 1 configs[3] line)")
     ap.add_argument("--batch", type=int, default=256, help="instances per GPU (configs[1] = 256)")
     ap.add_argument("--workload", default="hover", choices=["hover", "takeoff", "montecarlo"])
     ap.add_argument("--config", default="paper", choices=["paper", "horizon2x"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs array (BASELINE configs[2..4])")
+    ap.add_argument("--full", action="store_true",
+                    help="also the oracle parity sample, latencies, CPU baselines and extra_configs (BASELINE configs[2..4])")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the batch-1 latencies")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra_configs array")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as float64 DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -304,11 +335,14 @@ def main():
         B, workload = 4096, "montecarlo"
         inputs = sharding.rank_inputs(cfg, synth, B * world, rank, world, workload=workload)
         count = B
-        if args.steps == 200:
-            args.steps, args.warmup = 60, 6           # 60 x 0.43 ms: the same wall-clock order as 200 x 46 us
     else:
         first, count = sharding.shard_range(B * world, rank, world)   # contiguous slice, no exchange
         inputs = synth.make_batch(cfg, count, workload=workload, first_index=first)
+    # defaults: 60 x 0.43 ms on the N > 1 line is the same wall-clock order as 200 x 46 us at N = 1
+    if args.steps is None:
+        args.steps = 60 if multi else 200
+    if args.warmup is None:
+        args.warmup = 6 if multi else 20
     mpc = solver.BatchedVSMPC(cfg, device=local_rank, max_batch=count)
 
     d_in = torch.from_numpy(inputs).to(dev)
@@ -354,6 +388,10 @@ def main():
     rccl_ranks = int(solved[1].item()) if distributed else 1      # every rank added 1: proves the collective saw N ranks
     kernel_ms = float(kms.item())
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": d_x.cpu().numpy(), "first_moves": d_fm.cpu().numpy(),
+                                         "status": d_st.cpu().numpy(), "iterations": d_it.cpu().numpy()}, rank, world)
+
     if rank == 0:
         total = B * world
         value = total * args.steps / elapsed
@@ -394,6 +432,7 @@ def main():
                          "hbm_frac_informational": BYTES_ALG[args.config] * count / (kernel_ms * 1e-3) / 8.0e12},
             "solved": total_solved, "instances_per_step": total,
         }
+    if rank == 0 and args.full:
         x_host = d_x.cpu().numpy()
         out["parity_max_rel_err_vs_oracle"] = parity_sample(args.config, inputs, x_host)
         if not args.no_latency:
@@ -432,7 +471,7 @@ def main():
     # BASELINE.json configs[2..4] at full size, appended to the same line (every rank runs its own slice; `value` stays
     # on configs[1]).  Skipped when the caller picked a non-default workload itself.
     mpc.close()
-    if default_line and not args.no_extra:
+    if args.full and default_line and not args.no_extra:
         extra = []
         specs = EXTRA_CONFIGS
         if multi:     # configs[3] is the headline here; the 256-per-GPU hover figure of the N = 1 line moves down here
