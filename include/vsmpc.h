@@ -117,8 +117,30 @@ typedef struct vsmpc_handle vsmpc_handle;
  * own create and grows its log buffer only when a longer logged run is requested.
  * Horizons: any (nIter, nIterSmall, controlHorizon) listed in csrc/vsmpc_horizons.def has a kernel instantiation
  * (the kernels are straight-line code generated per horizon); others return VSMPC_ERR_UNSUPPORTED_CONFIG -- add the
- * horizon to VSMPC_HORIZONS and rebuild. */
+ * horizon to VSMPC_HORIZONS and rebuild, or use the runtime-sized kernel (vsmpc_create_ex below, or
+ * VSMPC_RUNTIME_HORIZON=1 in the environment). */
 int vsmpc_create(const vsmpc_config* cfg, int device, int max_batch, vsmpc_handle** out);
+
+/* vsmpc_create with a choice of solve kernel.  `flags`:
+ *   0                              exactly vsmpc_create without the environment switch below (tabled horizons only);
+ *   VSMPC_CREATE_RUNTIME_FALLBACK  the tabled instantiation where one exists, the RUNTIME-SIZED kernel otherwise;
+ *   VSMPC_CREATE_RUNTIME_ONLY      always the runtime-sized kernel (A/B runs, cross-checks at tabled horizons; it takes
+ *                                  precedence when both bits are set).
+ * Unknown bits return VSMPC_ERR_INVALID_ARG.  The runtime-sized kernel (csrc/vsmpc_runtime.hip) solves every configuration
+ * the validation accepts (2 <= nIter <= 40, 2 <= nIterSmall <= controlHorizon <= nIter) with the same record, outputs,
+ * statuses and active-set rule as the tuned kernels, at a fraction of their speed (profiles/runtime_horizon_bench.txt).
+ * It keeps the condensed matrix in device memory: (NP (NP + 1) / 2) doubles per instance of max_batch, NP = 8 HC +
+ * 4 (HC - nS + 1) + 1 (paper horizon 59 KB, (40, 2, 40) 0.9 MB), allocated here.  Launches of one runtime handle share
+ * that workspace: they must be ordered (one stream at a time, as for every handle).
+ * On a runtime handle every solve entry point works (vsmpc_solve_batch, _device, vsmpc_tick, the rollout API and its graph
+ * replay, vsmpc_timing_*), as do vsmpc_linearize_batch, vsmpc_assemble_dense, vsmpc_kinematics_batch and
+ * vsmpc_provider_batch; vsmpc_kernel_name returns "solve_kernel_rt" and vsmpc_condensed_dim NP.  vsmpc_set_kernel_form
+ * accepts form 0 only; vsmpc_debug_condensed and vsmpc_debug_phase_cycles return VSMPC_ERR_UNSUPPORTED_CONFIG.
+ * Environment: VSMPC_RUNTIME_HORIZON=1 makes vsmpc_create behave as vsmpc_create_ex(.., VSMPC_CREATE_RUNTIME_FALLBACK, ..),
+ * so that unmodified programs (the C++ wrapper, the pybind11 shim) run any horizon. */
+#define VSMPC_CREATE_RUNTIME_FALLBACK 0x1u
+#define VSMPC_CREATE_RUNTIME_ONLY 0x2u
+int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned flags, vsmpc_handle** out);
 void vsmpc_destroy(vsmpc_handle* h);
 
 /* IMPCProblem::getNOptimizationVariables / getNConstraints (IMPCProblem.h:71-78) and record sizes. */

@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(HERE, "libvsmpc.so")
 
 # every symbol include/vsmpc.h declares
 EXPORTS = (
-    "vsmpc_create", "vsmpc_destroy", "vsmpc_num_variables", "vsmpc_num_constraints", "vsmpc_input_doubles",
+    "vsmpc_create", "vsmpc_create_ex", "vsmpc_destroy", "vsmpc_num_variables", "vsmpc_num_constraints", "vsmpc_input_doubles",
     "vsmpc_max_batch", "vsmpc_solve_batch", "vsmpc_solve_batch_device", "vsmpc_linearize_batch",
     "vsmpc_assemble_dense", "vsmpc_condensed_dim", "vsmpc_debug_condensed", "vsmpc_timing_begin",
     "vsmpc_timing_end", "vsmpc_strerror", "vsmpc_kernel_name", "vsmpc_debug_phase_cycles", "vsmpc_kinematics_batch",
@@ -48,6 +48,8 @@ def load():
     vp, ip, dp, c_int = ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.c_int
     lib.vsmpc_create.argtypes = [ctypes.POINTER(CConfig), c_int, c_int, ctypes.POINTER(vp)]
     lib.vsmpc_create.restype = c_int
+    lib.vsmpc_create_ex.argtypes = [ctypes.POINTER(CConfig), c_int, c_int, ctypes.c_uint, ctypes.POINTER(vp)]
+    lib.vsmpc_create_ex.restype = c_int
     lib.vsmpc_destroy.argtypes = [vp]
     lib.vsmpc_destroy.restype = None
     for name in ("vsmpc_num_variables", "vsmpc_num_constraints", "vsmpc_input_doubles", "vsmpc_max_batch",

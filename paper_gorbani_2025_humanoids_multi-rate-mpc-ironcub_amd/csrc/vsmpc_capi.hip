@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -16,7 +17,10 @@ using namespace vsmpc;
 struct vsmpc_handle {
     vsmpc_config cfg;
     DevCfg dev;
-    int variant;
+    int variant;     // tuned instantiation (1..), or VARIANT_NONE on a runtime handle
+    int runtime;     // solve with the runtime-sized kernel (vsmpc_create_ex)
+    RtDims rt;       // its sizes (runtime handles only)
+    double* d_ws;    // its per-instance workspace, max_batch x rt.ws_doubles
     int form;        // condensing form of the solve kernel (vsmpc_set_kernel_form)
     KinOpts kin;     // vsmpc_set_kinematics_options
     int device;
@@ -105,6 +109,16 @@ int hip_fail(hipError_t e, const char* what) {
     } while (0)
 
 #define ON_DEVICE(dev) DeviceScope _scope(dev); HIP_TRY(_scope.err)
+
+// The solve launch of a handle: the tuned instantiation, or the runtime-sized kernel with the workspace of instances
+// `first` .. `first + batch - 1` (a chunk of a larger batch must not share workspace with a chunk on another stream).
+hipError_t solve_launch(const vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_fm, int* d_status,
+                        int* d_iters, size_t first, hipStream_t s) {
+    if (h->runtime)
+        return launch_solve_runtime(h->rt, h->dev, d_in, batch, h->d_ws + first * size_t(h->rt.ws_doubles), d_x, d_fm,
+                                    d_status, d_iters, s);
+    return launch_solve(h->variant, h->form, h->dev, d_in, batch, d_x, d_fm, d_status, d_iters, nullptr, nullptr, nullptr, s);
+}
 
 // carve-up of the mapped staging buffer (host or device view)
 struct Stage {
@@ -196,11 +210,24 @@ bool config_valid(const vsmpc_config& c) {
 extern "C" {
 
 int vsmpc_create(const vsmpc_config* cfg, int device, int max_batch, vsmpc_handle** out) {
+    // VSMPC_RUNTIME_HORIZON=1: unmodified programs get the runtime kernel for horizons outside the table
+    const char* env = getenv("VSMPC_RUNTIME_HORIZON");
+    const unsigned flags = (env != nullptr && env[0] == '1' && env[1] == '\0') ? VSMPC_CREATE_RUNTIME_FALLBACK : 0u;
+    return vsmpc_create_ex(cfg, device, max_batch, flags, out);
+}
+
+int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned flags, vsmpc_handle** out) {
     if (cfg == nullptr || out == nullptr || max_batch <= 0) return VSMPC_ERR_INVALID_ARG;
     *out = nullptr;
+    if ((flags & ~unsigned(VSMPC_CREATE_RUNTIME_FALLBACK | VSMPC_CREATE_RUNTIME_ONLY)) != 0u) return VSMPC_ERR_INVALID_ARG;
     if (!config_valid(*cfg)) return VSMPC_ERR_INVALID_ARG;
-    const int variant = select_variant(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon);
-    if (variant == VARIANT_NONE) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    const int variant = (flags & VSMPC_CREATE_RUNTIME_ONLY)
+                            ? int(VARIANT_NONE)
+                            : select_variant(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon);
+    if (variant == VARIANT_NONE && flags == 0u) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    const bool runtime = variant == VARIANT_NONE;
+    const RtDims rt = runtime_dims(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon);
+    if (runtime && runtime_lds_bytes(rt) > RT_MAX_LDS) return VSMPC_ERR_UNSUPPORTED_CONFIG;   // (not for a valid config)
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return VSMPC_ERR_INVALID_ARG;
@@ -212,7 +239,9 @@ int vsmpc_create(const vsmpc_config* cfg, int device, int max_batch, vsmpc_handl
     h->cfg = *cfg;
     fill_devcfg(*cfg, h->dev);
     h->variant = variant;
-    h->form = initial_kernel_form();
+    h->runtime = runtime ? 1 : 0;
+    h->rt = rt;
+    h->form = runtime ? 0 : initial_kernel_form();
     for (int i = 0; i < VSMPC_N_JOINTS; ++i) h->kin.sel[i] = 3 + i;   // the shipped robot: joints 3..10
     h->kin.constant_lambda = 0;
     if (h->form == 1 && !variant_has_structured(variant)) h->form = 0;
@@ -222,7 +251,7 @@ int vsmpc_create(const vsmpc_config* cfg, int device, int max_batch, vsmpc_handl
     h->n_var = NX * (N + 1) + NJ * H + NTH * (H - nS + 1);
     h->n_con = NX * (N + 1) + NTH * (N - nS + 1);
     h->n_in = VSMPC_IN_XREF + 12 * (N - nS + 1);
-    h->n_p = variant_condensed_dim(variant);
+    h->n_p = runtime ? rt.np : variant_condensed_dim(variant);
 
     const size_t B = size_t(max_batch);
     hipError_t e = hipSuccess;
@@ -236,6 +265,7 @@ int vsmpc_create(const vsmpc_config* cfg, int device, int max_batch, vsmpc_handl
     if (e == hipSuccess) e = hipMalloc(&h->d_kin, B * VSMPC_KIN_SIZE * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&h->d_kout, B * VSMPC_KIN_OUT * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&h->d_stamps, B * 16 * sizeof(unsigned long long));
+    if (e == hipSuccess && runtime) e = hipMalloc(&h->d_ws, B * size_t(rt.ws_doubles) * sizeof(double));
     for (int i = 0; i < PIPE_STREAMS && e == hipSuccess; ++i) {
         e = hipStreamCreateWithFlags(&h->pipe[i], hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&h->pipe_done[i], hipEventDisableTiming);
@@ -269,6 +299,7 @@ void vsmpc_destroy(vsmpc_handle* h) {
     if (h->d_kin) (void)hipFree(h->d_kin);
     if (h->d_kout) (void)hipFree(h->d_kout);
     if (h->d_stamps) (void)hipFree(h->d_stamps);
+    if (h->d_ws) (void)hipFree(h->d_ws);
     for (int i = 0; i < PIPE_STREAMS; ++i) {
         if (h->pipe[i]) (void)hipStreamDestroy(h->pipe[i]);
         if (h->pipe_done[i]) (void)hipEventDestroy(h->pipe_done[i]);
@@ -285,7 +316,9 @@ int vsmpc_num_constraints(const vsmpc_handle* h) { return h ? h->n_con : VSMPC_E
 int vsmpc_input_doubles(const vsmpc_handle* h) { return h ? h->n_in : VSMPC_ERR_INVALID_ARG; }
 int vsmpc_max_batch(const vsmpc_handle* h) { return h ? h->max_batch : VSMPC_ERR_INVALID_ARG; }
 int vsmpc_condensed_dim(const vsmpc_handle* h) { return h ? h->n_p : VSMPC_ERR_INVALID_ARG; }
-const char* vsmpc_kernel_name(const vsmpc_handle* h) { return h ? variant_kernel_name(h->variant) : "none"; }
+const char* vsmpc_kernel_name(const vsmpc_handle* h) {
+    return h ? (h->runtime ? runtime_kernel_name() : variant_kernel_name(h->variant)) : "none";
+}
 
 int vsmpc_solve_batch_device(vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_first_move,
                              int* d_status, int* d_iters, void* stream) {
@@ -293,8 +326,7 @@ int vsmpc_solve_batch_device(vsmpc_handle* h, const double* d_in, int batch, dou
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (batch == 0) return VSMPC_OK;
     ON_DEVICE(h->device);   // an enqueue-only entry must not change the caller's current device either
-    HIP_TRY(launch_solve(h->variant, h->form, h->dev, d_in, batch, d_x, d_first_move, d_status, d_iters, nullptr, nullptr, nullptr,
-                         static_cast<hipStream_t>(stream)));
+    HIP_TRY(solve_launch(h, d_in, batch, d_x, d_first_move, d_status, d_iters, 0, static_cast<hipStream_t>(stream)));
     return VSMPC_OK;
 }
 
@@ -310,7 +342,7 @@ int vsmpc_solve_batch(vsmpc_handle* h, const double* in, int batch, double* x, d
         // zero-copy path: the kernel reads the records from and writes the results to pinned host memory
         const Stage hv = stage_view(h, h->h_stage), dv = stage_view(h, h->d_stage);   // the same carve-up on both views
         memcpy(hv.in, in, B * h->n_in * sizeof(double));
-        HIP_TRY(launch_solve(h->variant, h->form, h->dev, dv.in, batch, dv.x, dv.fm, dv.st, dv.it, nullptr, nullptr, nullptr, s));
+        HIP_TRY(solve_launch(h, dv.in, batch, dv.x, dv.fm, dv.st, dv.it, 0, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (x) memcpy(x, hv.x, B * h->n_var * sizeof(double));
         if (first_move) memcpy(first_move, hv.fm, B * VSMPC_FM_SIZE * sizeof(double));
@@ -349,13 +381,12 @@ int vsmpc_solve_batch(vsmpc_handle* h, const double* in, int batch, double* x, d
         hipStream_t ps = h->pipe[k % nstreams];
         if (!ok(hipMemcpyAsync(h->d_in + o * h->n_in, in + o * h->n_in, N * h->n_in * sizeof(double), hipMemcpyHostToDevice, ps))) break;
         if (direct) {
-            ok(launch_solve(h->variant, h->form, h->dev, h->d_in + o * h->n_in, n, x ? zx + o * h->n_var : nullptr,
-                            first_move ? zfm + o * VSMPC_FM_SIZE : nullptr, zst + o, iters ? zit + o : nullptr,
-                            nullptr, nullptr, nullptr, ps));
+            ok(solve_launch(h, h->d_in + o * h->n_in, n, x ? zx + o * h->n_var : nullptr,
+                            first_move ? zfm + o * VSMPC_FM_SIZE : nullptr, zst + o, iters ? zit + o : nullptr, o, ps));
             continue;
         }
-        if (!ok(launch_solve(h->variant, h->form, h->dev, h->d_in + o * h->n_in, n, h->d_x + o * h->n_var,
-                             h->d_fm + o * VSMPC_FM_SIZE, h->d_status + o, h->d_iters + o, nullptr, nullptr, nullptr, ps))) break;
+        if (!ok(solve_launch(h, h->d_in + o * h->n_in, n, h->d_x + o * h->n_var, h->d_fm + o * VSMPC_FM_SIZE, h->d_status + o,
+                             h->d_iters + o, o, ps))) break;
         if (x) ok(hipMemcpyAsync(x + o * h->n_var, h->d_x + o * h->n_var, N * h->n_var * sizeof(double), hipMemcpyDeviceToHost, ps));
         if (first_move)
             ok(hipMemcpyAsync(first_move + o * VSMPC_FM_SIZE, h->d_fm + o * VSMPC_FM_SIZE,
@@ -388,7 +419,8 @@ int vsmpc_linearize_batch(vsmpc_handle* h, const double* in, int batch, double* 
     double* dBt = dBj + size_t(h->max_batch) * NX * NJ;
     double* dC = dBt + size_t(h->max_batch) * NX * NTH;
     HIP_TRY(hipMemcpy(h->d_in, in, B * h->n_in * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(launch_linearize(h->variant, h->dev, h->d_in, batch, dA, dBj, dBt, dC, nullptr));
+    if (h->runtime) HIP_TRY(launch_linearize_runtime(h->rt, h->dev, h->d_in, batch, dA, dBj, dBt, dC, nullptr));
+    else HIP_TRY(launch_linearize(h->variant, h->dev, h->d_in, batch, dA, dBj, dBt, dC, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     if (A) HIP_TRY(hipMemcpy(A, dA, B * NX * NX * sizeof(double), hipMemcpyDeviceToHost));
     if (Bj) HIP_TRY(hipMemcpy(Bj, dBj, B * NX * NJ * sizeof(double), hipMemcpyDeviceToHost));
@@ -491,6 +523,7 @@ int vsmpc_assemble_dense(vsmpc_handle* h, const double* in_one, double* H, doubl
 
 int vsmpc_debug_condensed(vsmpc_handle* h, const double* in_one, double* M, double* Lfac) {
     if (h == nullptr || in_one == nullptr) return VSMPC_ERR_INVALID_ARG;
+    if (h->runtime) return VSMPC_ERR_UNSUPPORTED_CONFIG;
     ON_DEVICE(h->device);
     const size_t np2 = size_t(h->n_p) * h->n_p;
     HIP_TRY(hipMemcpy(h->d_in, in_one, h->n_in * sizeof(double), hipMemcpyHostToDevice));
@@ -540,7 +573,7 @@ int vsmpc_tick(vsmpc_handle* h, const double* kin, double* in, int batch, double
         memcpy(hv.kin, kin, B * VSMPC_KIN_SIZE * sizeof(double));
         memcpy(hv.in, in, B * h->n_in * sizeof(double));
         HIP_TRY(launch_kinematics_patch(dv.kin, batch, dv.in, h->n_in, h->kin, s));
-        HIP_TRY(launch_solve(h->variant, h->form, h->dev, dv.in, batch, dv.x, dv.fm, dv.st, dv.it, nullptr, nullptr, nullptr, s));
+        HIP_TRY(solve_launch(h, dv.in, batch, dv.x, dv.fm, dv.st, dv.it, 0, s));
         HIP_TRY(hipStreamSynchronize(s));
         for (size_t b = 0; b < B; ++b)   // hand the completed fields back (the caller's record is the record of the tick)
             memcpy(in + b * h->n_in + VSMPC_IN_LLIN, hv.in + b * h->n_in + VSMPC_IN_LLIN, (24 + 24 + 9) * sizeof(double));
@@ -553,8 +586,7 @@ int vsmpc_tick(vsmpc_handle* h, const double* kin, double* in, int batch, double
     HIP_TRY(hipMemcpyAsync(h->d_kin, kin, B * VSMPC_KIN_SIZE * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(h->d_in, in, B * h->n_in * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(launch_kinematics_patch(h->d_kin, batch, h->d_in, h->n_in, h->kin, s));
-    HIP_TRY(launch_solve(h->variant, h->form, h->dev, h->d_in, batch, h->d_x, h->d_fm, h->d_status, h->d_iters, nullptr, nullptr,
-                         nullptr, s));
+    HIP_TRY(solve_launch(h, h->d_in, batch, h->d_x, h->d_fm, h->d_status, h->d_iters, 0, s));
     HIP_TRY(hipMemcpyAsync(in, h->d_in, B * h->n_in * sizeof(double), hipMemcpyDeviceToHost, s));
     if (x) HIP_TRY(hipMemcpyAsync(x, h->d_x, B * h->n_var * sizeof(double), hipMemcpyDeviceToHost, s));
     if (first_move) HIP_TRY(hipMemcpyAsync(first_move, h->d_fm, B * VSMPC_FM_SIZE * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -612,6 +644,7 @@ int vsmpc_set_kinematics_options(vsmpc_handle* h, const int* joint_selector, int
 
 int vsmpc_debug_phase_cycles(vsmpc_handle* h, const double* in, int batch, unsigned long long* stamps16) {
     if (h == nullptr || in == nullptr || stamps16 == nullptr || batch <= 0) return VSMPC_ERR_INVALID_ARG;
+    if (h->runtime) return VSMPC_ERR_UNSUPPORTED_CONFIG;
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     ON_DEVICE(h->device);
     unsigned long long* d_st = h->d_stamps;
@@ -826,8 +859,7 @@ constexpr int GRAPH_TICKS = 25;  // ticks per captured graph (50 kernel nodes)
 // synchronisation the loop needs
 hipError_t enqueue_tick(vsmpc_rollout* r, hipStream_t s) {
     vsmpc_handle* h = r->h;
-    hipError_t e = launch_solve(h->variant, h->form, h->dev, r->d_rec, r->batch, h->d_x, h->d_fm, h->d_status, h->d_iters, nullptr,
-                                nullptr, nullptr, s);
+    hipError_t e = solve_launch(h, r->d_rec, r->batch, h->d_x, h->d_fm, h->d_status, h->d_iters, 0, s);
     if (e == hipSuccess && r->use_tree) e = enqueue_tree(r, h->d_fm, h->d_status, s);   // A_mom, I_B of the joints after the move
     if (e == hipSuccess)
         e = launch_advance(r->rd, r->batch, r->d_state, r->d_params, r->d_tick, h->d_fm, h->d_status, h->d_iters,
@@ -910,6 +942,7 @@ int vsmpc_rollout_get_records(vsmpc_rollout* r, double* records) {
 
 int vsmpc_set_kernel_form(vsmpc_handle* h, int form) {
     if (h == nullptr || form < 0 || form > 2) return VSMPC_ERR_INVALID_ARG;
+    if (h->runtime && form != 0) return VSMPC_ERR_UNSUPPORTED_CONFIG;   // the runtime kernel has one form
     if (form == 1 && !variant_has_structured(h->variant)) return VSMPC_ERR_UNSUPPORTED_CONFIG;
     const int prev = h->form;
     h->form = form;

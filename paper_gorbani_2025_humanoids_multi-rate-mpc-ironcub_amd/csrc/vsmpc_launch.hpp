@@ -42,6 +42,26 @@ hipError_t launch_solve(int variant, int form, const DevCfg& cfg, const double* 
 hipError_t launch_linearize(int variant, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,
                             double* Bt, double* c, hipStream_t stream);
 
+// Runtime-sized solve kernel (vsmpc_runtime.hip): every horizon config_valid() accepts, sizes as kernel arguments.
+struct RtDims {
+    int n, ns, hc;        // nIter, nIterSmall, controlHorizon
+    int nvb, nu, nv;      // throttle blocks, joint unknowns 8 HC, throttle unknowns 4 NVB
+    int nz, np;           // condensed unknowns, + the affine / gradient column
+    int nin, nxs, nvar;   // record length, states 26 (N + 1), primal length
+    int ntri;             // NP (NP + 1) / 2: packed lower triangle of the augmented condensed matrix
+    int ws_doubles;       // per-instance global workspace (doubles)
+    int lds_doubles;      // dynamic LDS of one workgroup (doubles)
+};
+constexpr size_t RT_MAX_LDS = 160 * 1024;
+RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon);
+size_t runtime_lds_bytes(const RtDims& d);
+const char* runtime_kernel_name();
+// d_ws: workspace of the launch's first instance (instance b of the launch uses d_ws + b * d.ws_doubles)
+hipError_t launch_solve_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws, double* d_x,
+                                double* d_fm, int* d_status, int* d_iters, hipStream_t stream);
+hipError_t launch_linearize_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,
+                                    double* Bt, double* c, hipStream_t stream);
+
 struct KinOpts {
     int sel[VSMPC_N_JOINTS];   // robot joint index of every controlled joint (Lambda_ang columns)
     int constant_lambda;       // jointsLambdaOption "constant"

@@ -58,6 +58,12 @@ FM_THRUST = 16
 FM_THRUSTDOT = 20
 FM_SIZE = 24
 
+# vsmpc_create_ex flags (VSMPC_CREATE_* in include/vsmpc.h)
+CREATE_RUNTIME_FALLBACK = 0x1
+CREATE_RUNTIME_ONLY = 0x2
+RUNTIME_MODES = {"never": 0, "fallback": CREATE_RUNTIME_FALLBACK, "always": CREATE_RUNTIME_ONLY}
+RUNTIME_KERNEL_NAME = "solve_kernel_rt"
+
 # closed-loop rollout: plant state / parameter layouts (VSMPC_PS_* / VSMPC_PP_* in include/vsmpc.h)
 PS_P, PS_HLIN, PS_RPY, PS_HANG, PS_T, PS_TD, PS_Q, PS_U, PS_TDES, PS_TDDES = 0, 3, 6, 9, 12, 16, 20, 28, 32, 36
 PS_TNN, PS_EST, PS_EKFP = 40, 44, 52     # jet plant option (LSTM thrust, EKF estimates (T, Tdot) x 4, covariances 2x2 x 4)

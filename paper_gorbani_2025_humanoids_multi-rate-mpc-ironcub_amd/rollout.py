@@ -167,10 +167,11 @@ def load_reference_trajectories(npz_path: str):
 class ClosedLoopRollout:
     """`batch` closed loops resident on one GPU.  reset() uploads plant states, run(ticks) advances them."""
 
-    def __init__(self, cfg: L.MPCConfig, batch: int, traj_pos, traj_vel, traj_alpha, alpha_dt: float, device: int = 0):
+    def __init__(self, cfg: L.MPCConfig, batch: int, traj_pos, traj_vel, traj_alpha, alpha_dt: float, device: int = 0,
+                 runtime: str = "never"):
         self.cfg = cfg
         self.batch = batch
-        self.mpc = BatchedVSMPC(cfg, device=device, max_batch=batch)
+        self.mpc = BatchedVSMPC(cfg, device=device, max_batch=batch, runtime=runtime)   # runtime: see BatchedVSMPC
         self.lib = self.mpc.lib
         pos = np.ascontiguousarray(traj_pos, dtype=np.float64)
         vel = np.ascontiguousarray(traj_vel, dtype=np.float64)

@@ -30,13 +30,22 @@ KERNEL_FORM_AUTO, KERNEL_FORM_STRUCTURED, KERNEL_FORM_SYRK = 0, 1, 2
 class BatchedVSMPC:
     """`max_batch` independent MPC instances on one GPU (one workgroup per instance)."""
 
-    def __init__(self, cfg: L.MPCConfig | None = None, device: int = 0, max_batch: int = 256):
+    def __init__(self, cfg: L.MPCConfig | None = None, device: int = 0, max_batch: int = 256, runtime: str = "never"):
+        """runtime: "never" -- the tuned kernel of a tabled horizon, other horizons are refused (vsmpc_create);
+        "fallback" -- the runtime-sized kernel where the table has no instantiation; "always" -- the runtime-sized kernel
+        for every horizon (vsmpc_create_ex, include/vsmpc.h)."""
+        if runtime not in L.RUNTIME_MODES:
+            raise ValueError(f"runtime must be one of {sorted(L.RUNTIME_MODES)}, not {runtime!r}")
         self.cfg = cfg or L.paper_config()
         self.lib = _lib.load()
         self._ccfg = self.cfg.to_c()
         self._h = ctypes.c_void_p()
-        _lib.check(self.lib.vsmpc_create(ctypes.byref(self._ccfg), device, max_batch, ctypes.byref(self._h)),
-                   "vsmpc_create")
+        if runtime == "never":
+            _lib.check(self.lib.vsmpc_create(ctypes.byref(self._ccfg), device, max_batch, ctypes.byref(self._h)),
+                       "vsmpc_create")
+        else:
+            _lib.check(self.lib.vsmpc_create_ex(ctypes.byref(self._ccfg), device, max_batch, L.RUNTIME_MODES[runtime],
+                                                ctypes.byref(self._h)), "vsmpc_create_ex")
         self.device = device
         self.max_batch = max_batch
         self.n_var = self.lib.vsmpc_num_variables(self._h)
@@ -67,6 +76,11 @@ class BatchedVSMPC:
     @property
     def kernel_name(self) -> str:
         return self.lib.vsmpc_kernel_name(self._h).decode()
+
+    @property
+    def uses_runtime_kernel(self) -> bool:
+        """True when this handle solves with the runtime-sized kernel instead of a tuned per-horizon instantiation."""
+        return self.kernel_name == L.RUNTIME_KERNEL_NAME
 
     # ---- host-buffer entry (vsmpc_solve_batch)
     def solve(self, inputs: np.ndarray):
