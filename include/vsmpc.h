@@ -137,9 +137,12 @@ int vsmpc_create(const vsmpc_config* cfg, int device, int max_batch, vsmpc_handl
  * vsmpc_provider_batch; vsmpc_kernel_name returns "solve_kernel_rt" and vsmpc_condensed_dim NP.  vsmpc_set_kernel_form
  * accepts form 0 only; vsmpc_debug_condensed and vsmpc_debug_phase_cycles return VSMPC_ERR_UNSUPPORTED_CONFIG.
  * Environment: VSMPC_RUNTIME_HORIZON=1 makes vsmpc_create behave as vsmpc_create_ex(.., VSMPC_CREATE_RUNTIME_FALLBACK, ..),
- * so that unmodified programs (the C++ wrapper, the pybind11 shim) run any horizon. */
+ * so that unmodified programs (the C++ wrapper, the pybind11 shim) run any horizon.
+ * VSMPC_CREATE_SENSITIVITY (with any of the above, on tuned and runtime handles) also allocates the workspace of
+ * vsmpc_sensitivity_batch below; handles created without it allocate nothing for it. */
 #define VSMPC_CREATE_RUNTIME_FALLBACK 0x1u
 #define VSMPC_CREATE_RUNTIME_ONLY 0x2u
+#define VSMPC_CREATE_SENSITIVITY 0x4u
 int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned flags, vsmpc_handle** out);
 void vsmpc_destroy(vsmpc_handle* h);
 
@@ -162,6 +165,40 @@ int vsmpc_solve_batch(vsmpc_handle* h, const double* in, int batch, double* x, d
  * no synchronisation): the form a resident batch driver uses.  batch <= vsmpc_max_batch(h). */
 int vsmpc_solve_batch_device(vsmpc_handle* h, const double* d_in, int batch, double* d_x,
                              double* d_first_move, int* d_status, int* d_iters, void* stream);
+
+/*
+ * Sensitivities of the solution to the measured state X0 (in[VSMPC_IN_X0 .. +26]).  X0 enters the QP only through the
+ * initial-state rows, and the QP is solved exactly, so near a non-degenerate solution x* is an affine function of X0;
+ * its Jacobian is one more solve with the final active set ("Sensitivities").  Needs a handle created with
+ * VSMPC_CREATE_SENSITIVITY (otherwise VSMPC_ERR_UNSUPPORTED_CONFIG): it solves with sens_kernel_rt, the runtime-sized
+ * kernel with 26 more condensed columns, whose workspace is (NPS (NPS + 1) / 2) doubles per instance of max_batch,
+ * NPS = NP + 26 (87 KB at the paper horizon, 1.0 MB at (40, 2, 40)).  vsmpc_set_kernel_form does not affect it.
+ * Per instance:
+ *   x, first_move, status, iters   what vsmpc_solve_batch returns (bit for bit on a runtime handle, to rounding on a
+ *                                  tuned one, with the same iterations)
+ *   dx_dx0[nVar * 26]   row-major: entry i * 26 + j = d x_i / d X0_j, x in the reference variable order
+ *   dfm_dx0[24 * 26]    rows of the first-move block; the throttle-percent rows are 0 where the clamp to [0, 100] is active
+ *   active[NV]          final throttle states: 0 free, -1 at throttleMin, +1 at throttleMax, 2 pinned by the hold
+ *   sens_flags          VSMPC_SENS_DEGENERATE: a non-pinned throttle is weakly active (bound, |reduced gradient| <=
+ *                       VSMPC_SENS_GRAD_TOL (1 + max |s|), s the throttles' reduced gradient at v = 0) or nearly active (free,
+ *                       within VSMPC_SENS_BOUND_TOL (1 + |v|) of a bound): the Jacobian is still written, the derivative of
+ *                       the final active set's affine piece, i.e. one-sided;
+ *                       VSMPC_SENS_UNSOLVED: status is not Solved, the Jacobian rows are zero
+ * NV = vsmpc_num_throttle_unknowns(h) = 4 (HC - nS + 1).  Every output except status may be NULL.
+ */
+#define VSMPC_SENS_DEGENERATE 0x1
+#define VSMPC_SENS_UNSOLVED 0x2
+#define VSMPC_SENS_GRAD_TOL 1e-8
+#define VSMPC_SENS_BOUND_TOL 1e-9
+int vsmpc_num_throttle_unknowns(const vsmpc_handle* h);
+/* Host buffers; returns after the results are in them.  Errors as vsmpc_solve_batch. */
+int vsmpc_sensitivity_batch(vsmpc_handle* h, const double* in, int batch, double* x, double* first_move, int* status,
+                            int* iters, double* dx_dx0, double* dfm_dx0, int* active, int* sens_flags, void* stream);
+/* Same, all pointers are DEVICE pointers and the call only enqueues work on `stream`.  Launches of one handle share its
+ * workspace: they must be ordered (one stream at a time). */
+int vsmpc_sensitivity_batch_device(vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_first_move,
+                                   int* d_status, int* d_iters, double* d_dx_dx0, double* d_dfm_dx0, int* d_active,
+                                   int* d_sens_flags, void* stream);
 
 /* Parity split of the path: only the per-tick linearisation + discretisation, i.e.
  * SystemDynamicVS::updateDynamicMatrices/getAMatrix/getBJointsMatrix/getBThrottleMatrix/getCVector

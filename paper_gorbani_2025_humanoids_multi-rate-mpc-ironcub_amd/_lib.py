@@ -19,7 +19,8 @@ EXPORTS = (
     "vsmpc_rollout_create", "vsmpc_rollout_destroy", "vsmpc_rollout_reset", "vsmpc_rollout_run",
     "vsmpc_rollout_get_state", "vsmpc_rollout_get_records", "vsmpc_alloc_host", "vsmpc_free_host",
     "vsmpc_set_kernel_form", "vsmpc_set_kinematics_options", "vsmpc_provider_batch", "vsmpc_rollout_set_attitude_tracks",
-    "vsmpc_tick", "vsmpc_rollout_set_tree",
+    "vsmpc_tick", "vsmpc_rollout_set_tree", "vsmpc_num_throttle_unknowns", "vsmpc_sensitivity_batch",
+    "vsmpc_sensitivity_batch_device",
     # include/vsmpc_jet.h
     "vsmpc_jet_create", "vsmpc_jet_destroy", "vsmpc_jet_nn_step", "vsmpc_jet_nn_sequence", "vsmpc_jet_ekf_update",
     "vsmpc_jet_plant_run", "vsmpc_jet_plant_run_device", "vsmpc_rollout_set_jet_plant",
@@ -53,13 +54,18 @@ def load():
     lib.vsmpc_destroy.argtypes = [vp]
     lib.vsmpc_destroy.restype = None
     for name in ("vsmpc_num_variables", "vsmpc_num_constraints", "vsmpc_input_doubles", "vsmpc_max_batch",
-                 "vsmpc_condensed_dim"):
+                 "vsmpc_condensed_dim", "vsmpc_num_throttle_unknowns"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = c_int
     lib.vsmpc_solve_batch.argtypes = [vp, dp, c_int, dp, dp, vp, vp, vp]
     lib.vsmpc_solve_batch.restype = c_int
     lib.vsmpc_solve_batch_device.argtypes = [vp, dp, c_int, dp, dp, vp, vp, vp]
     lib.vsmpc_solve_batch_device.restype = c_int
+    # h, in, batch, x, first_move, status, iters, dx_dx0, dfm_dx0, active, sens_flags, stream
+    lib.vsmpc_sensitivity_batch.argtypes = [vp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp, vp]
+    lib.vsmpc_sensitivity_batch.restype = c_int
+    lib.vsmpc_sensitivity_batch_device.argtypes = [vp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp, vp]
+    lib.vsmpc_sensitivity_batch_device.restype = c_int
     lib.vsmpc_linearize_batch.argtypes = [vp, dp, c_int, dp, dp, dp, dp, dp]
     lib.vsmpc_linearize_batch.restype = c_int
     lib.vsmpc_assemble_dense.argtypes = [vp, dp, dp, dp, dp, dp, dp]

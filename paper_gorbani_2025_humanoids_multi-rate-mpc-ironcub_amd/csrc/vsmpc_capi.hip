@@ -21,7 +21,16 @@ struct vsmpc_handle {
     int runtime;     // solve with the runtime-sized kernel (vsmpc_create_ex)
     RtDims rt;       // its sizes (runtime handles only)
     double* d_ws;    // its per-instance workspace, max_batch x rt.ws_doubles
-    int form;        // condensing form of the solve kernel (vsmpc_set_kernel_form)
+    // VSMPC_CREATE_SENSITIVITY: sizes of sens_kernel_rt, its workspace (max_batch x rts.ws_doubles) and the staging of the
+    // host-pointer entry (SENS_CHUNK instances at a time)
+    int sens;
+    RtDims rts;
+    double* d_sws;
+    double* d_sdx;
+    double* d_sdfm;
+    int* d_sact;
+    int* d_sflags;
+    int form;       // condensing form of the solve kernel (vsmpc_set_kernel_form)
     KinOpts kin;     // vsmpc_set_kinematics_options
     int device;
     int max_batch;
@@ -60,6 +69,8 @@ constexpr int ZC_MAX = 8;  // largest batch served through the mapped staging bu
 constexpr int PIPE_CHUNK = VS_PIPE_CHUNK;   // instances per chunk of the pipelined host-pointer entry
 constexpr int PIPE_STREAMS = VS_PIPE_STREAMS;
 static_assert(PIPE_STREAMS >= 1 && PIPE_STREAMS <= 4, "vsmpc_handle::pipe holds four streams");
+constexpr int SENS_CHUNK = 256;   // instances per chunk of vsmpc_sensitivity_batch (dx_dx0 staging: 82 MB at (40, 2, 40))
+constexpr int SENS_NPAR = VSMPC_N_STATES;
 
 // resident closed-loop state of a batch (uses the handle's record / first-move / status buffers as its per-tick scratch)
 struct vsmpc_rollout {
@@ -219,15 +230,19 @@ int vsmpc_create(const vsmpc_config* cfg, int device, int max_batch, vsmpc_handl
 int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned flags, vsmpc_handle** out) {
     if (cfg == nullptr || out == nullptr || max_batch <= 0) return VSMPC_ERR_INVALID_ARG;
     *out = nullptr;
-    if ((flags & ~unsigned(VSMPC_CREATE_RUNTIME_FALLBACK | VSMPC_CREATE_RUNTIME_ONLY)) != 0u) return VSMPC_ERR_INVALID_ARG;
+    const unsigned kernel_flags = VSMPC_CREATE_RUNTIME_FALLBACK | VSMPC_CREATE_RUNTIME_ONLY;
+    if ((flags & ~(kernel_flags | VSMPC_CREATE_SENSITIVITY)) != 0u) return VSMPC_ERR_INVALID_ARG;
     if (!config_valid(*cfg)) return VSMPC_ERR_INVALID_ARG;
     const int variant = (flags & VSMPC_CREATE_RUNTIME_ONLY)
                             ? int(VARIANT_NONE)
                             : select_variant(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon);
-    if (variant == VARIANT_NONE && flags == 0u) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    if (variant == VARIANT_NONE && (flags & kernel_flags) == 0u) return VSMPC_ERR_UNSUPPORTED_CONFIG;
     const bool runtime = variant == VARIANT_NONE;
     const RtDims rt = runtime_dims(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon);
     if (runtime && runtime_lds_bytes(rt) > RT_MAX_LDS) return VSMPC_ERR_UNSUPPORTED_CONFIG;   // (not for a valid config)
+    const bool sens = (flags & VSMPC_CREATE_SENSITIVITY) != 0u;
+    const RtDims rts = runtime_dims(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon, true);
+    if (sens && runtime_lds_bytes(rts) > RT_MAX_LDS) return VSMPC_ERR_UNSUPPORTED_CONFIG;     // (not for a valid config)
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return VSMPC_ERR_INVALID_ARG;
@@ -241,6 +256,8 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     h->variant = variant;
     h->runtime = runtime ? 1 : 0;
     h->rt = rt;
+    h->sens = sens ? 1 : 0;
+    h->rts = rts;
     h->form = runtime ? 0 : initial_kernel_form();
     for (int i = 0; i < VSMPC_N_JOINTS; ++i) h->kin.sel[i] = 3 + i;   // the shipped robot: joints 3..10
     h->kin.constant_lambda = 0;
@@ -266,6 +283,14 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     if (e == hipSuccess) e = hipMalloc(&h->d_kout, B * VSMPC_KIN_OUT * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&h->d_stamps, B * 16 * sizeof(unsigned long long));
     if (e == hipSuccess && runtime) e = hipMalloc(&h->d_ws, B * size_t(rt.ws_doubles) * sizeof(double));
+    if (sens) {
+        const size_t C = std::min(B, size_t(SENS_CHUNK));
+        if (e == hipSuccess) e = hipMalloc(&h->d_sws, B * size_t(rts.ws_doubles) * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(&h->d_sdx, C * h->n_var * SENS_NPAR * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(&h->d_sdfm, C * VSMPC_FM_SIZE * SENS_NPAR * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(&h->d_sact, C * rts.nv * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc(&h->d_sflags, C * sizeof(int));
+    }
     for (int i = 0; i < PIPE_STREAMS && e == hipSuccess; ++i) {
         e = hipStreamCreateWithFlags(&h->pipe[i], hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&h->pipe_done[i], hipEventDisableTiming);
@@ -300,6 +325,11 @@ void vsmpc_destroy(vsmpc_handle* h) {
     if (h->d_kout) (void)hipFree(h->d_kout);
     if (h->d_stamps) (void)hipFree(h->d_stamps);
     if (h->d_ws) (void)hipFree(h->d_ws);
+    if (h->d_sws) (void)hipFree(h->d_sws);
+    if (h->d_sdx) (void)hipFree(h->d_sdx);
+    if (h->d_sdfm) (void)hipFree(h->d_sdfm);
+    if (h->d_sact) (void)hipFree(h->d_sact);
+    if (h->d_sflags) (void)hipFree(h->d_sflags);
     for (int i = 0; i < PIPE_STREAMS; ++i) {
         if (h->pipe[i]) (void)hipStreamDestroy(h->pipe[i]);
         if (h->pipe_done[i]) (void)hipEventDestroy(h->pipe_done[i]);
@@ -403,6 +433,61 @@ int vsmpc_solve_batch(vsmpc_handle* h, const double* in, int batch, double* x, d
         if (err == hipSuccess) err = e;
     }
     HIP_TRY(err);
+    return VSMPC_OK;
+}
+
+int vsmpc_num_throttle_unknowns(const vsmpc_handle* h) { return h ? h->rt.nv : VSMPC_ERR_INVALID_ARG; }
+
+int vsmpc_sensitivity_batch_device(vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_first_move,
+                                   int* d_status, int* d_iters, double* d_dx_dx0, double* d_dfm_dx0, int* d_active,
+                                   int* d_sens_flags, void* stream) {
+    if (h == nullptr || d_in == nullptr || d_status == nullptr || batch < 0) return VSMPC_ERR_INVALID_ARG;
+    if (!h->sens) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    if (batch == 0) return VSMPC_OK;
+    ON_DEVICE(h->device);
+    HIP_TRY(launch_sensitivity_runtime(h->rts, h->dev, d_in, batch, h->d_sws, d_x, d_first_move, d_status, d_iters, d_dx_dx0,
+                                       d_dfm_dx0, d_active, d_sens_flags, static_cast<hipStream_t>(stream)));
+    return VSMPC_OK;
+}
+
+int vsmpc_sensitivity_batch(vsmpc_handle* h, const double* in, int batch, double* x, double* first_move, int* status,
+                            int* iters, double* dx_dx0, double* dfm_dx0, int* active, int* sens_flags, void* stream) {
+    if (h == nullptr || in == nullptr || status == nullptr || batch < 0) return VSMPC_ERR_INVALID_ARG;
+    if (!h->sens) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    if (batch == 0) return VSMPC_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ON_DEVICE(h->device);
+    const size_t NV = size_t(h->rts.nv), J = SENS_NPAR, FM = VSMPC_FM_SIZE;
+    // chunks of SENS_CHUNK instances in stream order: the staging of one chunk is read back before the next overwrites it
+    hipError_t err = hipSuccess;
+    auto ok = [&](hipError_t e) { if (e != hipSuccess && err == hipSuccess) err = e; return err == hipSuccess; };
+    for (int first = 0; first < batch && err == hipSuccess; first += SENS_CHUNK) {
+        const int n = std::min(SENS_CHUNK, batch - first);
+        const size_t o = size_t(first), N = size_t(n);
+        if (!ok(hipMemcpyAsync(h->d_in + o * h->n_in, in + o * h->n_in, N * h->n_in * sizeof(double), hipMemcpyHostToDevice, s)))
+            break;
+        if (!ok(launch_sensitivity_runtime(h->rts, h->dev, h->d_in + o * h->n_in, n, h->d_sws + o * size_t(h->rts.ws_doubles),
+                                           x ? h->d_x + o * h->n_var : nullptr, first_move ? h->d_fm + o * FM : nullptr,
+                                           h->d_status + o, iters ? h->d_iters + o : nullptr, dx_dx0 ? h->d_sdx : nullptr,
+                                           dfm_dx0 ? h->d_sdfm : nullptr, active ? h->d_sact : nullptr,
+                                           sens_flags ? h->d_sflags : nullptr, s)))
+            break;
+        if (x) ok(hipMemcpyAsync(x + o * h->n_var, h->d_x + o * h->n_var, N * h->n_var * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (first_move)
+            ok(hipMemcpyAsync(first_move + o * FM, h->d_fm + o * FM, N * FM * sizeof(double), hipMemcpyDeviceToHost, s));
+        ok(hipMemcpyAsync(status + o, h->d_status + o, N * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (iters) ok(hipMemcpyAsync(iters + o, h->d_iters + o, N * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (dx_dx0)
+            ok(hipMemcpyAsync(dx_dx0 + o * h->n_var * J, h->d_sdx, N * h->n_var * J * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (dfm_dx0) ok(hipMemcpyAsync(dfm_dx0 + o * FM * J, h->d_sdfm, N * FM * J * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (active) ok(hipMemcpyAsync(active + o * NV, h->d_sact, N * NV * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (sens_flags) ok(hipMemcpyAsync(sens_flags + o, h->d_sflags, N * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    const hipError_t e = hipStreamSynchronize(s);   // nothing returns while copies into the caller's buffers are queued
+    if (err == hipSuccess) err = e;
+    if (err != hipSuccess) return hip_fail(err, "vsmpc_sensitivity_batch");
     return VSMPC_OK;
 }
 

@@ -146,6 +146,12 @@ struct Jet {
         u = u * sgU + muU;
         return u < 0.0 ? 0.0 : (u > 100.0 ? 100.0 : u);
     }
+    // derivative of throttle_of_v: sigma_U / sqrt(1 + 4 c12 v), 0 where the clamp to [0, 100] is active
+    static VS_HD double dthrottle_dv(double vv) {
+        const double r = sqrt(1.0 + 4.0 * c12 * vv);
+        const double u = (-1.0 + r) / (2.0 * c12) * sgU + muU;
+        return (u < 0.0 || u > 100.0) ? 0.0 : sgU / r;
+    }
     // JetDynamicVS::computeF/computeG/compute_dh_dT/compute_dh_dTDot (systemDynamicsVSMPC.cpp:431-461)
     static VS_HD double F(double T, double Td) { return f(stdT(T), stdTd(Td)) * sgT; }
     static VS_HD double G(double T, double Td) { return g(stdT(T), stdTd(Td)) * sgT; }

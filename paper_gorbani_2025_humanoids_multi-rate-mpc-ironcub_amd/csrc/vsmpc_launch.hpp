@@ -53,12 +53,18 @@ struct RtDims {
     int lds_doubles;      // dynamic LDS of one workgroup (doubles)
 };
 constexpr size_t RT_MAX_LDS = 160 * 1024;
-RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon);
+// sensitivity: the sizes of sens_kernel_rt (NP = NZ + 1 + 26: the parameter columns of d/dX0)
+RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon, bool sensitivity = false);
 size_t runtime_lds_bytes(const RtDims& d);
 const char* runtime_kernel_name();
 // d_ws: workspace of the launch's first instance (instance b of the launch uses d_ws + b * d.ws_doubles)
 hipError_t launch_solve_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws, double* d_x,
                                 double* d_fm, int* d_status, int* d_iters, hipStream_t stream);
+// sens_kernel_rt (vsmpc_sensitivity_batch): the solve outputs plus dx_dx0 [batch][nVar][26], dfm_dx0 [batch][24][26],
+// active [batch][NV] and the VSMPC_SENS_* flags [batch]; d from runtime_dims(.., true), d_ws as for the solve
+hipError_t launch_sensitivity_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws,
+                                      double* d_x, double* d_fm, int* d_status, int* d_iters, double* d_dx, double* d_dfm,
+                                      int* d_active, int* d_flags, hipStream_t stream);
 hipError_t launch_linearize_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,
                                     double* Bt, double* c, hipStream_t stream);
 

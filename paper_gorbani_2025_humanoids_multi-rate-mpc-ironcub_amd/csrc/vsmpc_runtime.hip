@@ -26,6 +26,20 @@
 // triangle row by row (element (i, j), j <= i, at i (i + 1) / 2 + j): NP (NP + 1) / 2 doubles, allocated at create.
 // LDS holds the record, the linearisation, one stage of Y, the compacted S_FF of the box QP and the vectors.
 // No private array is indexed by a runtime value: the two columns of a thread are unrolled at compile time.
+//
+// sens_kernel_rt (vsmpc_sensitivity_batch) is the same body (vsmpc_runtime_body.inc) with SENS = true; solve_kernel_rt's
+// code is not changed by it.  X0 enters the QP only through the initial-state rows, so the solution's Jacobian with
+// respect to X0 is that of the final active set's affine piece ("Sensitivities"; executable model:
+// tests/sensitivity_model.py):
+//   P1  26 parameter columns after the affine one (NP = NZ + 27 rows): column NZ + 1 + i starts from X_0 = e_i, takes no
+//       input, no c and no reference, so that C's parameter rows hold F = d(condensed gradient)/dX0
+//   P2  nothing: the input costs and their gradient terms belong to the affine row
+//   P3  the same Cholesky reduces the parameter rows to F~ (throttle columns) and l~ (joint columns)
+//   P4  after the box QP, on a Solved exit, with the factor of S_FF the last iteration left in LDS (the final free set):
+//       S_FF dv_F = -F~_F, dv = 0 on bound and pinned throttles
+//   P5  L_jj^T du = -(L_vj^T dv + l~)
+//   P6  dX_0 = I, dX_{k+1} = dX_k + dt_k (A dX_k + Bj dU + Bt dV)
+// The 26 right-hand sides of P4 / P5 are solved in place in the parameter rows of the workspace, which then hold dz/dX0.
 #include <atomic>
 
 #include "vsmpc_launch.hpp"
@@ -36,7 +50,8 @@ namespace vsmpc {
 namespace {
 
 constexpr int RT_BLOCK = 256;
-constexpr int RT_CPT = 2;                              // columns per thread: NP <= 8 * 40 + 4 * 39 + 1 = 477 < 512
+constexpr int RT_CPT = 2;    // columns per thread: NP <= 8 * 40 + 4 * 39 + 1 = 477 (+ 26 parameter columns: 503) < 512
+constexpr int RT_NPAR = NX;  // parameter columns of sens_kernel_rt: one per entry of X0
 constexpr int RT_LIN = NX * NX + NX * NJ + NX * NTH + 28;   // A | Bj | Bt | c (p0_linearize's contiguous block)
 struct RtTag {};                                       // p0_linearize does not use its dimension parameter
 constexpr int AS_PATIENCE_RT = 10;                     // the oracle's patience (vsmpc_kernels.hip: AS_PATIENCE)
@@ -89,7 +104,7 @@ VS_DEV RtSmem rt_smem(const RtDims& d, double* base) {
     s.state = reinterpret_cast<int*>(p); p += (d.nv + 1) / 2 + 1;
     s.idx = reinterpret_cast<int*>(p);   p += (d.nv + 1) / 2 + 1;
     s.flags = reinterpret_cast<int*>(p); p += 4;   // F_* slots
-    s.big = p;   // max(18 NP, NV (NV + 1) / 2)
+    s.big = p;   // max(18 NP, NV (NV + 1) / 2), and 2 x 26 x 26 with SENS
     return s;
 }
 
@@ -98,331 +113,46 @@ VS_DEV double rt_S(const double* __restrict__ M, int nu, int p, int q) {
     return p >= q ? M[tri(nu + p) + nu + q] : M[tri(nu + q) + nu + p];
 }
 
+// the largest dynamic LDS once per kernel and device: every horizon launches under it
+constexpr int RT_MAX_DEV = 64;
+hipError_t rt_allow_lds(const void* kernel, std::atomic<bool> (&attr_set)[RT_MAX_DEV], const RtDims& d) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= RT_MAX_DEV) return hipErrorInvalidDevice;
+    if (runtime_lds_bytes(d) > RT_MAX_LDS) return hipErrorInvalidValue;
+    if (!attr_set[dev].load(std::memory_order_acquire)) {
+        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(RT_MAX_LDS));
+        if (e != hipSuccess) return e;
+        attr_set[dev].store(true, std::memory_order_release);
+    }
+    return hipSuccess;
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(RT_BLOCK) void solve_kernel_rt(DevCfg cfg, RtDims d, const double* __restrict__ in,
                                                             double* __restrict__ ws, double* __restrict__ xout,
                                                             double* __restrict__ fmout, int* __restrict__ status_out,
                                                             int* __restrict__ iters_out) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const RtSmem s = rt_smem(d, smem);
-    const int tid = threadIdx.x, inst = blockIdx.x;
-    double* __restrict__ M = ws + size_t(inst) * size_t(d.ws_doubles);
-    const int NP = d.np, NZ = d.nz, NU = d.nu, NV = d.nv;
+    constexpr bool SENS = false;
+    double* const dxout = nullptr;
+    double* const dfmout = nullptr;
+    int* const active_out = nullptr;
+    int* const flags_out = nullptr;
+#include "vsmpc_runtime_body.inc"
+}
 
-    // ---- P0: record, configuration, linearisation
-    for (int i = tid; i < d.nin; i += RT_BLOCK) s.in[i] = in[size_t(inst) * d.nin + i];
-    if (tid < d.n) s.dt[tid] = cfg.dt[tid];
-    if (tid >= 64 && tid < 64 + NWROWS) s.sq[tid - 64] = cfg.sq[tid - 64];
-    if (tid == 0) { s.flags[F_STATUS] = VSMPC_STATUS_MAX_ITER; s.flags[F_ITERS] = 0; }
-    __syncthreads();
-    double* sA = s.lin;
-    double* sBj = sA + NX * NX;
-    double* sBt = sBj + NX * NJ;
-    double* sC = sBt + NX * NTH;
-    p0_linearize<RtTag>(cfg.use_jet, s.in, sA, sBj, sBt, sC, s.vprev, tid, RT_BLOCK);
-
-    // ---- P1: sensitivity recursion of every condensed column, C = sum_k Y_k^T Y_k
-    {
-        double X[RT_CPT][NX];
-        const double* src[RT_CPT];
-        int stride[RT_CPT], kind[RT_CPT], blk[RT_CPT];   // kind: 0 joint, 1 throttle, 2 affine, 3 none
-#pragma unroll
-        for (int u = 0; u < RT_CPT; ++u) {
-            const int c = tid + u * RT_BLOCK;
-            kind[u] = c < NU ? 0 : (c < NZ ? 1 : (c == NZ ? 2 : 3));
-            blk[u] = kind[u] == 0 ? c >> 3 : (kind[u] == 1 ? (c - NU) >> 2 : 0);
-            src[u] = kind[u] == 0 ? sBj + (c & 7) : (kind[u] == 1 ? sBt + ((c - NU) & 3) : sC);
-            stride[u] = kind[u] == 0 ? NJ : (kind[u] == 1 ? NTH : 1);
-#pragma unroll
-            for (int r = 0; r < NX; ++r) X[u][r] = kind[u] == 2 ? s.in[VSMPC_IN_X0 + r] : 0.0;
-        }
-        double* Y = s.big;   // Y[w * NP + c]
-        for (int k = 0; k < d.n; ++k) {
-            const double dt = s.dt[k];
-            const int jb = rt_joint_block(d, k), tb = rt_throttle_block(d, k);
-            const int i = k + 1;                                        // node of X_{k+1}
-            const int col = (i - 1) < d.ns ? 0 : (i - 1) - d.ns;      // reference window column (costsVSMPC.cpp:191-200)
-#pragma unroll
-            for (int u = 0; u < RT_CPT; ++u) {
-                if (kind[u] == 3) continue;
-                const bool on = kind[u] == 2 || (kind[u] == 0 && blk[u] == jb) || (kind[u] == 1 && blk[u] == tb);
-                double nx[NX];
-#pragma unroll
-                for (int r = 0; r < NX; ++r) {
-                    double a = on ? src[u][r * stride[u]] : 0.0;
-#pragma unroll
-                    for (int q = 0; q < NX; ++q)
-                        if (a_nz(r, q)) a = fma(sA[r * NX + q], X[u][q], a);
-                    nx[r] = fma(dt, a, X[u][r]);
-                }
-#pragma unroll
-                for (int r = 0; r < NX; ++r) X[u][r] = nx[r];
-                const int c = tid + u * RT_BLOCK;
-#pragma unroll
-                for (int w = 0; w < NWROWS; ++w) {
-                    const int r = wrow(w);
-                    const double ref = (kind[u] == 2 && r < 12) ? s.in[VSMPC_IN_XREF + col * 12 + r] : 0.0;
-                    Y[w * NP + c] = s.sq[w] * (X[u][r] - ref);
-                }
-            }
-            __syncthreads();
-            int ei = 0, ej = 0;
-            tri_advance(ei, ej, tid);
-            for (size_t e = tid; e < size_t(d.ntri); e += RT_BLOCK) {
-                double acc = 0.0;
-#pragma unroll
-                for (int w = 0; w < NWROWS; ++w) acc = fma(Y[w * NP + ei], Y[w * NP + ej], acc);
-                M[e] = k == 0 ? acc : M[e] + acc;
-                tri_advance(ei, ej, RT_BLOCK);
-            }
-            __syncthreads();
-        }
-    }
-
-    // ---- P2: input costs (every entry touched by exactly one thread), max |gradient| for the release tolerance
-    {
-        const double w_thr = cfg.w_thr;
-        for (int c = tid; c < NZ; c += RT_BLOCK) {
-            if (c < NU) {
-                const int j = c & 7;
-                M[tri(c) + c] += cfg.wj[j];                                   // costsVSMPC.cpp:375-381,564-571
-                M[tri(NZ) + c] += cfg.w_reg * s.in[VSMPC_IN_QERR + j];        // :574-589
-            } else {
-                const int q = c - NU, b = q >> 2, r = q & 3;
-                const int npairs = (b < d.nvb - 1 ? 1 : 0) + (b > 0 ? 1 : 0);  // first differences (:383-409)
-                double diag = M[tri(c) + c];
-                for (int p = 0; p < npairs; ++p) diag += w_thr;
-                if (b == 0) diag += cfg.w_init;                                // ThrottleInitialValueCost (:468-487)
-                M[tri(c) + c] = diag;
-                if (b > 0) M[tri(c) + c - 4] -= w_thr;
-                if (b == 0) M[tri(NZ) + c] += -cfg.w_init * s.vprev[r];
-            }
-        }
-        __syncthreads();
-        double gm = 0.0;
-        for (int c = tid; c < NZ; c += RT_BLOCK) gm = fmax(gm, fabs(M[tri(NZ) + c]));
-        s.red[tid] = gm;
-        __syncthreads();
-        for (int h = RT_BLOCK / 2; h > 0; h >>= 1) {
-            if (tid < h) s.red[tid] = fmax(s.red[tid], s.red[tid + h]);
-            __syncthreads();
-        }
-    }
-    const double gtol = 1e-10 * (1.0 + s.red[0]);
-
-    // ---- P3: Cholesky of the joint columns; the trailing block becomes (S, s)
-    bool bad = false;
-    for (int j = 0; j < NU; ++j) {
-        const double piv = M[tri(j) + j];
-        if (!(piv > 0.0)) { bad = true; break; }   // (every thread reads the same value: a uniform exit)
-        const double l = sqrt(piv), il = 1.0 / l;
-        for (int i = j + 1 + tid; i < NP; i += RT_BLOCK) {
-            const double v = M[tri(i) + j] * il;
-            M[tri(i) + j] = v;
-            s.col[i] = v;
-        }
-        __syncthreads();
-        if (tid == 0) M[tri(j) + j] = l;           // (after the barrier: every thread has read the pivot)
-        const int m = NP - 1 - j;                  // trailing rows / columns j + 1 .. NP - 1
-        const size_t nt = size_t(m) * (m + 1) / 2;
-        int ei = 0, ej = 0;
-        tri_advance(ei, ej, tid);
-        for (size_t e = tid; e < nt; e += RT_BLOCK) {
-            const int gi = j + 1 + ei, gj = j + 1 + ej;
-            M[tri(gi) + gj] -= s.col[gi] * s.col[gj];
-            tri_advance(ei, ej, RT_BLOCK);
-        }
-        __syncthreads();
-    }
-
-    // ---- P4: box QP on the throttles, block principal pivoting (executable model: tests/runtime_model.py box_qp)
-    const bool hold = s.in[VSMPC_IN_HOLD] != 0.0;
-    const double vmin = cfg.vmin, vmax = cfg.vmax;
-    double* z = s.z;              // z[0..NU) joints, z[NU..NZ) throttles
-    double* zv = z + NU;
-    double* sS = M + tri(NZ) + NU;  // reduced gradient s
-    if (!bad) {
-        for (int p = tid; p < NV; p += RT_BLOCK) s.state[p] = (hold && p < NTH) ? -1 : 0;  // the hold pins v0 at v_prev
-        if (tid == 0) { s.flags[F_BEST] = NV + 1; s.flags[F_PATIENCE] = AS_PATIENCE_RT; }
-        __syncthreads();
-        for (int it = 0; it < cfg.max_as_iter; ++it) {
-            // bound values, free list
-            for (int p = tid; p < NV; p += RT_BLOCK) {
-                const bool fixed = hold && p < NTH;
-                const int st = s.state[p];
-                if (st != 0) zv[p] = fixed ? s.vprev[p] : (st < 0 ? vmin : vmax);
-            }
-            if (tid == 0) {
-                int nf = 0;
-                for (int p = 0; p < NV; ++p)
-                    if (s.state[p] == 0) s.idx[nf++] = p;
-                s.flags[F_NF] = nf;
-            }
-            __syncthreads();
-            const int nf = s.flags[F_NF];
-            double* K = s.big;
-            double* rhs = s.vec0;
-            double* y = s.vec1;
-            // rhs_F = -(s_F + S_FB z_B); K = S_FF (packed lower)
-            for (int a = tid; a < nf; a += RT_BLOCK) {
-                const int p = s.idx[a];
-                double acc = sS[p];
-                for (int q = 0; q < NV; ++q)
-                    if (s.state[q] != 0) acc = fma(rt_S(M, NU, p, q), zv[q], acc);
-                rhs[a] = -acc;
-            }
-            {
-                const size_t nk = size_t(nf) * (nf + 1) / 2;
-                int ei = 0, ej = 0;
-                tri_advance(ei, ej, tid);
-                for (size_t e = tid; e < nk; e += RT_BLOCK) {
-                    K[e] = rt_S(M, NU, s.idx[ei], s.idx[ej]);
-                    tri_advance(ei, ej, RT_BLOCK);
-                }
-            }
-            __syncthreads();
-            // Cholesky of K
-            for (int j = 0; j < nf; ++j) {
-                const double piv = K[tri(j) + j];
-                if (!(piv > 0.0)) { bad = true; break; }
-                const double l = sqrt(piv), il = 1.0 / l;
-                __syncthreads();   // everyone has read the pivot before it is overwritten
-                for (int i = j + 1 + tid; i < nf; i += RT_BLOCK) K[tri(i) + j] *= il;
-                if (tid == 0) K[tri(j) + j] = l;
-                __syncthreads();
-                const int m = nf - 1 - j;
-                const size_t nt = size_t(m) * (m + 1) / 2;
-                int ei = 0, ej = 0;
-                tri_advance(ei, ej, tid);
-                for (size_t e = tid; e < nt; e += RT_BLOCK) {
-                    const int gi = j + 1 + ei, gj = j + 1 + ej;
-                    K[tri(gi) + gj] -= K[tri(gi) + j] * K[tri(gj) + j];
-                    tri_advance(ei, ej, RT_BLOCK);
-                }
-                __syncthreads();
-            }
-            if (bad) break;
-            // L y = rhs, then L^T v = y (v into y)
-            for (int j = 0; j < nf; ++j) {
-                const double yj = rhs[j] / K[tri(j) + j];
-                for (int i = j + 1 + tid; i < nf; i += RT_BLOCK) rhs[i] = fma(-K[tri(i) + j], yj, rhs[i]);
-                if (tid == 0) y[j] = yj;
-                __syncthreads();
-            }
-            for (int j = nf - 1; j >= 0; --j) {
-                const double vj = y[j] / K[tri(j) + j];
-                for (int i = tid; i < j; i += RT_BLOCK) y[i] = fma(-K[tri(j) + i], vj, y[i]);
-                __syncthreads();
-                if (tid == 0) zv[s.idx[j]] = vj;
-            }
-            __syncthreads();
-            // gradient of the reduced problem at z
-            double* grad = s.vec2;
-            for (int p = tid; p < NV; p += RT_BLOCK) {
-                double acc = sS[p];
-                for (int q = 0; q < NV; ++q) acc = fma(rt_S(M, NU, p, q), zv[q], acc);
-                grad[p] = acc;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int ninf = 0, last = -1;
-                for (int p = 0; p < NV; ++p) {
-                    const bool fixed = hold && p < NTH;
-                    const int st = s.state[p];
-                    const double tol = 1e-12 * (1.0 + fabs(zv[p]));
-                    const bool vlo = st == 0 && zv[p] < vmin - tol;
-                    const bool vhi = st == 0 && zv[p] > vmax + tol;
-                    const bool rel = !fixed && ((st == -1 && grad[p] < -gtol) || (st == 1 && grad[p] > gtol));
-                    if (vlo || vhi || rel) { ++ninf; last = p; }
-                }
-                s.flags[F_ITERS] = it + 1;
-                if (ninf == 0) {
-                    s.flags[F_STATUS] = VSMPC_STATUS_SOLVED;
-                } else {
-                    bool all = true;
-                    if (ninf < s.flags[F_BEST]) { s.flags[F_BEST] = ninf; s.flags[F_PATIENCE] = AS_PATIENCE_RT; }
-                    else if (s.flags[F_PATIENCE] > 0) { --s.flags[F_PATIENCE]; }
-                    else all = false;   // single pivot on the largest infeasible index
-                    for (int p = 0; p < NV; ++p) {
-                        if (!all && p != last) continue;
-                        const bool fixed = hold && p < NTH;
-                        const int st = s.state[p];
-                        const double tol = 1e-12 * (1.0 + fabs(zv[p]));
-                        if (st == 0 && zv[p] < vmin - tol) s.state[p] = -1;
-                        else if (st == 0 && zv[p] > vmax + tol) s.state[p] = 1;
-                        else if (!fixed && ((st == -1 && grad[p] < -gtol) || (st == 1 && grad[p] > gtol))) s.state[p] = 0;
-                    }
-                }
-            }
-            __syncthreads();
-            if (s.flags[F_STATUS] == VSMPC_STATUS_SOLVED) break;
-        }
-        __syncthreads();
-        // the final point: bound throttles exactly on their bound
-        for (int p = tid; p < NV; p += RT_BLOCK) {
-            const bool fixed = hold && p < NTH;
-            const int st = s.state[p];
-            if (st != 0) zv[p] = fixed ? s.vprev[p] : (st < 0 ? vmin : vmax);
-        }
-        __syncthreads();
-    }
-
-    // ---- P5: joints, L_jj^T u = -(L_vj^T v + l_j)
-    if (!bad) {
-        double* r = s.col;
-        for (int j = tid; j < NU; j += RT_BLOCK) {
-            double acc = M[tri(NZ) + j];
-            for (int p = 0; p < NV; ++p) acc = fma(M[tri(NU + p) + j], zv[p], acc);
-            r[j] = -acc;
-        }
-        __syncthreads();
-        for (int j = NU - 1; j >= 0; --j) {
-            const double uj = r[j] / M[tri(j) + j];
-            for (int i = tid; i < j; i += RT_BLOCK) r[i] = fma(-M[tri(j) + i], uj, r[i]);
-            __syncthreads();
-            if (tid == 0) z[j] = uj;
-        }
-        __syncthreads();
-    }
-
-    // ---- P6: state trajectory X_{k+1} = X_k + dt_k (A X_k + Bj U_jb + Bt v_tb + c), outputs
-    double* sX = s.x;
-    if (tid < NX) sX[tid] = s.in[VSMPC_IN_X0 + tid];
-    __syncthreads();
-    for (int k = 0; k < d.n; ++k) {
-        if (tid < NX) {
-            const int r = tid;
-            const double* U = z + NJ * rt_joint_block(d, k);
-            const double* V = zv + NTH * rt_throttle_block(d, k);
-            double a = sC[r];
-            for (int q = 0; q < NJ; ++q) a = fma(sBj[r * NJ + q], U[q], a);
-            for (int q = 0; q < NTH; ++q) a = fma(sBt[r * NTH + q], V[q], a);
-            for (int q = 0; q < NX; ++q) a = fma(sA[r * NX + q], sX[k * NX + q], a);
-            sX[(k + 1) * NX + r] = fma(s.dt[k], a, sX[k * NX + r]);
-        }
-        __syncthreads();
-    }
-    const int iters = s.flags[F_ITERS];
-    const int status = bad ? VSMPC_STATUS_NUMERICAL : s.flags[F_STATUS];
-    if (xout != nullptr) {
-        double* xo = xout + size_t(inst) * d.nvar;
-        for (int i = tid; i < d.nxs; i += RT_BLOCK) xo[i] = sX[i];
-        for (int i = tid; i < NZ; i += RT_BLOCK) xo[d.nxs + i] = bad ? 0.0 : z[i];
-    }
-    if (fmout != nullptr && tid < VSMPC_FM_SIZE) {
-        double v;
-        if (tid < 8) v = z[tid];                                      // delta q           (variableSamplingMPC.cpp:99)
-        else if (tid < 12) v = zv[tid - 8];                           // v0                (:100)
-        else if (tid < 16) v = Jet::throttle_of_v(zv[tid - 12]);      // throttle %        (:146-149)
-        else if (tid < 20) v = sX[NX + 12 + (tid - 16)];              // thrust, node 1    (:101)
-        else v = sX[NX + 16 + (tid - 20)];                            // thrust rate, node 1 (:102)
-        fmout[size_t(inst) * VSMPC_FM_SIZE + tid] = v;
-    }
-    if (tid == 0) {
-        status_out[inst] = status;
-        if (iters_out != nullptr) iters_out[inst] = bad ? 0 : iters;
-    }
+// solve_kernel_rt + the 26 parameter columns and the outputs dx_dx0 [nVar][26], dfm_dx0 [24][26], active [NV] and the
+// sensitivity flags (per instance, each may be null)
+__global__ __launch_bounds__(RT_BLOCK) void sens_kernel_rt(DevCfg cfg, RtDims d, const double* __restrict__ in,
+                                                           double* __restrict__ ws, double* __restrict__ xout,
+                                                           double* __restrict__ fmout, int* __restrict__ status_out,
+                                                           int* __restrict__ iters_out, double* __restrict__ dxout,
+                                                           double* __restrict__ dfmout, int* __restrict__ active_out,
+                                                           int* __restrict__ flags_out) {
+    constexpr bool SENS = true;
+#include "vsmpc_runtime_body.inc"
 }
 
 __global__ __launch_bounds__(256) void linearize_kernel_rt(DevCfg cfg, int n_in, const double* __restrict__ in,
@@ -445,7 +175,7 @@ __global__ __launch_bounds__(256) void linearize_kernel_rt(DevCfg cfg, int n_in,
     for (int i = tid; i < NX; i += 256) c[size_t(b) * NX + i] = sC[i];
 }
 
-RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon) {
+RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon, bool sensitivity) {
     RtDims d{};
     d.n = n_iter;
     d.ns = n_iter_small;
@@ -454,7 +184,7 @@ RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon) {
     d.nu = NJ * d.hc;
     d.nv = NTH * d.nvb;
     d.nz = d.nu + d.nv;
-    d.np = d.nz + 1;
+    d.np = d.nz + 1 + (sensitivity ? RT_NPAR : 0);
     d.nin = VSMPC_IN_XREF + 12 * (d.n - d.ns + 1);
     d.nxs = NX * (d.n + 1);
     d.nvar = d.nxs + d.nz;
@@ -462,8 +192,9 @@ RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon) {
     d.ws_doubles = d.ntri;
     const int fixed = ((d.nin + 1) & ~1) + RT_LIN + 4 + MAX_STAGES + NWROWS + 2 + NX * (d.n + 1) + ((d.nz + 1) & ~1) +
                       ((d.np + 1) & ~1) + RT_BLOCK + 3 * ((d.nv + 1) & ~1) + 2 * ((d.nv + 1) / 2 + 1) + 4;
-    const int ybuf = NWROWS * d.np, kbuf = d.nv * (d.nv + 1) / 2;
-    d.lds_doubles = fixed + (ybuf > kbuf ? ybuf : kbuf);
+    const int ybuf = NWROWS * d.np, kbuf = d.nv * (d.nv + 1) / 2, dxbuf = sensitivity ? 2 * NX * RT_NPAR : 0;
+    const int big = ybuf > kbuf ? ybuf : kbuf;
+    d.lds_doubles = fixed + (big > dxbuf ? big : dxbuf);
     return d;
 }
 
@@ -471,22 +202,23 @@ size_t runtime_lds_bytes(const RtDims& d) { return size_t(d.lds_doubles) * sizeo
 
 hipError_t launch_solve_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws, double* d_x,
                                 double* d_fm, int* d_status, int* d_iters, hipStream_t stream) {
-    constexpr int MAX_DEV = 64;
-    static std::atomic<bool> attr_set[MAX_DEV];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static std::atomic<bool> attr_set[RT_MAX_DEV];
+    const hipError_t e = rt_allow_lds(reinterpret_cast<const void*>(&solve_kernel_rt), attr_set, d);
     if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= MAX_DEV) return hipErrorInvalidDevice;
-    const size_t lds = runtime_lds_bytes(d);
-    if (lds > RT_MAX_LDS) return hipErrorInvalidValue;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {   // the largest size once: every horizon launches under it
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel_rt), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                int(RT_MAX_LDS));
-        if (e != hipSuccess) return e;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(solve_kernel_rt, dim3(batch), dim3(RT_BLOCK), lds, stream, cfg, d, d_in, d_ws, d_x, d_fm, d_status,
-                       d_iters);
+    hipLaunchKernelGGL(solve_kernel_rt, dim3(batch), dim3(RT_BLOCK), runtime_lds_bytes(d), stream, cfg, d, d_in, d_ws, d_x,
+                       d_fm, d_status, d_iters);
+    return hipGetLastError();
+}
+
+hipError_t launch_sensitivity_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws,
+                                      double* d_x, double* d_fm, int* d_status, int* d_iters, double* d_dx, double* d_dfm,
+                                      int* d_active, int* d_flags, hipStream_t stream) {
+    static std::atomic<bool> attr_set[RT_MAX_DEV];
+    if (d.np != d.nz + 1 + RT_NPAR || d.np > RT_BLOCK * RT_CPT) return hipErrorInvalidValue;   // runtime_dims(.., true)
+    const hipError_t e = rt_allow_lds(reinterpret_cast<const void*>(&sens_kernel_rt), attr_set, d);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sens_kernel_rt, dim3(batch), dim3(RT_BLOCK), runtime_lds_bytes(d), stream, cfg, d, d_in, d_ws, d_x,
+                       d_fm, d_status, d_iters, d_dx, d_dfm, d_active, d_flags);
     return hipGetLastError();
 }
 

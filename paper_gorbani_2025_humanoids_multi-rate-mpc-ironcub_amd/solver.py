@@ -30,28 +30,32 @@ KERNEL_FORM_AUTO, KERNEL_FORM_STRUCTURED, KERNEL_FORM_SYRK = 0, 1, 2
 class BatchedVSMPC:
     """`max_batch` independent MPC instances on one GPU (one workgroup per instance)."""
 
-    def __init__(self, cfg: L.MPCConfig | None = None, device: int = 0, max_batch: int = 256, runtime: str = "never"):
+    def __init__(self, cfg: L.MPCConfig | None = None, device: int = 0, max_batch: int = 256, runtime: str = "never",
+                 sensitivity: bool = False):
         """runtime: "never" -- the tuned kernel of a tabled horizon, other horizons are refused (vsmpc_create);
         "fallback" -- the runtime-sized kernel where the table has no instantiation; "always" -- the runtime-sized kernel
-        for every horizon (vsmpc_create_ex, include/vsmpc.h)."""
+        for every horizon (vsmpc_create_ex, include/vsmpc.h).  sensitivity: also allocate what solve_sensitivity needs
+        (VSMPC_CREATE_SENSITIVITY)."""
         if runtime not in L.RUNTIME_MODES:
             raise ValueError(f"runtime must be one of {sorted(L.RUNTIME_MODES)}, not {runtime!r}")
         self.cfg = cfg or L.paper_config()
         self.lib = _lib.load()
         self._ccfg = self.cfg.to_c()
         self._h = ctypes.c_void_p()
-        if runtime == "never":
+        if runtime == "never" and not sensitivity:
             _lib.check(self.lib.vsmpc_create(ctypes.byref(self._ccfg), device, max_batch, ctypes.byref(self._h)),
                        "vsmpc_create")
         else:
-            _lib.check(self.lib.vsmpc_create_ex(ctypes.byref(self._ccfg), device, max_batch, L.RUNTIME_MODES[runtime],
-                                                ctypes.byref(self._h)), "vsmpc_create_ex")
+            flags = L.RUNTIME_MODES[runtime] | (L.CREATE_SENSITIVITY if sensitivity else 0)
+            _lib.check(self.lib.vsmpc_create_ex(ctypes.byref(self._ccfg), device, max_batch, flags, ctypes.byref(self._h)),
+                       "vsmpc_create_ex")
         self.device = device
         self.max_batch = max_batch
         self.n_var = self.lib.vsmpc_num_variables(self._h)
         self.n_con = self.lib.vsmpc_num_constraints(self._h)
         self.n_in = self.lib.vsmpc_input_doubles(self._h)
         self.n_p = self.lib.vsmpc_condensed_dim(self._h)
+        self.n_v = self.lib.vsmpc_num_throttle_unknowns(self._h)
         assert self.n_var == self.cfg.n_var and self.n_in == self.cfg.n_in and self.n_con == self.cfg.n_con
 
     def set_kernel_form(self, form: int) -> int:
@@ -109,6 +113,38 @@ class BatchedVSMPC:
             ctypes.c_void_p(d_status.data_ptr()),
             ctypes.c_void_p(d_iters.data_ptr()) if d_iters is not None else None,
             ctypes.c_void_p(s.cuda_stream)), "vsmpc_solve_batch_device")
+
+    # ---- sensitivities of the solution to X0 (vsmpc_sensitivity_batch); needs sensitivity=True at construction
+    def solve_sensitivity(self, inputs: np.ndarray, jacobian: bool = True) -> dict:
+        """x, first_move, status, iters as solve(); dx_dx0 [B, n_var, 26] (only when `jacobian`) and dfm_dx0 [B, 24, 26]:
+        d x / d X0 and d first_move / d X0; active [B, n_v]: final throttle states (L.ACTIVE_*); flags [B]: L.SENS_*."""
+        inputs = np.ascontiguousarray(inputs, dtype=np.float64)
+        if inputs.ndim != 2 or inputs.shape[1] != self.n_in:
+            raise ValueError(f"inputs must be [batch, {self.n_in}]")
+        B, J = inputs.shape[0], L.N_STATES
+        out = {"x": np.empty((B, self.n_var)), "first_move": np.empty((B, L.FM_SIZE)),
+               "status": np.empty(B, dtype=np.int32), "iters": np.empty(B, dtype=np.int32),
+               "dx_dx0": np.empty((B, self.n_var, J)) if jacobian else None, "dfm_dx0": np.empty((B, L.FM_SIZE, J)),
+               "active": np.empty((B, self.n_v), dtype=np.int32), "flags": np.empty(B, dtype=np.int32)}
+        _lib.check(self.lib.vsmpc_sensitivity_batch(
+            self._h, _ptr(inputs), B, _ptr(out["x"]), _ptr(out["first_move"]), _ptr(out["status"]), _ptr(out["iters"]),
+            _ptr(out["dx_dx0"]), _ptr(out["dfm_dx0"]), _ptr(out["active"]), _ptr(out["flags"]), None),
+            "vsmpc_sensitivity_batch")
+        if not jacobian:
+            del out["dx_dx0"]
+        return out
+
+    def solve_sensitivity_device(self, d_in, d_x, d_fm, d_status, d_iters, d_dx, d_dfm, d_active, d_flags, stream=None):
+        """vsmpc_sensitivity_batch_device: torch CUDA tensors (every output but d_status may be None), enqueue only"""
+        import torch
+        assert d_in.is_cuda and d_in.dtype == torch.float64 and d_in.is_contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
+
+        def p(t):
+            return None if t is None else ctypes.c_void_p(t.data_ptr())
+        _lib.check(self.lib.vsmpc_sensitivity_batch_device(
+            self._h, p(d_in), d_in.shape[0], p(d_x), p(d_fm), p(d_status), p(d_iters), p(d_dx), p(d_dfm), p(d_active),
+            p(d_flags), ctypes.c_void_p(s.cuda_stream)), "vsmpc_sensitivity_batch_device")
 
     def timing_begin(self, stream):
         _lib.check(self.lib.vsmpc_timing_begin(self._h, ctypes.c_void_p(stream.cuda_stream)), "vsmpc_timing_begin")
