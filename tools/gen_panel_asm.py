@@ -162,6 +162,7 @@ class Stream:
 K375 = 76
 BARRIER_VARIANTS = [(1, 3), (2, 3), (2, 6), (3, 6)]        # (row slots, pivot behind which the barrier sits)
 LAST_PANEL_PIVOTS = [8, 12]                                   # NZ - 16 (NT - 1) of the built horizons (vsmpc_device.hpp)
+JOINT_DUMMY_PIVOTS = [8]                                      # NUY % 16 of the structured horizons (vsmpc_device.hpp)
 SLOTS = 1
 
 
@@ -196,9 +197,10 @@ def g(c):
     return M.G0 + 2 * c
 
 
-def prologue(s, slots, bar=False):
+def prologue(s, slots, bar=False, ncol=NP):
     """Loads.  bar: the rows below the diagonal tile are requested only after the workgroup barrier inside the stream (the
-    wavefronts that complete them arrive there later than the one tile this stream starts with)."""
+    wavefronts that complete them arrive there later than the one tile this stream starts with).  ncol: columns of the rows
+    below that the stream reads (see stream_dpp)."""
     for c in range(NP):
         s.add("dsr", f"ds_read_b64 {vp(g(c))}, v{M.DGA} offset:{8 * c}", [f"v{M.DGA}"], regs("v", g(c)) + ["lgkm"])
     s.add("smov", f"s_mov_b32 s{K375}, 0", [], [f"s{K375}"])
@@ -212,10 +214,10 @@ def prologue(s, slots, bar=False):
         s.add("wait", "s_waitcnt lgkmcnt(0)", ["lgkm2"], [r for sl in range(slots) for c in range(NP) for r in regs("v", a(c, sl))])
         return
     for sl in range(slots):
-        for c in range(NP):
+        for c in range(ncol):
             s.add("dsr", f"ds_read_b64 {vp(a(c, sl))}, v{M.LDA[sl]} offset:{8 * c}", [f"v{M.LDA[sl]}"], regs("v", a(c, sl)) + ["lgkm"])
     # one wait for all loads (finer counts would let pivot 0 start earlier: ~100 cycles, not worth the bookkeeping)
-    allr = [r for c in range(NP) for r in regs("v", g(c))] + [r for sl in range(slots) for c in range(NP) for r in regs("v", a(c, sl))]
+    allr = [r for c in range(NP) for r in regs("v", g(c))] + [r for sl in range(slots) for c in range(ncol) for r in regs("v", a(c, sl))]
     s.add("wait", "s_waitcnt lgkmcnt(0)", ["lgkm"], allr)
 
 
@@ -236,12 +238,15 @@ def rsqrt_chain(s, d_src, d_regs, INV=None):
     return s.add("fma", f"v_fma_f64 {vp(INV)}, {vp(Z)}, {vp(W)}, {vp(Y)}", regs("v", Z) + regs("v", W) + regs("v", Y), regs("v", INV))
 
 
-def stream_dpp(npiv=NP, slots=1, bar_after=None):
+def stream_dpp(npiv=NP, slots=1, bar_after=None, ncol=NP):
     """slots = 0: the diagonal tile alone (the last panel: npiv pivots, its other rows carried as ordinary rows).
     bar_after = KB: the stream starts on the diagonal tile alone and joins a workgroup barrier once 1 / L_KB,KB is known; the
-    rows below are loaded behind it, and their share of pivots 0 .. KB is caught up from there (same instructions, later)."""
+    rows below are loaded behind it, and their share of pivots 0 .. KB is caught up from there (same instructions, later).
+    ncol < NP: only columns 0 .. ncol - 1 are updated -- the columns behind them are decoupled unknowns (exact zeros in the
+    pivot columns: every skipped update would subtract a signed zero), which are left as they were loaded."""
+    assert ncol == NP or bar_after is None, "the barrier variants load every column"
     s = Stream()
-    prologue(s, slots, bar_after is not None)
+    prologue(s, slots, bar_after is not None, ncol)
     DP = M.DP
     for j in range(npiv):
         INV = M.inv(j)
@@ -258,7 +263,7 @@ def stream_dpp(npiv=NP, slots=1, bar_after=None):
         for sl in range(slots):
             s.add("mul", f"v_mul_f64 {vp(a(j, sl))}, {vp(a(j, sl))}, {vp(INV)}", regs("v", a(j, sl)) + regs("v", INV), regs("v", a(j, sl)))
             s.add("dsw", f"ds_write_b64 v{M.STA[sl]}, {vp(a(j, sl))} offset:{8 * j}", [f"v{M.STA[sl]}"] + regs("v", a(j, sl)), ["lds"])
-        for c in range(j + 1, NP):
+        for c in range(j + 1, ncol):
             for dst, src1 in [(g(c), g(j))] + [(a(c, sl), a(j, sl)) for sl in range(slots)]:
                 s.add("dpp", f"v_fmac_f64_dpp {vp(dst)}, -{vp(g(j))}, {vp(src1)} row_newbcast:{c} row_mask:0xf bank_mask:0xf",
                       regs("v", g(j)) + regs("v", src1) + regs("v", dst), regs("v", dst), dpp_src=regs("v", g(j)))
@@ -435,12 +440,18 @@ def main():
     for npiv in LAST_PANEL_PIVOTS:
         todo.append((f"panel_last{npiv}_dpp", npiv, 0, f"The last panel: {npiv} pivots in the diagonal tile, whose other rows are carried as ordinary "
                      f"rows.\n// Lane 16 r + c carries row c (r = 0 is the copy that is stored); inv_last = 1 / L_{npiv - 1},{npiv - 1}."))
+    for npiv in JOINT_DUMMY_PIVOTS:
+        todo.append((f"panel{npiv}x1_dpp", (npiv, npiv), 1,
+                     f"The joint panel column that ends in dummy unknowns (unit diagonal, no coupling): {npiv} pivots and {npiv} columns, 1 row\n"
+                     f"// slot.  Rows / columns {npiv}..15 of the diagonal tile stay the identity block they are, the rows below keep their (zero)\n"
+                     f"// entries there, 1 / L_jj goes to invd_addr[0..{npiv - 1}].  Otherwise panel16x1_dpp; inv_last = 1 / L_{npiv - 1},{npiv - 1}."))
     for name, npiv, slots, comment in todo:
         kb = None
         if isinstance(slots, tuple):
             slots, kb = slots
+        npiv, ncol = npiv if isinstance(npiv, tuple) else (npiv, NP)
         M = Map(max(slots, 1), 0 if kb is None else kb + 1)
-        t, ninstr, nops, cycles = function(name, stream_dpp(npiv, slots, kb), comment, slots)
+        t, ninstr, nops, cycles = function(name, stream_dpp(npiv, slots, kb, ncol), comment, slots)
         text += t
         print(f"{name}: {ninstr} instructions, {nops} wait states, modelled {cycles} cycles")
     for slots in (1, 2, 3):
