@@ -64,7 +64,7 @@ typedef struct vsmpc_config {
     double w_rpy_err[3];       /* weightRPYError    */
     double w_ang_mom[3];       /* weightAngMom      */
     double w_delta_joint[8];   /* weightDeltaJoint  */
-    double w_throttle;         /* weightThrottle    */
+    double w_throttle;         /* weightThrottle; below 10 the QP is nearly singular: still solved, but the minimiser is no longer determined to 1e-8 */
     double w_initial_throttle; /* weightInitialThrottle */
     double w_reg_joint_pos;    /* weightRegularizationJointPos */
     double throttle_min;       /* throttleMin (percent) */

@@ -1,0 +1,199 @@
+"""Shared table of MPC configurations away from the paper's values (plain helper module, imported by tests).
+
+The paper defaults (layout.MPCConfig()) are degenerate where the tuned kernels have index arithmetic of their own: eight
+equal joint weights, w_throttle == w_initial_throttle, uniform or x == y state-weight groups, period_mpc == period_small,
+ratio exactly 20, throttle limits equal to the jet model's own clamp.  Everything here breaks those ties:
+
+  ALL_DISTINCT        no two scalars equal, none equal to its default
+  one_at_a_time()     exactly one field (or one component of a vector field) off its default, with records on which
+                      that field acts
+  EDGE                configurations at the ends of the range (zero weights, 1..1e6 joint-weight spread, a narrow throttle
+                      box, non-round periods, the small-w_throttle end of the parity range)
+  NON_DEFAULT         the settings the runtime-kernel and sensitivity tests have used from the start
+
+Configurations are plain dicts of MPCConfig / oracle Config keyword arguments; configs() builds both objects.
+"""
+import importlib
+
+import numpy as np
+
+PKG = "paper_gorbani_2025_humanoids_multi-rate-mpc-ironcub_amd"
+PAPER = (17, 7, 12)
+HORIZONS = [(17, 7, 12), (21, 9, 15), (34, 14, 24)]          # csrc/vsmpc_horizons.def
+
+NON_DEFAULT = dict(w_delta_joint=(65000.0, 30000.0, 1000.0, 65000.0, 200.0, 5e4, 8e3, 65000.0), w_reg_joint_pos=0.0,
+                   throttle_min=10.0, throttle_max=90.0, period_small=0.004)
+
+ALL_DISTINCT = dict(period_mpc=0.004, period_small=0.006, period_large=0.09,          # ratio 15
+                    w_com_pos=(430.0, 610.0, 5200.0), w_com_pos_err=(21000.0, 27000.0, 52000.0),
+                    w_lin_mom=(0.8, 1.3, 1.9), w_rpy=(900.0, 1150.0, 1400.0), w_rpy_err=(8000.0, 11000.0, 13000.0),
+                    w_ang_mom=(60.0, 85.0, 110.0),
+                    w_delta_joint=(65000.0, 30000.0, 1000.0, 52000.0, 200.0, 5e4, 8e3, 41000.0),
+                    w_throttle=70000.0, w_initial_throttle=95000.0, w_reg_joint_pos=35.0,
+                    throttle_min=8.0, throttle_max=88.0)
+
+# Below this w_throttle the reduced Hessian is close enough to singular that two exact float64 solvers no longer agree
+# to the parity bar (include/vsmpc.h): the smallest power of ten at which the oracle and algo_model
+# agree to 1e-10 with equal iteration counts on records() (found on the CPU; test_config_cases.py keeps it honest).
+W_THROTTLE_PARITY_MIN = 10.0
+
+JOINT_SPREAD = (1e6, 3e4, 10.0, 5e4, 1.0, 5e5, 8e2, 4e4)
+
+EDGE = {
+    "wreg0_nonuniform_joints": dict(w_reg_joint_pos=0.0, w_delta_joint=ALL_DISTINCT["w_delta_joint"]),
+    "w_lin_mom_zero": dict(w_lin_mom=(0.0, 0.0, 0.0)),
+    "joint_spread_1_1e6": dict(w_delta_joint=JOINT_SPREAD),
+    "throttle_box_45_55": dict(throttle_min=45.0, throttle_max=55.0),
+    "periods_0047_093": dict(period_small=0.0047, period_large=0.093),
+    "hold_outside_box": dict(throttle_min=20.0, throttle_max=80.0),
+    "w_throttle_parity_min": dict(w_throttle=W_THROTTLE_PARITY_MIN),
+}
+
+# DUAL_MAX_ACTIVE / VS_DUAL3_MAX of box_qp in csrc/vsmpc_kernels.hip (test_config_cases.py checks the copy against the
+# source text); which form (21, 9, 15) runs is not asserted anywhere, so it has no entry
+DUAL_FORM_MAX = {(17, 7, 12): 16, (34, 14, 24): 24}
+
+STATE_FIELDS = ("w_com_pos", "w_lin_mom", "w_rpy", "w_ang_mom", "w_com_pos_err", "w_rpy_err")
+
+
+def _mod(name):
+    return importlib.import_module(f"{PKG}.{name}")
+
+
+def all_distinct(horizon):
+    """ALL_DISTINCT for a tabled horizon ((34, 14, 24): a fast period of 0.003, so that 14 fast steps fit the slow one)"""
+    s = dict(ALL_DISTINCT)
+    if tuple(horizon) == (34, 14, 24):
+        s["period_small"] = 0.003
+    return s
+
+
+def configs(ref, horizon, settings):
+    """(layout.MPCConfig, oracle Config) for a horizon and a settings dict"""
+    kw = dict(n_iter=horizon[0], n_iter_small=horizon[1], control_horizon=horizon[2], **settings)
+    return _mod("layout").MPCConfig(**kw), ref.Config(**kw)
+
+
+def dt_atol(cfg):
+    """Bar for one implementation's time-step schedule against another's: the steps are differences of two warp values
+    of size up to period_large, each rounded (and summed in another order or with fused multiply-adds) -- 4 ulp of it."""
+    return 4.0 * float(np.spacing(cfg.period_large))
+
+
+XML_KEYS = {  # src/config/vs_mcp_config.xml:7-43 -> vsmpc_config field
+    "nIter": "n_iter", "nIterSmall": "n_iter_small", "controlHorizon": "control_horizon", "useJetDynamic": "use_jet_dynamic",
+    "periodMPC": "period_mpc", "periodMPCSmallSteps": "period_small", "periodMPCLargeSteps": "period_large",
+    "weightCoMPos": "w_com_pos", "weightCoMPosError": "w_com_pos_err", "weightLinMom": "w_lin_mom", "weightRPY": "w_rpy",
+    "weightRPYError": "w_rpy_err", "weightAngMom": "w_ang_mom", "weightDeltaJoint": "w_delta_joint",
+    "weightThrottle": "w_throttle", "weightInitialThrottle": "w_initial_throttle",
+    "weightRegularizationJointPos": "w_reg_joint_pos", "throttleMin": "throttle_min", "throttleMax": "throttle_max",
+}
+
+
+def xml_params(cfg):
+    """The VS_MPC_CONFIG dictionary (the XML's key names) that describes the MPCConfig `cfg`"""
+    out = {}
+    for key, field in XML_KEYS.items():
+        v = getattr(cfg, field)
+        out[key] = list(v) if isinstance(v, tuple) else v
+    return out
+
+
+def saturated(cfg, n=4, first_index=40):
+    """test_gpu_parity.test_saturated_throttles' records: a free tick whose CoM reference is 30 m above (first half) or
+    below (second half), so that many throttle bounds are active at the upper / lower limit"""
+    L = _mod("layout")
+    recs = _mod("synth").make_batch(cfg, n, workload="hover", first_index=first_index)
+    recs[:, L.IN_HOLD] = 0.0
+    recs[:, L.IN_XREF + 2::12] += 30.0
+    recs[n // 2:, L.IN_XREF + 2::12] -= 60.0
+    recs[:, 22] = recs[:, 2] - recs[:, L.IN_XREF + 2]           # keep X0's position error consistent
+    return recs
+
+
+def records(cfg, n=3, first_index=5):
+    """hover + take-off + Monte-Carlo + the saturated free-tick records (both directions)"""
+    synth = _mod("synth")
+    recs = [synth.make_batch(cfg, n, workload=w, first_index=first_index) for w in ("hover", "takeoff", "montecarlo")]
+    return np.concatenate(recs + [saturated(cfg)])
+
+
+def edge_records(name, cfg, n=3):
+    """records() adapted to the edge configuration `name`"""
+    L = _mod("layout")
+    recs = records(cfg, n=n)
+    if name == "throttle_box_45_55":
+        # free ticks (a hold pin alone would end the active-set loop after one pass), previous throttle inside the box;
+        # the last record keeps the hold pin: its three other throttle blocks still leave the narrow box
+        recs[:, L.IN_HOLD] = 0.0
+        recs[:, L.IN_UPREV:L.IN_UPREV + 4] = np.clip(recs[:, L.IN_UPREV:L.IN_UPREV + 4], 46.0, 54.0)
+        recs[-1, L.IN_HOLD] = 1.0
+    if name == "hold_outside_box":
+        # hold on, previous throttle above / below the configured box: the pin v0 = v(u_prev) wins over the box
+        # (constraintsVSMPC.cpp:351-358 writes l = u = v(u_prev) for block 0 whatever the limits are)
+        recs[:, L.IN_HOLD] = 1.0
+        recs[0::2, L.IN_UPREV:L.IN_UPREV + 4] = (93.0, 88.0, 97.0, 84.0)
+        recs[1::2, L.IN_UPREV:L.IN_UPREV + 4] = (7.0, 12.0, 3.0, 16.0)
+    return recs
+
+
+def _generic_records(cfg):
+    synth = _mod("synth")
+    return np.concatenate([synth.make_batch(cfg, 2, workload=w, first_index=5) for w in ("hover", "takeoff", "montecarlo")])
+
+
+def one_at_a_time():
+    """(name, settings, records) at the paper horizon: exactly one field, or one component of a vector field, differs
+    from the default, and the records are ones on which that field acts.  The records are built with the *default*
+    configuration, so the same records can be solved under the default settings for comparison."""
+    L = _mod("layout")
+    cfg = L.MPCConfig()
+    generic = _generic_records(cfg)
+    for f in STATE_FIELDS:                                       # 18 state-weight components
+        for i in range(3):
+            v = list(getattr(cfg, f))
+            v[i] *= 2.5
+            yield f"{f}[{i}]", {f: tuple(v)}, generic
+    for j in range(8):                                           # 8 joint weights
+        w = list(cfg.w_delta_joint)
+        w[j] *= 0.4
+        yield f"w_delta_joint[{j}]", {"w_delta_joint": tuple(w)}, generic
+    yield "w_throttle", {"w_throttle": 50000.0}, generic
+    # the anchor -w_init v(u_prev) only acts where v0 is free and the optimum is away from v(u_prev)
+    free = generic.copy()
+    free[:, L.IN_HOLD] = 0.0
+    free[0::2, L.IN_UPREV:L.IN_UPREV + 4] = np.clip(free[0::2, L.IN_UPREV:L.IN_UPREV + 4] + 25.0, 0.0, 100.0)
+    free[1::2, L.IN_UPREV:L.IN_UPREV + 4] = np.clip(free[1::2, L.IN_UPREV:L.IN_UPREV + 4] - 25.0, 0.0, 100.0)
+    yield "w_initial_throttle", {"w_initial_throttle": 50000.0}, free
+    qe = generic.copy()
+    qe[:, L.IN_QERR:L.IN_QERR + 8] *= 10.0                      # 0.2 rad of joint-position error
+    yield "w_reg_joint_pos", {"w_reg_joint_pos": 200.0}, qe
+    sat = saturated(cfg, n=6)
+    yield "throttle_min", {"throttle_min": 30.0}, sat[3:]        # pushed down: lower bounds active
+    yield "throttle_max", {"throttle_max": 85.0}, sat[:3]        # pushed up: upper bounds active
+    yield "period_small", {"period_small": 0.004}, generic
+    yield "period_large", {"period_large": 0.09}, generic
+
+
+def first_violated(ref, rcfg, rec):
+    """Size of the first violated set: how many throttles of the solve with only the hold pin enforced (the first pass of
+    the active-set loop) leave the box.  The tuned kernels pick the box-QP formulation by it (csrc/vsmpc_kernels.hip,
+    box_qp): the dual form up to DUAL_FORM_MAX[horizon] violated throttles, the primal form on the Schur complement for
+    more."""
+    H, g, Ac, lo, hi = ref.assemble_dense(rcfg, rec)
+    nxs = 26 * (rcfg.n_iter + 1)
+    sol = np.linalg.solve(Ac[:nxs, :nxs], np.column_stack([lo[:nxs], Ac[:nxs, nxs:]]))
+    Z = np.vstack([-sol[:, 1:], np.eye(rcfg.n_var - nxs)])
+    xp = np.concatenate([sol[:, 0], np.zeros(rcfg.n_var - nxs)])
+    Hr, gr = Z.T @ H @ Z, Z.T @ (H @ xp + g)
+    o, nthr = 8 * rcfg.control_horizon, 4 * rcfg.n_vblocks
+    zlo, zhi = lo[nxs:nxs + nthr], hi[nxs:nxs + nthr]
+    pinned = np.zeros(Hr.shape[0], dtype=bool)
+    pinned[o:o + nthr] = zlo == zhi
+    z = np.zeros(Hr.shape[0])
+    z[o:o + nthr][zlo == zhi] = zlo[zlo == zhi]
+    F = ~pinned
+    z[F] = np.linalg.solve(Hr[np.ix_(F, F)], -(gr[F] + Hr[np.ix_(F, pinned)] @ z[pinned]))
+    v = z[o:o + nthr]
+    tol = 1e-12 * (1.0 + np.abs(v))
+    return int(((v < zlo - tol) | (v > zhi + tol)).sum())

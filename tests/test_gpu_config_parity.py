@@ -1,0 +1,306 @@
+"""The tuned solve kernels (solve_kernel<...> of csrc/vsmpc_horizons.def) away from the paper's configuration.
+
+Every value of vsmpc_config reaches the kernel at run time (fill_devcfg -> CFG_SQ / CFG_WJ / CFG_WREG / CFG_WTHR /
+CFG_WINIT / CFG_VMIN / CFG_VMAX / dt[]), and the paper defaults are degenerate exactly where the kernel indexes them: eight
+equal joint weights, w_throttle == w_initial_throttle, uniform or x == y state-weight groups, period_mpc == period_small.
+tests/config_cases.py breaks those ties (ALL_DISTINCT, one field at a time, edge configurations); here the tuned kernel
+is compared, phase by phase and per output group, with the oracle (oracle/vsmpc_ref.py), with the condensed problem the
+oracle's dense QP implies (algo_model.reduced_condensed), with its own other condensing form, and with the independent
+runtime-sized kernel -- at the project's bars: solution and first move 1e-8 relative with equal active-set iteration
+counts, linearisation 1e-13, condensed M 1e-12 (paper horizon) / 1e-11, factor L 1e-11 / 1e-10, form against form
+1e-13 (M), 1e-12 / 1e-11 (L).  The reference side sits at 1e-13 or better at every one of these configurations
+(tests/test_config_cases.py)."""
+import ctypes
+import importlib
+
+import numpy as np
+import pytest
+
+from conftest import PKG, relerr
+import config_cases as cc
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-8
+CASES = ["ALL_DISTINCT"] + list(cc.EDGE)
+
+
+def _settings(horizon, name):
+    return cc.all_distinct(horizon) if name == "ALL_DISTINCT" else cc.EDGE[name]
+
+
+def _records(name, cfg):
+    return cc.records(cfg) if name == "ALL_DISTINCT" else cc.edge_records(name, cfg)
+
+
+def _tuned(solver_mod, cfg, n):
+    m = solver_mod.BatchedVSMPC(cfg, device=0, max_batch=n, runtime="never")
+    assert "solve_kernel" in m.kernel_name and not m.uses_runtime_kernel
+    return m
+
+
+def _check_solution(ref, rcfg, layout, recs, x, fm, st, it):
+    """per output group, as test_gpu_parity.test_solve_matches_oracle does; returns the oracle's solutions"""
+    assert (st == layout.STATUS_SOLVED).all(), st
+    oj, ov = rcfg.off_joints, rcfg.off_throttle
+    worst = {"x": 0.0, "thrust": 0.0, "thrust_dot": 0.0, "traj": 0.0, "v": 0.0, "dq": 0.0, "fm": 0.0}
+    xs = []
+    for b, rec in enumerate(recs):
+        xr, _, itr, _ = ref.solve_instance(rcfg, rec)
+        xs.append(xr)
+        X, Xr = x[b, :oj].reshape(-1, 26), xr[:oj].reshape(-1, 26)
+        worst["x"] = max(worst["x"], relerr(x[b], xr))
+        worst["thrust"] = max(worst["thrust"], relerr(X[:, 12:16], Xr[:, 12:16]))
+        worst["thrust_dot"] = max(worst["thrust_dot"], relerr(X[:, 16:20], Xr[:, 16:20]))
+        worst["traj"] = max(worst["traj"], relerr(X[:, 0:12], Xr[:, 0:12]))
+        worst["v"] = max(worst["v"], relerr(x[b, ov:], xr[ov:]))
+        worst["dq"] = max(worst["dq"], relerr(x[b, oj:ov], xr[oj:ov]))
+        worst["fm"] = max(worst["fm"], relerr(fm[b], ref.first_move_vector(rcfg, xr)))
+        assert it[b] == itr, (b, it[b], itr)              # same active-set path as the oracle's pivoting rule
+    print("worst vs oracle:", {k: f"{v:.2e}" for k, v in worst.items()})
+    for k, v in worst.items():
+        assert v < TOL, (k, v)
+    return np.array(xs)
+
+
+@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("horizon", cc.HORIZONS)
+def test_tuned_kernel_matches_oracle_phase_by_phase(solver_mod, ref, layout, horizon, name):
+    import algo_model
+    from test_gpu_parity import _kkt_properties
+    cfg, rcfg = cc.configs(ref, horizon, _settings(horizon, name))
+    recs = _records(name, cfg)
+    paper = tuple(horizon) == cc.PAPER
+    m = _tuned(solver_mod, cfg, len(recs))
+    rt = solver_mod.BatchedVSMPC(cfg, device=0, max_batch=len(recs), runtime="always")
+    try:
+        # P0: linearisation and the time-step schedule
+        A, Bj, Bt, c, dt = m.linearize(recs)
+        np.testing.assert_allclose(dt, ref.dt_schedule(rcfg), rtol=0, atol=cc.dt_atol(rcfg))
+        for b, rec in enumerate(recs):
+            Ar, Bjr, Btr, cr = ref.linearize(rcfg, rec)
+            assert relerr(A[b], Ar) < 1e-13 and relerr(Bj[b], Bjr) < 1e-14
+            assert relerr(Bt[b], Btr) < 1e-13 and relerr(c[b], cr) < 1e-13
+        # the reference-ordered dense QP
+        for rec in (recs[3], recs[-1]):
+            H, g, Ac, lo, hi = m.assemble_dense(rec)
+            Hr, gr, Acr, lor, hir = ref.assemble_dense(rcfg, rec)
+            np.testing.assert_array_equal(H, Hr)
+            assert relerr(g, gr) < 1e-14 and relerr(Ac, Acr) < 1e-13
+            assert relerr(lo, lor) < 1e-13 and relerr(hi, hir) < 1e-13
+            assert np.array_equal(Ac == 0, Acr == 0)
+        # P1-P3: condensed Hessian, gradient row and factor, in both condensing forms
+        # ((21, 9, 15) has the SYRK form only: the structured form is refused there, and checked where it exists)
+        prev = m.set_kernel_form(solver_mod.KERNEL_FORM_AUTO)
+        try:
+            forms = {}
+            for form in (solver_mod.KERNEL_FORM_STRUCTURED, solver_mod.KERNEL_FORM_SYRK):
+                try:
+                    m.set_kernel_form(form)
+                except ValueError:
+                    assert tuple(horizon) == (21, 9, 15) and form == solver_mod.KERNEL_FORM_STRUCTURED, (horizon, form)
+                    continue
+                forms[form] = (m.solve(recs), [m.debug_condensed(recs[b])[:2] for b in (3, len(recs) - 1)])
+        finally:
+            m.set_kernel_form(prev)
+        assert solver_mod.KERNEL_FORM_SYRK in forms
+        for k, b in enumerate((3, len(recs) - 1)):        # a take-off record and a saturated one
+            Me, ge, Le = algo_model.reduced_condensed(rcfg, ref, recs[b])
+            nz = Me.shape[0]
+            for form, (_, cond) in forms.items():
+                M, Lf = cond[k]
+                Mh = np.tril(M[:nz, :nz])
+                Mh = Mh + np.tril(Mh, -1).T
+                eM, eg = relerr(Mh, Me), relerr(M[nz, :nz], ge)
+                eL, eLg = relerr(np.tril(Lf[:nz, :nz]), Le), relerr(Lf[nz, :nz], np.linalg.solve(Le, ge))
+                print(f"form {form} record {b}: M {eM:.2e} g {eg:.2e} L {eL:.2e} L^-1 g {eLg:.2e}")
+                assert eM < (1e-12 if paper else 1e-11) and eg < (1e-12 if paper else 1e-11), (form, b, eM, eg)
+                assert eL < (1e-11 if paper else 1e-10) and eLg < (1e-11 if paper else 1e-10), (form, b, eL, eLg)
+            if len(forms) == 2:
+                (Ma, La), (Mb, Lb) = (forms[f][1][k] for f in (solver_mod.KERNEL_FORM_STRUCTURED, solver_mod.KERNEL_FORM_SYRK))
+                assert relerr(np.tril(Ma[:nz + 1, :nz]), np.tril(Mb[:nz + 1, :nz])) < 1e-13
+                assert relerr(np.tril(La[:nz + 1, :nz]), np.tril(Lb[:nz + 1, :nz])) < (1e-12 if paper else 1e-11)
+        if len(forms) == 2:
+            a, b_ = forms[solver_mod.KERNEL_FORM_STRUCTURED][0], forms[solver_mod.KERNEL_FORM_SYRK][0]
+            np.testing.assert_array_equal(a[2], b_[2])
+            np.testing.assert_array_equal(a[3], b_[3])
+            assert relerr(a[0], b_[0]) < (1e-11 if paper else 1e-10) and relerr(a[1], b_[1]) < (1e-11 if paper else 1e-10)
+        # the solve, per output group, in the handle's own (automatic) form
+        x, fm, st, it = m.solve(recs)
+        _check_solution(ref, rcfg, layout, recs, x, fm, st, it)
+        v = x[:, rcfg.off_throttle:]
+        vmin, vmax = ref.throttle_bounds(rcfg)
+        free = recs[:, layout.IN_HOLD] == 0.0
+        assert v[:, 4:].min() >= vmin and v[:, 4:].max() <= vmax
+        assert v[free, :4].min(initial=vmax) >= vmin and v[free, :4].max(initial=vmin) <= vmax
+        held = ~free
+        vprev = ref.v_of_throttle(recs[:, layout.IN_UPREV:layout.IN_UPREV + 4])
+        np.testing.assert_allclose(v[held, :4], vprev[held], rtol=0, atol=1e-15)       # the pin wins over the box
+        if name == "hold_outside_box":
+            assert ((vprev > vmax) | (vprev < vmin)).all()
+        if name == "throttle_box_45_55":
+            assert it.min() > 1, it
+            if paper:                                      # both box-QP formulations run (the longer horizons' first
+                fv = [cc.first_violated(ref, rcfg, rec) for rec in recs]   # violated sets are all beyond the switch)
+                assert min(fv) <= cc.DUAL_FORM_MAX[cc.PAPER] < max(fv), fv
+        if paper:
+            _kkt_properties(ref, rcfg, recs, x, range(0, len(recs), 3))
+        # the runtime-sized kernel: an independent HIP implementation of the same solve
+        xr_, fmr, str_, itr_ = rt.solve(recs)
+        assert rt.uses_runtime_kernel
+        np.testing.assert_array_equal(st, str_)
+        np.testing.assert_array_equal(it, itr_)
+        assert relerr(xr_, x) < 1e-10 and relerr(fmr, fm) < 1e-10, (relerr(xr_, x), relerr(fmr, fm))
+    finally:
+        m.close()
+        rt.close()
+
+
+def test_one_field_at_a_time(solver_mod, ref, layout):
+    """Every field of vsmpc_config on its own: the tuned kernel follows the oracle, and the oracle's solution under the
+    case differs from its default-configuration solution of the same records by at least 1e-5 relative -- a field the
+    kernel ignored, or read from its neighbour's slot, cannot pass."""
+    dcfg = ref.Config()
+    base = {}
+    n = 0
+    for name, s, recs in cc.one_at_a_time():
+        cfg, rcfg = cc.configs(ref, cc.PAPER, s)
+        m = _tuned(solver_mod, cfg, 32)
+        try:
+            x, fm, st, it = m.solve(recs)
+        finally:
+            m.close()
+        xs = _check_solution(ref, rcfg, layout, recs, x, fm, st, it)
+        for b, rec in enumerate(recs):                    # per record: one that proves nothing fails loudly
+            key = rec.tobytes()
+            if key not in base:
+                base[key] = ref.solve_instance(dcfg, rec)[0]
+            moved = relerr(xs[b], base[key])
+            assert moved >= 1e-5, (name, b, moved)
+        n += 1
+    assert n == 33
+
+
+def test_entry_points_are_bit_identical_at_all_distinct(solver_mod, synth, layout, ref):
+    """tick, solve_device and the pinned direct-store path against solve, once with every configuration value distinct"""
+    import torch
+    _lib = importlib.import_module(PKG + "._lib")
+    lib = _lib.load()
+    cfg, _ = cc.configs(ref, cc.PAPER, cc.all_distinct(cc.PAPER))
+    B = 24
+    recs = np.concatenate([synth.make_batch(cfg, 12, workload="takeoff"), cc.records(cfg, n=4)[:12]])
+    m = _tuned(solver_mod, cfg, B)
+    try:
+        x, fm, st, it = m.solve(recs)
+        assert (st == layout.STATUS_SOLVED).all() and it.max() > 1
+        dev = torch.device("cuda:0")
+        d_in = torch.from_numpy(recs).to(dev)
+        d_x = torch.zeros((B, cfg.n_var), dtype=torch.float64, device=dev)
+        d_fm = torch.zeros((B, 24), dtype=torch.float64, device=dev)
+        d_st = torch.zeros(B, dtype=torch.int32, device=dev)
+        d_it = torch.zeros(B, dtype=torch.int32, device=dev)
+        m.solve_device(d_in, d_x, d_fm, d_st, d_it)
+        torch.cuda.synchronize()
+        for got, want in ((d_x, x), (d_fm, fm), (d_st, st), (d_it, it)):
+            np.testing.assert_array_equal(got.cpu().numpy(), want)
+
+        def pinned(shape, dtype):
+            nb = int(np.prod(shape)) * np.dtype(dtype).itemsize
+            ptr = lib.vsmpc_alloc_host(nb)
+            assert ptr
+            return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), (nb,)).view(dtype).reshape(shape), ptr
+        bufs = [pinned((B, cfg.n_in), np.float64), pinned((B, cfg.n_var), np.float64), pinned((B, 24), np.float64),
+                pinned((B,), np.int32), pinned((B,), np.int32)]
+        try:
+            (pin, _), (px, _), (pfm, _), (pst, _), (pit, _) = bufs
+            pin[:] = recs
+            px[:] = np.nan; pfm[:] = np.nan; pst[:] = -7; pit[:] = -7
+            vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+            _lib.check(lib.vsmpc_solve_batch(m._h, vp(pin), B, vp(px), vp(pfm), vp(pst), vp(pit), None), "vsmpc_solve_batch")
+            for got, want in ((px, x), (pfm, fm), (pst, st), (pit, it)):
+                np.testing.assert_array_equal(got, want)
+        finally:
+            for _, ptr in bufs:
+                lib.vsmpc_free_host(ptr)
+        # vsmpc_tick == vsmpc_kinematics_batch + vsmpc_solve_batch
+        rng = np.random.default_rng(321)
+        kin = rng.normal(size=(B, layout.KIN_SIZE))
+        for b in range(B):
+            q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+            kin[b, layout.KIN_WRB:layout.KIN_WRB + 9] = (q * np.sign(np.linalg.det(q))).reshape(-1)
+            kin[b, layout.KIN_THRUST:layout.KIN_THRUST + 4] = rng.uniform(20, 220, size=4)
+            a = rng.normal(size=(6, 6))
+            kin[b, layout.KIN_MB:layout.KIN_MB + 36] = (a @ a.T + 6 * np.eye(6)).reshape(-1)
+        two = recs.copy()
+        m.kinematics(kin, two)
+        x2, fm2, st2, it2 = m.solve(two)
+        one = recs.copy()
+        x1, fm1, st1, it1 = m.tick(kin, one)
+        np.testing.assert_array_equal(one, two)
+        for got, want in ((x1, x2), (fm1, fm2), (st1, st2), (it1, it2)):
+            np.testing.assert_array_equal(got, want)
+        assert (st1 == layout.STATUS_SOLVED).all()
+    finally:
+        m.close()
+
+
+def test_closed_loop_rollout_at_all_distinct(solver_mod, ref, layout):
+    """40 closed-loop ticks with period_mpc != period_small and a hold ratio of 15 (two releases of the hold, at ticks 14
+    and 29 of a fresh loop): the resident GPU loop (csrc/vsmpc_rollout.hip: period_mpc, ratio, the hold counter, the
+    sub-steps) against tests/rollout_model.py driven by the oracle's optimum, at test_gpu_rollout's bar."""
+    import rollout_model as rom
+    ro = importlib.import_module(PKG + ".rollout")
+    cfg, rcfg = cc.configs(ref, cc.PAPER, cc.all_distinct(cc.PAPER))
+    assert cfg.ratio == 15 and cfg.period_mpc != cfg.period_small
+    B, T = 2, 40
+    sub = int(round(cfg.period_mpc / 1e-3))              # the plant integrates at 1 kHz (vsmpc_rollout_create): 4 sub-steps here
+    assert sub == 4
+    st0, pa = ro.make_plant(cfg, B, workload="hover")
+    pos, vel, alpha, adt = ro.make_trajectory(cfg, "hover", 10.0)
+    r = ro.ClosedLoopRollout(cfg, B, pos, vel, alpha, adt, device=0)
+    try:
+        assert not r.mpc.uses_runtime_kernel
+        r.reset(st0, pa)
+        r.run(T, log=False)
+        gpu = r.state()
+    finally:
+        r.close()
+    for b in range(B):
+        s = st0[b].copy()
+        model = rom.make_tick_model(cfg, s, pa[b], pos, vel, alpha)
+        free = 0
+        for tick in range(T):
+            rec = rom.build_record(cfg, model, s, pa[b])
+            free += rec[layout.IN_HOLD] == 0.0
+            x, _, _, _ = ref.solve_instance(rcfg, rec)
+            fm = ref.first_move_vector(rcfg, x)
+            model.consume(fm, 1)
+            s = rom.advance(cfg, s, pa[b], tick, fm, 1, alpha, adt, substeps=sub)
+        assert 2 <= free <= 3, free                       # ratio 15: the hold was released two or three times in 40 ticks
+        assert relerr(gpu[b], s) < 1e-8, (b, relerr(gpu[b], s))
+
+
+def test_w_throttle_zero_properties(solver_mod, ref, layout):
+    """w_throttle = 0 is accepted but not a parity case: the reduced Hessian is nearly singular (smallest eigenvalue
+    2.7e-4 against 6.4e5), two exact float64 solvers reach the same objective to 11 digits with minimisers 0.5 apart.
+    What must hold on the tuned kernel: solved, every row feasible, throttles inside the box, and an objective no larger
+    than the oracle's by more than 1e-9 |objective|.  No comparison of x or of iteration counts."""
+    cfg, rcfg = cc.configs(ref, cc.PAPER, dict(w_throttle=0.0))
+    recs = cc.records(cfg)
+    m = _tuned(solver_mod, cfg, len(recs))
+    try:
+        x, fm, st, it = m.solve(recs)
+    finally:
+        m.close()
+    assert (st == layout.STATUS_SOLVED).all(), st
+    vmin, vmax = ref.throttle_bounds(rcfg)
+    for b, rec in enumerate(recs):
+        xr, _, _, (H, g, Ac, lo, hi) = ref.solve_instance(rcfg, rec)
+        r = Ac @ x[b]
+        assert np.maximum(lo - r, r - hi).max() < 1e-9 * max(1.0, np.abs(x[b]).max()), b
+        v = x[b, rcfg.off_throttle:]
+        if rec[layout.IN_HOLD] != 0.0:
+            v = v[4:]
+        assert v.min() >= vmin and v.max() <= vmax
+        f, fr = 0.5 * x[b] @ H @ x[b] + g @ x[b], 0.5 * xr @ H @ xr + g @ xr
+        print(f"record {b}: objective {f:.12e} oracle {fr:.12e}")
+        assert f <= fr + 1e-9 * abs(fr), (b, f, fr)

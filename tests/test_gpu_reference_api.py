@@ -163,3 +163,50 @@ def test_reference_signatures_build_the_reference_records(solver_mod, layout, re
         assert abs(mpc._m_nTurns[2]) == 1 and qp.getAlphaGravity() == fields["alpha"]
     finally:
         raw.close()
+
+
+def test_configure_reads_every_configuration_key(solver_mod, layout, ref):
+    """configure() fed config_cases.ALL_DISTINCT under the XML's key names: the configuration it holds is that one field
+    by field, the hold is released every 15th tick, and every tick's outputs are those of a BatchedVSMPC(ALL_DISTINCT)
+    solve of the record it built (thrust and thrust rate bit for bit; the throttle getter inverts the jet map in numpy)."""
+    import config_cases as cc
+    api = importlib.import_module(PKG + ".reference_api")
+    consts = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_constants.json")))
+    traj = np.load(os.path.join(ROOT, "tests", "golden", "reference_trajectories.npz"))
+    cfg, _ = cc.configs(ref, cc.PAPER, cc.all_distinct(cc.PAPER))
+    params = dict(consts["VS_MPC_CONFIG"], **cc.xml_params(cfg))
+    params["TRAJECTORY_MANAGER"] = {"alphaGravity": traj["alphaGravity"], "fps": int(traj["alphaGravity_fps"][0])}
+    params["POSITION_TRAJECTORY"] = {"positionCoM": traj["positionCoM"], "velocityCoM": traj["velocityCoM"],
+                                     "RPY": traj["RPY"], "RPYDot": traj["RPYDot"], "fps": int(traj["trajectory_fps"][0])}
+    rng = np.random.default_rng(29)
+    robot = FakeRobot(rng)
+    qp = api.QPInput(robot)
+    qp.setThrottleMPC([70.0, 72.0, 74.0, 71.0])
+    qp.setThrustDesMPC(robot.T)
+    qp.setOutputQPJointsPosition(robot.q)
+    qp.setEstimatedThrustDot([1.0, -2.0, 0.5, 0.0])
+    mpc = api.VariableSamplingMPC()
+    assert mpc.configure(params, qp)
+    assert mpc.cfg == cfg
+    raw = solver_mod.BatchedVSMPC(cfg, device=0, max_batch=1)
+    try:
+        for k in range(32):
+            robot.p = robot.p + np.array([0.001, -0.0005, 0.002])
+            robot.base = robot.p + np.array([0.02, 0.0, -0.15])
+            robot.T = robot.T + rng.normal(0, 0.3, 4)
+            qp.setEstimatedThrustDot(rng.normal(0, 3.0, 4))
+            assert mpc.update(qp)
+            rec = mpc._record.copy()
+            assert rec[layout.IN_HOLD] == (0.0 if k % 15 == 14 else 1.0)
+            assert mpc.solveMPC()
+            x, fm, st, it = raw.solve(rec[None, :])
+            assert mpc.getQPProblemStatus() == st[0] == layout.STATUS_SOLVED
+            np.testing.assert_array_equal(mpc.getThrustReference(), fm[0, 16:20])
+            np.testing.assert_array_equal(mpc.getThrustDotReference(), fm[0, 20:24])
+            np.testing.assert_allclose(mpc.getThrottleReference(), fm[0, 12:16], rtol=0, atol=1e-12)
+            qp.setThrottleMPC(mpc.getThrottleReference())
+            qp.setThrustDesMPC(mpc.getThrustReference())
+            qp.setThrustDotDesMPC(mpc.getThrustDotReference())
+            qp.setOutputQPJointsPosition(mpc.getJointsReferencePosition())
+    finally:
+        raw.close()

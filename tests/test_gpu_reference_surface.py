@@ -285,3 +285,53 @@ def test_blf_style_python_handler(pinned):
         assert front.configure(top.get_group("VS_MPC_CONFIG"), qp)          # as the harness passes it (:37,70)
         qp.setEstimatedThrustDot(sc.load(1))
         assert front.update(qp) and front.solveMPC() and front.getQPProblemStatus() == 1
+
+
+def test_readers_honour_every_configuration_key(driver, pinned, tmp_path, layout, solver_mod, ref):
+    """The three configuration readers (include/VariableSamplingMPC.hpp through the driver, the pybind module, the Python
+    twin) fed config_cases.ALL_DISTINCT as the XML-keyed dictionary: every tick's outputs are bit for bit those of a
+    BatchedVSMPC(ALL_DISTINCT) solve of the record the reader built, and the hold is released every 15th tick
+    (periodMPCLargeSteps / periodMPCSmallSteps, not the default 20).  Two keys read into each other's field cannot pass:
+    no two values of a group are equal."""
+    import config_cases as cc
+    consts, traj = pinned
+    cfg, _ = cc.configs(ref, cc.PAPER, cc.all_distinct(cc.PAPER))
+    consts = dict(consts, VS_MPC_CONFIG=dict(consts["VS_MPC_CONFIG"], **cc.xml_params(cfg)))
+    selector = list(range(3, 11))
+    n_ticks = 35
+    sc = fp.Scenario(n_ticks=n_ticks, seed=23)
+    params = params_of(consts, traj, selector)
+    n_in = cfg.n_in
+    (tmp_path / "scenario.bin").write_bytes(sc.serialise(consts, traj, selector).tobytes())
+    res = subprocess.run([driver, str(tmp_path / "scenario.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
+    assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
+    cpp = np.frombuffer((tmp_path / "out.bin").read_bytes(), dtype=np.float64).reshape(n_ticks, -1)
+    api = importlib.import_module(PKG + ".reference_api")
+    twin = api.VariableSamplingMPC()
+    qp = new_qp(api, sc)
+    assert twin.configure(params, qp)
+    assert twin.cfg == cfg                                      # the twin's reader, field by field
+    py_rows = drive(twin, qp, sc, lambda m: m._record, n_in)
+    bindings = importlib.import_module(PKG + ".bindingsMPC")
+    shim = bindings.VariableSamplingMPC()
+    qp2 = new_qp(api, sc)
+    assert shim.configure(params, qp2)
+    pb_rows = drive(shim, qp2, sc, lambda m: m.getRecord(), n_in)
+    np.testing.assert_array_equal(cpp, pb_rows)
+    assert relerr(cpp[:, :n_in], py_rows[:, :n_in]) < 1e-12
+    np.testing.assert_array_equal(cpp[:, layout.IN_HOLD], [0.0 if k % 15 == 14 else 1.0 for k in range(n_ticks)])
+    raw = solver_mod.BatchedVSMPC(cfg, device=0, max_batch=n_ticks)
+    try:
+        o = n_in
+        for rows, exact_throttle in ((cpp, True), (pb_rows, True), (py_rows, False)):
+            x, fm, st, it = raw.solve(np.ascontiguousarray(rows[:, :n_in]))
+            assert (st == layout.STATUS_SOLVED).all()
+            np.testing.assert_array_equal(rows[:, o], st)
+            np.testing.assert_array_equal(rows[:, o + 1:o + 5], fm[:, 16:20])       # thrust reference
+            np.testing.assert_array_equal(rows[:, o + 5:o + 9], fm[:, 20:24])       # thrust-rate reference
+            if exact_throttle:
+                np.testing.assert_array_equal(rows[:, o + 9:o + 13], fm[:, 12:16])  # throttle reference
+            else:   # (the twin's getter inverts the jet map in numpy, as in test_gpu_reference_api.py)
+                np.testing.assert_allclose(rows[:, o + 9:o + 13], fm[:, 12:16], rtol=0, atol=1e-12)
+    finally:
+        raw.close()

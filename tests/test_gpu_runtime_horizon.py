@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import relerr
+from config_cases import NON_DEFAULT
 import rollout_model as rom
 
 pytestmark = pytest.mark.gpu
@@ -18,8 +19,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "paper_gorbani_2025_humanoids_multi-rate-mpc-ironcub_amd"
 TOL = 1e-8
 TABLED = [(17, 7, 12), (34, 14, 24), (21, 9, 15)]
-NON_DEFAULT = dict(w_delta_joint=(65000.0, 30000.0, 1000.0, 65000.0, 200.0, 5e4, 8e3, 65000.0), w_reg_joint_pos=0.0,
-                   throttle_min=10.0, throttle_max=90.0, period_small=0.004)
 
 
 def _cfgs(layout, ref, horizon, **settings):

@@ -111,3 +111,34 @@ def test_shim_runs_a_tick(shim, solver_mod, synth, layout):
         np.testing.assert_array_equal(mpc.getFinalCoMPosition(), x[k, 442:445])
     assert not mpc.update(rec[0][:100])
     ref.close()
+
+
+@pytest.mark.gpu
+def test_shim_reads_every_configuration_key(shim, solver_mod, synth, layout, ref):
+    """Every XML key lands in its own field: configured from the XML-keyed dictionary of config_cases.ALL_DISTINCT (no two
+    values of a group equal), the shim's outputs are bit for bit those of BatchedVSMPC(ALL_DISTINCT) for the same
+    records -- and not those of the default configuration."""
+    import config_cases as cc
+    cfg, _ = cc.configs(ref, cc.PAPER, cc.all_distinct(cc.PAPER))
+    rec = cc.records(cfg, n=2)
+    mpc = shim.VariableSamplingMPC()
+    assert mpc.configureRecord(cc.xml_params(cfg), np.zeros(23), np.zeros(3))
+    raw = solver_mod.BatchedVSMPC(cfg, device=0, max_batch=len(rec))
+    dflt = solver_mod.BatchedVSMPC(layout.paper_config(), device=0, max_batch=len(rec))
+    try:
+        x, fm, st, it = raw.solve(rec)
+        xd, fmd, _, _ = dflt.solve(rec)
+        q = np.zeros(23)
+        for k in range(len(rec)):
+            assert mpc.update(rec[k]) and mpc.solveMPC()
+            assert mpc.getQPProblemStatus() == st[k] == layout.STATUS_SOLVED
+            q[3:11] += fm[k, 0:8]
+            np.testing.assert_array_equal(mpc.getJointsReferencePosition(), q)
+            np.testing.assert_array_equal(mpc.getThrottleReference(), fm[k, 12:16])
+            np.testing.assert_array_equal(mpc.getThrustReference(), fm[k, 16:20])
+            np.testing.assert_array_equal(mpc.getThrustDotReference(), fm[k, 20:24])
+            np.testing.assert_array_equal(mpc.getMPCSolution(), x[k, cfg.off_joints:])
+            assert not np.array_equal(fm[k, 0:8], fmd[k, 0:8])
+    finally:
+        raw.close()
+        dflt.close()

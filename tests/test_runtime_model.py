@@ -13,13 +13,12 @@ import numpy as np
 import pytest
 
 from conftest import relerr
+from config_cases import NON_DEFAULT
 import runtime_model as rm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-NON_DEFAULT = dict(w_delta_joint=(65000.0, 30000.0, 1000.0, 65000.0, 200.0, 5e4, 8e3, 65000.0), w_reg_joint_pos=0.0,
-                   throttle_min=10.0, throttle_max=90.0, period_small=0.004)
 
 
 def _cases(layout, synth, ref, horizon, settings, n_per_workload=2):

@@ -6,10 +6,9 @@ import numpy as np
 import pytest
 
 from conftest import relerr
+from config_cases import NON_DEFAULT
 import sensitivity_model as sm
 
-NON_DEFAULT = dict(w_delta_joint=(65000.0, 30000.0, 1000.0, 65000.0, 200.0, 5e4, 8e3, 65000.0), w_reg_joint_pos=0.0,
-                   throttle_min=10.0, throttle_max=90.0, period_small=0.004)
 CASES = [(h, s) for h in ((17, 7, 12), (20, 5, 9)) for s in ("default", "non_default")]
 
 
