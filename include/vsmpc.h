@@ -87,7 +87,8 @@ typedef struct vsmpc_config {
 #define VSMPC_IN_LLIN 67      /* 24 Lambda_lin,B 3x8 row-major (systemDynamicsVSMPC.cpp:321-350)               */
 #define VSMPC_IN_LANG 91      /* 24 Lambda_ang,B 3x8 row-major (systemDynamicsVSMPC.cpp:159-206)               */
 #define VSMPC_IN_INERTIA 115  /*  9 I_G 3x3 row-major (systemDynamicsVSMPC.cpp:128-130)                        */
-#define VSMPC_IN_RPY 124      /*  3 base RPY used for W^-1 (systemDynamicsVSMPC.cpp:132-147)                   */
+#define VSMPC_IN_RPY 124      /*  3 base RPY used for W^-1 (systemDynamicsVSMPC.cpp:132-147); W^-1 has no yaw
+                                    term, so entry 2 is never read (tests/test_gpu_record_parity.py pins it)   */
 #define VSMPC_IN_PREF 127     /*  3 QPInput::getPosCoMReference (systemDynamicsVSMPC.cpp:316)                  */
 #define VSMPC_IN_RPYINIT 130  /*  3 configure-time RPY m_rpyInit (systemDynamicsVSMPC.cpp:67,100)              */
 #define VSMPC_IN_T0 133       /*  4 linearisation thrust (systemDynamicsVSMPC.cpp:401-409)                     */
@@ -98,7 +99,9 @@ typedef struct vsmpc_config {
 #define VSMPC_IN_QERR 153     /*  8 q_cmd,sel - q_ref0 (costsVSMPC.cpp:574-589)                                */
 #define VSMPC_IN_HOLD 161     /*  1 != 0 when the 20-tick hold pins v0 this tick (constraintsVSMPC.cpp:351)    */
 #define VSMPC_IN_XREF 162     /* 12*(nIter-nIterSmall+1): reference window, column-major xref[col*12+row],
-                                    rows = CoM, h_lin, RPY, h_ang (costsVSMPC.cpp:96-99,183-264)               */
+                                    rows = CoM, h_lin, RPY, h_ang (costsVSMPC.cpp:96-99,183-264).  Node k reads
+                                    column 0 (k - 1 < nIterSmall) or k - 1 - nIterSmall (costsVSMPC.cpp:191-200),
+                                    so the last column is never read (pinned by the same test)                 */
 
 /* First-move block written per instance (variableSamplingMPC.cpp:99-102,138-151), 24 doubles. */
 #define VSMPC_FM_DQ 0          /* 8 joint-position increments  x[off_joints .. +8]             */

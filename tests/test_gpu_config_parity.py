@@ -180,18 +180,16 @@ def test_one_field_at_a_time(solver_mod, ref, layout):
     assert n == 33
 
 
-def test_entry_points_are_bit_identical_at_all_distinct(solver_mod, synth, layout, ref):
-    """tick, solve_device and the pinned direct-store path against solve, once with every configuration value distinct"""
+def _check_entry_points(solver_mod, layout, cfg, recs):
+    """solve_device, the pinned direct-store path and tick against solve, bit for bit; returns what solve gave"""
     import torch
     _lib = importlib.import_module(PKG + "._lib")
     lib = _lib.load()
-    cfg, _ = cc.configs(ref, cc.PAPER, cc.all_distinct(cc.PAPER))
-    B = 24
-    recs = np.concatenate([synth.make_batch(cfg, 12, workload="takeoff"), cc.records(cfg, n=4)[:12]])
+    B = len(recs)
     m = _tuned(solver_mod, cfg, B)
     try:
         x, fm, st, it = m.solve(recs)
-        assert (st == layout.STATUS_SOLVED).all() and it.max() > 1
+        assert (st == layout.STATUS_SOLVED).all(), st
         dev = torch.device("cuda:0")
         d_in = torch.from_numpy(recs).to(dev)
         d_x = torch.zeros((B, cfg.n_var), dtype=torch.float64, device=dev)
@@ -241,6 +239,16 @@ def test_entry_points_are_bit_identical_at_all_distinct(solver_mod, synth, layou
         assert (st1 == layout.STATUS_SOLVED).all()
     finally:
         m.close()
+    return x, fm, st, it
+
+
+def test_entry_points_are_bit_identical_at_all_distinct(solver_mod, synth, layout, ref):
+    """tick, solve_device and the pinned direct-store path against solve, once with every configuration value distinct"""
+    cfg, _ = cc.configs(ref, cc.PAPER, cc.all_distinct(cc.PAPER))
+    recs = np.concatenate([synth.make_batch(cfg, 12, workload="takeoff"), cc.records(cfg, n=4)[:12]])
+    assert len(recs) == 24
+    _, _, _, it = _check_entry_points(solver_mod, layout, cfg, recs)
+    assert it.max() > 1
 
 
 def test_closed_loop_rollout_at_all_distinct(solver_mod, ref, layout):
