@@ -12,9 +12,12 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libvsmpc.so")
-SOURCES = ["vsmpc_kernels.hip", "vsmpc_rollout.hip", "vsmpc_capi.hip", "vsmpc_jet.hip", "vsmpc_provider.hip",
+SOLVE = "vsmpc_kernels.hip"     # the per-horizon unit: compiled twice per horizon (production / diagnostic instantiations)
+SOURCES = [SOLVE, "vsmpc_dispatch.hip", "vsmpc_rollout.hip", "vsmpc_capi.hip", "vsmpc_jet.hip", "vsmpc_provider.hip",
            "vsmpc_runtime.hip"]
-HEADERS = ["vsmpc_device.hpp", "vsmpc_launch.hpp", "vsmpc_p0.hpp", "vsmpc_panel_asm.inc", "vsmpc_runtime_body.inc", "vsmpc_jet_device.hpp", "vsmpc_horizons.def", os.path.join("..", "..", "include", "vsmpc.h"),
+HEADERS = ["vsmpc_device.hpp", "vsmpc_launch.hpp", "vsmpc_p0.hpp", "vsmpc_smem.hpp", "vsmpc_p1_syrk.hpp", "vsmpc_p1_struct.hpp",
+           "vsmpc_p3.hpp", "vsmpc_p4.hpp", "vsmpc_p5.hpp", "vsmpc_panel_asm.inc",
+           "vsmpc_runtime_body.inc", "vsmpc_jet_device.hpp", "vsmpc_horizons.def", os.path.join("..", "..", "include", "vsmpc.h"),
            os.path.join("..", "..", "include", "vsmpc_jet.h")]
 
 
@@ -64,19 +67,19 @@ SCHED_MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 
 
 def _units():
-    """(object name, source, extra flags): vsmpc_kernels.hip is compiled once for its common part and twice per horizon
-    (production / diagnostic instantiations, see the note on translation units in the file), everything else once."""
-    units = [("kernels_common", "vsmpc_kernels.hip", ["-DVS_TU_COMMON"])]
+    """(object name, source, extra flags): vsmpc_kernels.hip is compiled twice per horizon (production / diagnostic
+    instantiations, see the note on the launchers in the file), everything else once."""
+    units = []
     for n, ns, hc in horizons():
         # Machine scheduler strategy per horizon (measured on MI355X, default against -amdgpu-sched-strategy=max-ilp): the
         # short-horizon kernels (<= 256 registers, two workgroups per CU) gain 2-3 % with max-ilp -- 36.6 -> 35.7 us per 256-launch,
         # 327 -> 317 us per 4096 -- the long-horizon kernel (512 registers, tiles in AGPRs) loses 2.6 % (1,593 -> 1,634 us).
         sched = SCHED_MAX_ILP if n <= 24 else []
         for st in (0, 1):
-            units.append((f"kernels_{n}_{ns}_{hc}_{'diag' if st else 'prod'}", "vsmpc_kernels.hip",
+            units.append((f"kernels_{n}_{ns}_{hc}_{'diag' if st else 'prod'}", SOLVE,
                           [f"-DVS_TU_HORIZON={n},{ns},{hc}", f"-DVS_TU_STAMPS={st}"] + sched))
     for src in SOURCES:
-        if src != "vsmpc_kernels.hip":
+        if src != SOLVE:
             units.append((os.path.splitext(src)[0], src, []))
     return units
 
@@ -86,7 +89,7 @@ def _deps(src):
 
 
 def _extra_flags():
-    """VSMPC_HIPCC_FLAGS: measurement builds (tools/exp_build.sh), e.g. -DVS_DIAG_SPLIT"""
+    """VSMPC_HIPCC_FLAGS: measurement builds, e.g. -DVS_DIAG_P3 (tools/gpu_phases.py)"""
     return os.environ.get("VSMPC_HIPCC_FLAGS", "").split()
 
 

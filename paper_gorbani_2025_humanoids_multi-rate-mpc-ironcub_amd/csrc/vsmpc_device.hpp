@@ -61,10 +61,6 @@ struct Dims {
     static constexpr int PCOLS = BLOCK / 2;
     static constexpr int CPT = (NP + PCOLS - 1) / PCOLS;
     static constexpr int WG_PER_CU = NP <= 128 ? 2 : 1;
-    // shared panels: a wavefront carries the diagonal tile in lanes 0..15 of its first row slot and PANEL_RPW rows below
-    // it in the remaining lanes of PANEL_SLOTS slots of 64 rows; at most NWAVES - 1 wavefronts share a panel
-    static constexpr int PANEL_SLOTS = (NP - 16 + 48 * (NWAVES - 1) - 1) / (48 * (NWAVES - 1)) <= 1 ? 1 : 2;
-    static_assert((NP - 16 + (64 * PANEL_SLOTS - 16) - 1) / (64 * PANEL_SLOTS - 16) <= NWAVES - 1, "panel 0 leaves one wavefront for the side work");
     // Where the factor lives (v10).  The trailing matrix and, after its column has been the panel, every finished
     // off-diagonal tile of L stay in the REGISTERS of the wavefront that owns the tile.  LDS only ever holds
     //   * a ring of two panel columns (column p while it is factored / applied, column p+1 being handed over),
@@ -83,7 +79,7 @@ struct Dims {
     static constexpr int SCRATCH_TILES = ((SCRATCH_QP > SCRATCH_P6 ? SCRATCH_QP : SCRATCH_P6) + TS - 1) / TS;
     static constexpr int CORNER_TILE0 = RING_TILES > SCRATCH_TILES ? RING_TILES : SCRATCH_TILES;
     static constexpr int L_TILES = CORNER_TILE0 + NCORNER;   // LDS tiles addressed through tile_off()
-    // Structured condensing (kernel v13, P1s in vsmpc_kernels.hip): the condensed Hessian from forward / adjoint
+    // Structured condensing (kernel v13, P1s in vsmpc_p1_struct.hpp): the condensed Hessian from forward / adjoint
     // recursions of 3 HC generator columns + NV throttle columns + the affine column per half, whose forward
     // trajectories (9 N doubles) stay in the registers of the lane that owns the column.  Needs the trajectory to fit
     // the register file and the joint rows to be tile aligned; other horizons condense with the SYRK (P1).

@@ -1,5 +1,5 @@
-// Host-visible launch interface of vsmpc_kernels.hip (internal to the library; the public
-// boundary is include/vsmpc.h).
+// Host-visible launch interface of the kernel units (vsmpc_dispatch.hip, vsmpc_kernels.hip, ...; internal to the library;
+// the public boundary is include/vsmpc.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,6 +41,15 @@ hipError_t launch_solve(int variant, int form, const DevCfg& cfg, const double* 
                         hipStream_t stream);
 hipError_t launch_linearize(int variant, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,
                             double* Bt, double* c, hipStream_t stream);
+// the launchers of one horizon: explicit instantiations in that horizon's units of vsmpc_kernels.hip (STAMPS: the diagnostic
+// one), which launch_solve / launch_linearize (vsmpc_dispatch.hip) dispatch onto
+template <int N, int NS, int HC, bool STAMPS>
+hipError_t launch_solve_dims(int form, const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm,
+                             int* d_status, int* d_iters, double* dbgM, double* dbgL, unsigned long long* stamps,
+                             hipStream_t stream);
+template <int N, int NS, int HC>
+hipError_t launch_linearize_dims(const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj, double* Bt,
+                                 double* c, hipStream_t stream);
 
 // Runtime-sized solve kernel (vsmpc_runtime.hip): every horizon config_valid() accepts, sizes as kernel arguments.
 struct RtDims {

@@ -49,7 +49,7 @@ EDGE = {
     "w_throttle_parity_min": dict(w_throttle=W_THROTTLE_PARITY_MIN),
 }
 
-# DUAL_MAX_ACTIVE / VS_DUAL3_MAX of box_qp in csrc/vsmpc_kernels.hip (test_config_cases.py checks the copy against the
+# DUAL_MAX_ACTIVE / DUAL3_MAX of box_qp in csrc/vsmpc_p4.hpp (test_config_cases.py checks the copy against the
 # source text); which form (21, 9, 15) runs is not asserted anywhere, so it has no entry
 DUAL_FORM_MAX = {(17, 7, 12): 16, (34, 14, 24): 24}
 
@@ -177,7 +177,7 @@ def one_at_a_time():
 
 def first_violated(ref, rcfg, rec):
     """Size of the first violated set: how many throttles of the solve with only the hold pin enforced (the first pass of
-    the active-set loop) leave the box.  The tuned kernels pick the box-QP formulation by it (csrc/vsmpc_kernels.hip,
+    the active-set loop) leave the box.  The tuned kernels pick the box-QP formulation by it (csrc/vsmpc_p4.hpp,
     box_qp): the dual form up to DUAL_FORM_MAX[horizon] violated throttles, the primal form on the Schur complement for
     more."""
     H, g, Ac, lo, hi = ref.assemble_dense(rcfg, rec)

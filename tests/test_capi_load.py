@@ -109,7 +109,7 @@ def test_product_path_does_not_touch_oracle():
 def test_build_adds_a_horizon_from_the_environment(tmp_path, solver_mod):
     """Row a14: the horizon table is a build-time input (the reference sizes itself from its XML at run time,
     variableSamplingMPC.cpp:24-45).  VSMPC_HORIZONS adds an instantiation: build.horizons() parses it, and a library built
-    with an extra horizon (tools/quick_build.sh: a copy of the sources, the tracked table is left alone) carries the solve
+    with an extra horizon (tools/quick_build.sh: build.py on a copy of the sources, the tracked table is left alone) carries the solve
     kernel for it.  Compile-only: vsmpc_create needs a device."""
     import importlib
     import subprocess

@@ -146,10 +146,10 @@ def test_one_at_a_time_cases_move_the_oracles_solution(ref):
 
 
 def test_dual_form_thresholds_match_the_kernel_source():
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), cc.PKG, "csrc", "vsmpc_kernels.hip")).read()
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), cc.PKG, "csrc", "vsmpc_p4.hpp")).read()
     assert int(re.search(r"constexpr int DUAL_MAX_ACTIVE = (\d+);", src).group(1)) == cc.DUAL_FORM_MAX[(17, 7, 12)]
-    assert int(re.search(r"#define VS_DUAL3_MAX (\d+)", src).group(1)) == cc.DUAL_FORM_MAX[(34, 14, 24)]
-    assert "n_violated <= (DUAL3 ? VS_DUAL3_MAX : DUAL_MAX_ACTIVE)" in src
+    assert int(re.search(r"constexpr int DUAL3_MAX = (\d+);", src).group(1)) == cc.DUAL_FORM_MAX[(34, 14, 24)]
+    assert "n_violated <= (DUAL3 ? DUAL3_MAX : DUAL_MAX_ACTIVE)" in src
 
 
 @pytest.mark.parametrize("horizon", cc.HORIZONS)

@@ -27,8 +27,8 @@ def kernels(solver_mod):
 
 
 def production(kernels, n, ns, hc):
-    """solve_kernel<Dims<n, ns, hc>, STAMPS = false, FORM = 1, PLDS = *>"""
-    pat = re.compile(rf"solve_kernel<.*Dims<{n}, {ns}, {hc}>\s*,\s*false,\s*1,\s*(true|false)>")
+    """solve_kernel<Dims<n, ns, hc>, STAMPS = false, FORM = 1>"""
+    pat = re.compile(rf"solve_kernel<.*Dims<{n}, {ns}, {hc}>\s*,\s*false,\s*1>")
     return {k: v for k, v in kernels.items() if pat.search(k)}
 
 

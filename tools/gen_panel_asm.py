@@ -3,7 +3,7 @@
 
 Why.  A panel stream is ~550 vector instructions in ONE wavefront, and a lone wavefront issues one FP64 vector instruction
 every ~5.5 cycles whatever the dependencies look like (tools/microbench/lat_probe.hip, f64_issue.hip): the stream costs
-its instruction count.  In the C++ form (panel_factor<1, 16> of vsmpc_kernels.hip) two thirds of the instructions are
+its instruction count.  In the C++ form (panel_factor of vsmpc_p3.hpp, sixteen pivots) two thirds of the instructions are
 v_readlane pairs: every entry l_cj of the pivot column is moved to a scalar register pair so that the FMA that updates
 column c can read it.  gfx90a+ has a cheaper broadcast for FP64: DPP `row_newbcast:c` on v_fmac_f64 -- lane c of every row
 of 16 lanes feeds all 16 lanes of that row, inside the FMA.  That needs the broadcast source in every 16-lane row, so:
@@ -391,7 +391,7 @@ def function_rows(name, slots, comment):
 
 HEADER = """// GENERATED by tools/gen_panel_asm.py -- do not edit (the why and the how are in that file's header).
 // Sixteen-pivot panel streams of P3 as hand-scheduled gfx950 assembly.  Same arithmetic, operation by operation, as
-// panel_factor<1, 16> (bit-identical results); what differs is how the pivot column reaches the other lanes and the order.
+// the C++ stream panel_factor (vsmpc_p3.hpp) with sixteen pivots (bit-identical results); what differs is how the pivot column reaches the other lanes and the order.
 """
 
 

@@ -1,5 +1,5 @@
-// The 16-pivot panel stream of P3 in isolation: the C++ form the compiler schedules (panel_factor<1, 16> of
-// vsmpc_kernels.hip, one row per lane, v_readlane broadcasts) against the hand-scheduled assembly of
+// The 16-pivot panel stream of P3 in isolation: the C++ form the compiler schedules (panel_factor of
+// vsmpc_p3.hpp with sixteen pivots, one row per lane, v_readlane broadcasts) against the hand-scheduled assembly of
 // csrc/vsmpc_panel_asm.inc (tools/gen_panel_asm.py).  One wavefront per workgroup, one workgroup per CU; s_memtime around
 // the stream, LDS loads and stores included in both.  Prints the median cycles of each and whether the results agree bit
 // for bit.

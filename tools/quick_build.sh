@@ -1,17 +1,16 @@
 #!/bin/bash
-# Experiment build with ONE horizon (fast: ~40 s instead of 2.5 min): tools/quick_build.sh [N,NS,HC] [extra hipcc flags]
-# Writes $Q/libvsmpc.so (or $QUICK_OUT/libvsmpc.so); the tracked csrc/vsmpc_horizons.def is left alone (a copy of
-# the sources is compiled).
+# Experiment build beside the tree: tools/quick_build.sh [N,NS,HC[;N,NS,HC...]] [extra hipcc flags]
+# Runs build.py on a copy of the sources with VSMPC_HORIZONS / VSMPC_HIPCC_FLAGS set and writes $Q/libvsmpc.so (or
+# $QUICK_OUT/libvsmpc.so); the tracked csrc/vsmpc_horizons.def and the library of the tree are left alone.
 set -e
 cd "$(dirname "$0")/.."
 PKG=paper_gorbani_2025_humanoids_multi-rate-mpc-ironcub_amd
 H=${1:-17,7,12}; shift || true
 Q=${QUICK_OUT:-exp/quick}
 rm -rf $Q/src && mkdir -p $Q/src/$PKG/csrc $Q/src/include
+cp $PKG/build.py $Q/src/$PKG/
 cp $PKG/csrc/*.hip $PKG/csrc/*.hpp $PKG/csrc/*.inc $Q/src/$PKG/csrc/
 cp include/*.h $Q/src/include/
-echo "X($(echo $H | sed 's/,/, /g'))" > $Q/src/$PKG/csrc/vsmpc_horizons.def
-S=$Q/src/$PKG/csrc
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wl,-rpath,/opt/rocm/lib "$@" \
-    -o $Q/libvsmpc.so $S/vsmpc_kernels.hip $S/vsmpc_rollout.hip $S/vsmpc_capi.hip $S/vsmpc_jet.hip $S/vsmpc_provider.hip
+VSMPC_HORIZONS="$H" VSMPC_HIPCC_FLAGS="$*" python3 $Q/src/$PKG/build.py > $Q/build.log 2>&1 || { cat $Q/build.log; exit 1; }
+cp $Q/src/$PKG/libvsmpc.so $Q/libvsmpc.so
 echo "built $Q/libvsmpc.so for horizon $H"

@@ -1,6 +1,6 @@
-"""Where a solve kernel spills: compiles one translation unit of vsmpc_kernels.hip with --save-temps and lists every
+"""Where a solve kernel spills: compiles one per-horizon unit of vsmpc_kernels.hip with --save-temps and lists every
 scratch store / reload of the chosen instantiation with the nearest basic-block label in front of it (inlined function
-names survive in the labels).     python tools/spill_map.py 34,14,24 [form=1] [plds=0]"""
+names survive in the labels).     python tools/spill_map.py 34,14,24 [form=1]"""
 import collections
 import os
 import re
@@ -15,7 +15,6 @@ SRC = os.path.join(ROOT, "paper_gorbani_2025_humanoids_multi-rate-mpc-ironcub_am
 def main():
     hz = sys.argv[1] if len(sys.argv) > 1 else "34,14,24"
     form = sys.argv[2] if len(sys.argv) > 2 else "1"
-    plds = sys.argv[3] if len(sys.argv) > 3 else "0"
     tmp = os.environ.get("SPILL_TMP") or tempfile.mkdtemp(prefix="spill_")
     asm = os.path.join(tmp, "vsmpc_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
     if not os.path.exists(asm) or os.environ.get("SPILL_REBUILD"):
@@ -24,7 +23,7 @@ def main():
                        + os.environ.get("VSMPC_HIPCC_FLAGS", "").split(), cwd=tmp, check=True, capture_output=True)
     S = open(asm).read().split("\n")
     n, ns, hc = hz.split(",")
-    pat = rf"^_ZN5vsmpc12solve_kernelINS_4DimsILi{n}ELi{ns}ELi{hc}EEELb0ELi{form}ELb{plds}E.*:"
+    pat = rf"^_ZN5vsmpc12solve_kernelINS_4DimsILi{n}ELi{ns}ELi{hc}EEELb0ELi{form}EE.*:"
     start = [i for i, l in enumerate(S) if re.match(pat, l)][0]
     end = [i for i in range(start, len(S)) if S[i].startswith(".Lfunc_end")][0]
     body = S[start:end]
