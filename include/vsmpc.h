@@ -117,7 +117,8 @@ typedef struct vsmpc_handle vsmpc_handle;
  * (variableSamplingMPC.cpp:7-86): validates the configuration, selects the kernel instantiation and
  * allocates every device and staging buffer for `max_batch` instances on HIP device `device` (solve, linearise,
  * kinematics, diagnostics).  No allocation happens in any later call on the handle; a rollout object allocates at its
- * own create and grows its log buffer only when a longer logged run is requested.
+ * own create, grows its log buffer only when a longer logged run is requested, and allocates the buffers of a tree plant
+ * or of per-instance tunables in the first vsmpc_rollout_set_tree / vsmpc_rollout_set_tunables that asks for them.
  * Horizons: any (nIter, nIterSmall, controlHorizon) listed in csrc/vsmpc_horizons.def has a kernel instantiation
  * (the kernels are straight-line code generated per horizon); others return VSMPC_ERR_UNSUPPORTED_CONFIG -- add the
  * horizon to VSMPC_HORIZONS and rebuild, or use the runtime-sized kernel (vsmpc_create_ex below, or
@@ -146,6 +147,7 @@ int vsmpc_create(const vsmpc_config* cfg, int device, int max_batch, vsmpc_handl
 #define VSMPC_CREATE_RUNTIME_FALLBACK 0x1u
 #define VSMPC_CREATE_RUNTIME_ONLY 0x2u
 #define VSMPC_CREATE_SENSITIVITY 0x4u
+#define VSMPC_CREATE_TUNABLES 0x8u      /* device staging of vsmpc_solve_batch_tuned: max_batch x VSMPC_TUNE_SIZE doubles */
 int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned flags, vsmpc_handle** out);
 void vsmpc_destroy(vsmpc_handle* h);
 
@@ -168,6 +170,36 @@ int vsmpc_solve_batch(vsmpc_handle* h, const double* in, int batch, double* x, d
  * no synchronisation): the form a resident batch driver uses.  batch <= vsmpc_max_batch(h). */
 int vsmpc_solve_batch_device(vsmpc_handle* h, const double* d_in, int batch, double* d_x,
                              double* d_first_move, int* d_status, int* d_iters, void* stream);
+
+/*
+ * Per-instance tunables: one launch whose instances each carry their own weights and throttle box (gain studies over the
+ * batch axis).  The TUNABLES of an instance are the vsmpc_config fields that change neither a size nor the time grid: the
+ * six 3-vectors of state weights, w_delta_joint[8], w_throttle, w_initial_throttle, w_reg_joint_pos, throttle_min and
+ * throttle_max.  The STRUCTURAL fields (n_iter, n_iter_small, control_horizon, use_jet_dynamic and the three periods) stay
+ * the handle's.
+ *
+ * vsmpc_pack_tunables converts `n` configurations into rows of VSMPC_TUNE_SIZE doubles, out[n][VSMPC_TUNE_SIZE] (host).
+ * A row is OPAQUE: it is "produced by vsmpc_pack_tunables", in the form the kernels keep the configuration in, by the
+ * same code that converts the handle's own configuration at create (a row packed from the handle's configuration is bit
+ * for bit what the plain entries solve with).  Returns VSMPC_ERR_INVALID_ARG when a cfgs[i] differs from the handle in a
+ * structural field or fails the value checks of vsmpc_create; vsmpc_strerror(VSMPC_ERR_INVALID_ARG) then names the
+ * configuration and the field, until the next call on that thread that packs successfully or returns
+ * VSMPC_ERR_INVALID_ARG for a reason of its own (which gets the plain text).  No device work.
+ */
+#define VSMPC_TUNE_SIZE 32
+int vsmpc_pack_tunables(const vsmpc_handle* h, const vsmpc_config* cfgs, int n, double* out /* [n][VSMPC_TUNE_SIZE] */);
+/* vsmpc_solve_batch with instance i solved under row i of `tunables` (host, [batch][VSMPC_TUNE_SIZE]): the same chunking
+ * and the same treatment of pinned and pageable buffers.  Needs a handle created with VSMPC_CREATE_TUNABLES, which
+ * allocates the device staging of the rows at create (otherwise VSMPC_ERR_UNSUPPORTED_CONFIG).  Tuned and runtime
+ * handles; vsmpc_set_kernel_form applies as to vsmpc_solve_batch.  A non-finite tunable ends like a non-finite record:
+ * status VSMPC_STATUS_NUMERICAL for that instance.  Sensitivities with per-instance tunables are out of scope:
+ * vsmpc_sensitivity_batch always uses the handle's configuration. */
+int vsmpc_solve_batch_tuned(vsmpc_handle* h, const double* in, const double* tunables, int batch, double* x,
+                            double* first_move, int* status, int* iters, void* stream);
+/* Same, all pointers are DEVICE pointers (d_tunables 16-byte aligned) and the call only enqueues work on `stream`.
+ * Needs no create flag. */
+int vsmpc_solve_batch_tuned_device(vsmpc_handle* h, const double* d_in, const double* d_tunables, int batch, double* d_x,
+                                   double* d_first_move, int* d_status, int* d_iters, void* stream);
 
 /*
  * Sensitivities of the solution to the measured state X0 (in[VSMPC_IN_X0 .. +26]).  X0 enters the QP only through the
@@ -397,6 +429,14 @@ int vsmpc_rollout_set_attitude_tracks(vsmpc_rollout* r, const double* traj_rpy, 
  * (tree->robot_joint[j] = 3 + j for the default selector).  NULL switches back to the parametric plant.  Call before
  * vsmpc_rollout_reset; a tick is then six launches instead of two (still replayed from a captured graph). */
 int vsmpc_rollout_set_tree(vsmpc_rollout* r, const vsmpc_tree* tree);
+/* Per-instance tunables of the rollout's solves: tunables[batch][VSMPC_TUNE_SIZE] (host, rows of vsmpc_pack_tunables)
+ * are copied to a device buffer the rollout owns, and every tick's solve launch -- those inside the captured graph too --
+ * is then of the per-instance-tunables kind.  NULL restores the handle's shared configuration.  Call before
+ * vsmpc_rollout_reset, like vsmpc_rollout_set_tree; the captured ticks are rebuilt.  The record and advance kernels read
+ * no tunable: the solve is the only launch of a tick that changes.  The first call with rows allocates the device buffer
+ * (batch x VSMPC_TUNE_SIZE doubles, kept until vsmpc_rollout_destroy), as vsmpc_rollout_set_tree allocates on first use;
+ * a call that fails leaves the rollout as it was, runnable without a reset. */
+int vsmpc_rollout_set_tunables(vsmpc_rollout* r, const double* tunables);
 int vsmpc_rollout_get_state(vsmpc_rollout* r, double* state);
 int vsmpc_rollout_get_records(vsmpc_rollout* r, double* records);
 

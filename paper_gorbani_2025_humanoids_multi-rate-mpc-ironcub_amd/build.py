@@ -12,12 +12,12 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libvsmpc.so")
-SOLVE = "vsmpc_kernels.hip"     # the per-horizon unit: compiled twice per horizon (production / diagnostic instantiations)
+SOLVE = "vsmpc_kernels.hip"     # the per-horizon unit: production / diagnostic / per-instance-tunables instantiations
 SOURCES = [SOLVE, "vsmpc_dispatch.hip", "vsmpc_rollout.hip", "vsmpc_capi.hip", "vsmpc_jet.hip", "vsmpc_provider.hip",
            "vsmpc_runtime.hip"]
 HEADERS = ["vsmpc_device.hpp", "vsmpc_launch.hpp", "vsmpc_p0.hpp", "vsmpc_smem.hpp", "vsmpc_p1_syrk.hpp", "vsmpc_p1_struct.hpp",
            "vsmpc_p3.hpp", "vsmpc_p4.hpp", "vsmpc_p5.hpp", "vsmpc_panel_asm.inc",
-           "vsmpc_runtime_body.inc", "vsmpc_jet_device.hpp", "vsmpc_horizons.def", os.path.join("..", "..", "include", "vsmpc.h"),
+           "vsmpc_runtime_body.inc", "vsmpc_solve_body.inc", "vsmpc_jet_device.hpp", "vsmpc_horizons.def", os.path.join("..", "..", "include", "vsmpc.h"),
            os.path.join("..", "..", "include", "vsmpc_jet.h")]
 
 
@@ -67,8 +67,11 @@ SCHED_MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 
 
 def _units():
-    """(object name, source, extra flags): vsmpc_kernels.hip is compiled twice per horizon (production / diagnostic
-    instantiations, see the note on the launchers in the file), everything else once."""
+    """(object name, source, extra flags): vsmpc_kernels.hip is compiled four times per horizon (production, diagnostic and
+    the two condensing forms of the per-instance-tunables kind, see the note on the launchers in the file), everything
+    else once.  Which horizons have a structured form is decided in the C++ (Dims::STRUCT_P1), so the structured unit is
+    listed for every horizon: where the horizon has none (21,9,15 of the default table) it holds no kernel, only a
+    launcher that returns hipErrorInvalidValue and that the dispatcher never calls."""
     units = []
     for n, ns, hc in horizons():
         # Machine scheduler strategy per horizon (measured on MI355X, default against -amdgpu-sched-strategy=max-ilp): the
@@ -78,6 +81,9 @@ def _units():
         for st in (0, 1):
             units.append((f"kernels_{n}_{ns}_{hc}_{'diag' if st else 'prod'}", SOLVE,
                           [f"-DVS_TU_HORIZON={n},{ns},{hc}", f"-DVS_TU_STAMPS={st}"] + sched))
+        for form in (0, 1):     # the per-instance-tunables kind: one unit per condensing form (1 = structured)
+            units.append((f"kernels_{n}_{ns}_{hc}_tuned_{'struct' if form else 'syrk'}", SOLVE,
+                          [f"-DVS_TU_HORIZON={n},{ns},{hc}", "-DVS_TU_STAMPS=2", f"-DVS_TU_FORM={form}"] + sched))
     for src in SOURCES:
         if src != SOLVE:
             units.append((os.path.splitext(src)[0], src, []))

@@ -30,6 +30,9 @@ struct vsmpc_handle {
     double* d_sdfm;
     int* d_sact;
     int* d_sflags;
+    // VSMPC_CREATE_TUNABLES: device staging of the rows of vsmpc_solve_batch_tuned, max_batch x VSMPC_TUNE_SIZE
+    int tunables;
+    double* d_tun;
     int form;       // condensing form of the solve kernel (vsmpc_set_kernel_form)
     KinOpts kin;     // vsmpc_set_kinematics_options
     int device;
@@ -55,7 +58,7 @@ struct vsmpc_handle {
     // small batches through the host-pointer entry (the reference's own use: one instance per tick): pinned,
     // device-mapped staging that the kernel reads and writes directly, instead of five small copies
     double* h_stage;      // host view:  in[ZC_MAX][n_in] | x[ZC_MAX][n_var] | fm[ZC_MAX][24] | status[ZC_MAX] | iters[ZC_MAX] |
-                          //             kin[ZC_MAX][VSMPC_KIN_SIZE] (vsmpc_tick)
+                          //             kin[ZC_MAX][VSMPC_KIN_SIZE] (vsmpc_tick) | tun[ZC_MAX][VSMPC_TUNE_SIZE]
     double* d_stage;      // device view of the same allocation (its own base pointer: the two views are unrelated addresses)
 };
 
@@ -102,6 +105,9 @@ struct vsmpc_rollout {
     vsmpc_tree tree;
     double* d_rs;             // provider states [batch][VSMPC_RS_SIZE]
     double* d_ro;             // Robot-level outputs of the provider [batch][VSMPC_RO_SIZE]
+    // per-instance tunables (vsmpc_rollout_set_tunables)
+    int use_tun;
+    double* d_tun;            // rows [batch][VSMPC_TUNE_SIZE]
 };
 
 namespace {
@@ -123,8 +129,16 @@ int hip_fail(hipError_t e, const char* what) {
 
 // The solve launch of a handle: the tuned instantiation, or the runtime-sized kernel with the workspace of instances
 // `first` .. `first + batch - 1` (a chunk of a larger batch must not share workspace with a chunk on another stream).
+// d_tun: rows of per-instance tunables of these instances (the tuned kind of either kernel), or nullptr: the handle's
+// configuration for all of them.
 hipError_t solve_launch(const vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_fm, int* d_status,
-                        int* d_iters, size_t first, hipStream_t s) {
+                        int* d_iters, size_t first, hipStream_t s, const double* d_tun = nullptr) {
+    if (d_tun != nullptr) {
+        if (h->runtime)
+            return launch_solve_runtime_tuned(h->rt, h->dev, d_in, d_tun, batch, h->d_ws + first * size_t(h->rt.ws_doubles), d_x,
+                                              d_fm, d_status, d_iters, s);
+        return launch_solve_tuned(h->variant, h->form, h->dev, d_in, d_tun, batch, d_x, d_fm, d_status, d_iters, s);
+    }
     if (h->runtime)
         return launch_solve_runtime(h->rt, h->dev, d_in, batch, h->d_ws + first * size_t(h->rt.ws_doubles), d_x, d_fm,
                                     d_status, d_iters, s);
@@ -133,7 +147,7 @@ hipError_t solve_launch(const vsmpc_handle* h, const double* d_in, int batch, do
 
 // carve-up of the mapped staging buffer (host or device view)
 struct Stage {
-    double* in; double* x; double* fm; int* st; int* it; double* kin;
+    double* in; double* x; double* fm; int* st; int* it; double* kin; double* tun;
 };
 Stage stage_view(const vsmpc_handle* h, double* base) {
     Stage v;
@@ -143,6 +157,7 @@ Stage stage_view(const vsmpc_handle* h, double* base) {
     v.st = reinterpret_cast<int*>(v.fm + size_t(ZC_MAX) * VSMPC_FM_SIZE);
     v.it = v.st + ZC_MAX;
     v.kin = v.fm + size_t(ZC_MAX) * (VSMPC_FM_SIZE + 1);
+    v.tun = v.kin + size_t(ZC_MAX) * VSMPC_KIN_SIZE;   // (every block before it is a multiple of ZC_MAX doubles: 64-byte aligned)
     return v;
 }
 
@@ -178,23 +193,55 @@ void fill_dt(const vsmpc_config& c, double* dt) {
         dt[i] = i < c.n_iter_small ? warp(double(i + 1)) - warp(double(i)) : c.period_large;
 }
 
-void fill_devcfg(const vsmpc_config& c, DevCfg& d) {
-    memset(&d, 0, sizeof(d));
-    fill_dt(c, d.dt);
+// The tunables of a configuration in the form the kernels keep them in (sCfg order, CFG_*): the row of
+// vsmpc_pack_tunables, and what fill_devcfg puts into the kernel argument.
+void fill_tunables(const vsmpc_config& c, double* row) {
+    static_assert(CFG_SIZE == VSMPC_TUNE_SIZE, "a row of tunables is the LDS configuration block");
     // diagonal of Q on the weighted rows (costsVSMPC.cpp:78-93): p, h_lin, rpy, h_ang | e_pos, e_rpy
     const double q[NWROWS] = {c.w_com_pos[0], c.w_com_pos[1], c.w_com_pos[2], c.w_lin_mom[0], c.w_lin_mom[1],
                               c.w_lin_mom[2], c.w_rpy[0], c.w_rpy[1], c.w_rpy[2], c.w_ang_mom[0],
                               c.w_ang_mom[1], c.w_ang_mom[2], c.w_com_pos_err[0], c.w_com_pos_err[1],
                               c.w_com_pos_err[2], c.w_rpy_err[0], c.w_rpy_err[1], c.w_rpy_err[2]};
-    for (int i = 0; i < NWROWS; ++i) d.sq[i] = std::sqrt(q[i]);
-    for (int i = 0; i < NJ; ++i) d.wj[i] = c.w_delta_joint[i] + c.w_reg_joint_pos;
-    d.w_reg = c.w_reg_joint_pos;
-    d.w_thr = c.w_throttle;
-    d.w_init = c.w_initial_throttle;
-    d.vmin = Jet::v_of_throttle_div(c.throttle_min);  // constraintsVSMPC.cpp:329-332
-    d.vmax = Jet::v_of_throttle_div(c.throttle_max);
+    for (int i = 0; i < NWROWS; ++i) row[CFG_SQ + i] = std::sqrt(q[i]);
+    for (int i = 0; i < NJ; ++i) row[CFG_WJ + i] = c.w_delta_joint[i] + c.w_reg_joint_pos;
+    row[CFG_WREG] = c.w_reg_joint_pos;
+    row[CFG_WTHR] = c.w_throttle;
+    row[CFG_WINIT] = c.w_initial_throttle;
+    row[CFG_VMIN] = Jet::v_of_throttle_div(c.throttle_min);  // constraintsVSMPC.cpp:329-332
+    row[CFG_VMAX] = Jet::v_of_throttle_div(c.throttle_max);
+    for (int i = CFG_VMAX + 1; i < CFG_SIZE; ++i) row[i] = 0.0;
+}
+
+void fill_devcfg(const vsmpc_config& c, DevCfg& d) {
+    memset(&d, 0, sizeof(d));
+    fill_dt(c, d.dt);
+    double row[CFG_SIZE];
+    fill_tunables(c, row);
+    for (int i = 0; i < NWROWS; ++i) d.sq[i] = row[CFG_SQ + i];
+    for (int i = 0; i < NJ; ++i) d.wj[i] = row[CFG_WJ + i];
+    d.w_reg = row[CFG_WREG];
+    d.w_thr = row[CFG_WTHR];
+    d.w_init = row[CFG_WINIT];
+    d.vmin = row[CFG_VMIN];
+    d.vmax = row[CFG_VMAX];
     d.use_jet = c.use_jet_dynamic ? 1 : 0;
     d.max_as_iter = 64;
+}
+
+// the value checks on the tunables: the name of the first field that fails, or nullptr
+const char* tunables_invalid(const vsmpc_config& c) {
+    const struct { const double* v; int n; const char* name; } w[] = {
+        {c.w_com_pos, 3, "w_com_pos"}, {c.w_lin_mom, 3, "w_lin_mom"}, {c.w_rpy, 3, "w_rpy"}, {c.w_ang_mom, 3, "w_ang_mom"},
+        {c.w_com_pos_err, 3, "w_com_pos_err"}, {c.w_rpy_err, 3, "w_rpy_err"}, {&c.w_throttle, 1, "w_throttle"},
+        {&c.w_initial_throttle, 1, "w_initial_throttle"}, {&c.w_reg_joint_pos, 1, "w_reg_joint_pos"}};
+    for (const auto& f : w)
+        for (int i = 0; i < f.n; ++i)
+            if (!(f.v[i] >= 0.0)) return f.name;
+    for (int i = 0; i < NJ; ++i)
+        if (!(c.w_delta_joint[i] + c.w_reg_joint_pos > 0.0)) return "w_delta_joint";  // condensed Hessian must stay PD
+    if (!(c.w_initial_throttle > 0.0)) return "w_initial_throttle";
+    if (!(c.throttle_max > c.throttle_min)) return "throttle_max";
+    return nullptr;
 }
 
 bool config_valid(const vsmpc_config& c) {
@@ -202,21 +249,29 @@ bool config_valid(const vsmpc_config& c) {
     if (c.n_iter_small < 2 || c.n_iter_small > c.control_horizon) return false;
     if (c.control_horizon > c.n_iter) return false;
     if (!(c.period_small > 0.0) || !(c.period_large > 0.0)) return false;
-    const double q[] = {c.w_com_pos[0], c.w_com_pos[1], c.w_com_pos[2], c.w_lin_mom[0], c.w_lin_mom[1],
-                        c.w_lin_mom[2], c.w_rpy[0], c.w_rpy[1], c.w_rpy[2], c.w_ang_mom[0], c.w_ang_mom[1],
-                        c.w_ang_mom[2], c.w_com_pos_err[0], c.w_com_pos_err[1], c.w_com_pos_err[2],
-                        c.w_rpy_err[0], c.w_rpy_err[1], c.w_rpy_err[2], c.w_throttle, c.w_initial_throttle,
-                        c.w_reg_joint_pos};
-    for (double v : q)
-        if (!(v >= 0.0)) return false;
-    for (int i = 0; i < NJ; ++i)
-        if (!(c.w_delta_joint[i] + c.w_reg_joint_pos > 0.0)) return false;  // condensed Hessian must stay PD
-    if (!(c.w_initial_throttle > 0.0)) return false;
-    if (!(c.throttle_max > c.throttle_min)) return false;
-    return true;
+    return tunables_invalid(c) == nullptr;
+}
+
+thread_local char g_arg_msg[160] = "";   // the last refusal of vsmpc_pack_tunables on this thread (vsmpc_strerror)
+
+// the name of the first structural field in which `c` differs from the handle's configuration, or nullptr
+const char* structural_mismatch(const vsmpc_config& c, const vsmpc_config& h) {
+    if (c.n_iter != h.n_iter) return "n_iter";
+    if (c.n_iter_small != h.n_iter_small) return "n_iter_small";
+    if (c.control_horizon != h.control_horizon) return "control_horizon";
+    if ((c.use_jet_dynamic != 0) != (h.use_jet_dynamic != 0)) return "use_jet_dynamic";
+    if (c.period_mpc != h.period_mpc) return "period_mpc";
+    if (c.period_small != h.period_small) return "period_small";
+    if (c.period_large != h.period_large) return "period_large";
+    return nullptr;
 }
 
 }  // namespace
+
+int vsmpc::invalid_arg() {
+    g_arg_msg[0] = '\0';
+    return VSMPC_ERR_INVALID_ARG;
+}
 
 extern "C" {
 
@@ -228,11 +283,11 @@ int vsmpc_create(const vsmpc_config* cfg, int device, int max_batch, vsmpc_handl
 }
 
 int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned flags, vsmpc_handle** out) {
-    if (cfg == nullptr || out == nullptr || max_batch <= 0) return VSMPC_ERR_INVALID_ARG;
+    if (cfg == nullptr || out == nullptr || max_batch <= 0) return invalid_arg();
     *out = nullptr;
     const unsigned kernel_flags = VSMPC_CREATE_RUNTIME_FALLBACK | VSMPC_CREATE_RUNTIME_ONLY;
-    if ((flags & ~(kernel_flags | VSMPC_CREATE_SENSITIVITY)) != 0u) return VSMPC_ERR_INVALID_ARG;
-    if (!config_valid(*cfg)) return VSMPC_ERR_INVALID_ARG;
+    if ((flags & ~(kernel_flags | VSMPC_CREATE_SENSITIVITY | VSMPC_CREATE_TUNABLES)) != 0u) return invalid_arg();
+    if (!config_valid(*cfg)) return invalid_arg();
     const int variant = (flags & VSMPC_CREATE_RUNTIME_ONLY)
                             ? int(VARIANT_NONE)
                             : select_variant(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon);
@@ -245,7 +300,7 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     if (sens && runtime_lds_bytes(rts) > RT_MAX_LDS) return VSMPC_ERR_UNSUPPORTED_CONFIG;     // (not for a valid config)
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return VSMPC_ERR_INVALID_ARG;
+    if (device < 0 || device >= ndev) return invalid_arg();
     ON_DEVICE(device);
 
     vsmpc_handle* h = new (std::nothrow) vsmpc_handle();
@@ -258,6 +313,7 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     h->rt = rt;
     h->sens = sens ? 1 : 0;
     h->rts = rts;
+    h->tunables = (flags & VSMPC_CREATE_TUNABLES) != 0u ? 1 : 0;
     h->form = runtime ? 0 : initial_kernel_form();
     for (int i = 0; i < VSMPC_N_JOINTS; ++i) h->kin.sel[i] = 3 + i;   // the shipped robot: joints 3..10
     h->kin.constant_lambda = 0;
@@ -291,13 +347,15 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
         if (e == hipSuccess) e = hipMalloc(&h->d_sact, C * rts.nv * sizeof(int));
         if (e == hipSuccess) e = hipMalloc(&h->d_sflags, C * sizeof(int));
     }
+    if (e == hipSuccess && h->tunables) e = hipMalloc(&h->d_tun, B * VSMPC_TUNE_SIZE * sizeof(double));
     for (int i = 0; i < PIPE_STREAMS && e == hipSuccess; ++i) {
         e = hipStreamCreateWithFlags(&h->pipe[i], hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&h->pipe_done[i], hipEventDisableTiming);
     }
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->pipe_start, hipEventDisableTiming);
     if (e == hipSuccess) {
-        const size_t zc = size_t(ZC_MAX) * (h->n_in + h->n_var + VSMPC_FM_SIZE + 1 + VSMPC_KIN_SIZE) * sizeof(double);  // ints share one double
+        const size_t zc = size_t(ZC_MAX) * (h->n_in + h->n_var + VSMPC_FM_SIZE + 1 + VSMPC_KIN_SIZE + VSMPC_TUNE_SIZE) *
+                          sizeof(double);  // ints share one double
         e = hipHostMalloc(reinterpret_cast<void**>(&h->h_stage), zc, hipHostMallocMapped);
         if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_stage), h->h_stage, 0);
     }
@@ -330,6 +388,7 @@ void vsmpc_destroy(vsmpc_handle* h) {
     if (h->d_sdfm) (void)hipFree(h->d_sdfm);
     if (h->d_sact) (void)hipFree(h->d_sact);
     if (h->d_sflags) (void)hipFree(h->d_sflags);
+    if (h->d_tun) (void)hipFree(h->d_tun);
     for (int i = 0; i < PIPE_STREAMS; ++i) {
         if (h->pipe[i]) (void)hipStreamDestroy(h->pipe[i]);
         if (h->pipe_done[i]) (void)hipEventDestroy(h->pipe_done[i]);
@@ -341,18 +400,18 @@ void vsmpc_destroy(vsmpc_handle* h) {
     delete h;
 }
 
-int vsmpc_num_variables(const vsmpc_handle* h) { return h ? h->n_var : VSMPC_ERR_INVALID_ARG; }
-int vsmpc_num_constraints(const vsmpc_handle* h) { return h ? h->n_con : VSMPC_ERR_INVALID_ARG; }
-int vsmpc_input_doubles(const vsmpc_handle* h) { return h ? h->n_in : VSMPC_ERR_INVALID_ARG; }
-int vsmpc_max_batch(const vsmpc_handle* h) { return h ? h->max_batch : VSMPC_ERR_INVALID_ARG; }
-int vsmpc_condensed_dim(const vsmpc_handle* h) { return h ? h->n_p : VSMPC_ERR_INVALID_ARG; }
+int vsmpc_num_variables(const vsmpc_handle* h) { return h ? h->n_var : invalid_arg(); }
+int vsmpc_num_constraints(const vsmpc_handle* h) { return h ? h->n_con : invalid_arg(); }
+int vsmpc_input_doubles(const vsmpc_handle* h) { return h ? h->n_in : invalid_arg(); }
+int vsmpc_max_batch(const vsmpc_handle* h) { return h ? h->max_batch : invalid_arg(); }
+int vsmpc_condensed_dim(const vsmpc_handle* h) { return h ? h->n_p : invalid_arg(); }
 const char* vsmpc_kernel_name(const vsmpc_handle* h) {
     return h ? (h->runtime ? runtime_kernel_name() : variant_kernel_name(h->variant)) : "none";
 }
 
 int vsmpc_solve_batch_device(vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_first_move,
                              int* d_status, int* d_iters, void* stream) {
-    if (h == nullptr || d_in == nullptr || d_status == nullptr || batch < 0) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr || d_in == nullptr || d_status == nullptr || batch < 0) return invalid_arg();
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (batch == 0) return VSMPC_OK;
     ON_DEVICE(h->device);   // an enqueue-only entry must not change the caller's current device either
@@ -360,11 +419,13 @@ int vsmpc_solve_batch_device(vsmpc_handle* h, const double* d_in, int batch, dou
     return VSMPC_OK;
 }
 
-int vsmpc_solve_batch(vsmpc_handle* h, const double* in, int batch, double* x, double* first_move, int* status,
-                      int* iters, void* stream) {
-    if (h == nullptr || in == nullptr || status == nullptr || batch < 0) return VSMPC_ERR_INVALID_ARG;
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
+}  // extern "C"
+
+namespace {
+
+// vsmpc_solve_batch (tun == nullptr) and vsmpc_solve_batch_tuned (tun: host rows, one per instance, staged like the records)
+int solve_batch_host(vsmpc_handle* h, const double* in, const double* tun, int batch, double* x, double* first_move,
+                     int* status, int* iters, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     ON_DEVICE(h->device);
     const size_t B = size_t(batch);
@@ -372,7 +433,8 @@ int vsmpc_solve_batch(vsmpc_handle* h, const double* in, int batch, double* x, d
         // zero-copy path: the kernel reads the records from and writes the results to pinned host memory
         const Stage hv = stage_view(h, h->h_stage), dv = stage_view(h, h->d_stage);   // the same carve-up on both views
         memcpy(hv.in, in, B * h->n_in * sizeof(double));
-        HIP_TRY(solve_launch(h, dv.in, batch, dv.x, dv.fm, dv.st, dv.it, 0, s));
+        if (tun) memcpy(hv.tun, tun, B * VSMPC_TUNE_SIZE * sizeof(double));
+        HIP_TRY(solve_launch(h, dv.in, batch, dv.x, dv.fm, dv.st, dv.it, 0, s, tun ? dv.tun : nullptr));
         HIP_TRY(hipStreamSynchronize(s));
         if (x) memcpy(x, hv.x, B * h->n_var * sizeof(double));
         if (first_move) memcpy(first_move, hv.fm, B * VSMPC_FM_SIZE * sizeof(double));
@@ -410,13 +472,16 @@ int vsmpc_solve_batch(vsmpc_handle* h, const double* in, int batch, double* x, d
         const size_t o = size_t(first), N = size_t(n);
         hipStream_t ps = h->pipe[k % nstreams];
         if (!ok(hipMemcpyAsync(h->d_in + o * h->n_in, in + o * h->n_in, N * h->n_in * sizeof(double), hipMemcpyHostToDevice, ps))) break;
+        const double* dt = tun ? h->d_tun + o * VSMPC_TUNE_SIZE : nullptr;
+        if (tun && !ok(hipMemcpyAsync(h->d_tun + o * VSMPC_TUNE_SIZE, tun + o * VSMPC_TUNE_SIZE,
+                                      N * VSMPC_TUNE_SIZE * sizeof(double), hipMemcpyHostToDevice, ps))) break;
         if (direct) {
             ok(solve_launch(h, h->d_in + o * h->n_in, n, x ? zx + o * h->n_var : nullptr,
-                            first_move ? zfm + o * VSMPC_FM_SIZE : nullptr, zst + o, iters ? zit + o : nullptr, o, ps));
+                            first_move ? zfm + o * VSMPC_FM_SIZE : nullptr, zst + o, iters ? zit + o : nullptr, o, ps, dt));
             continue;
         }
         if (!ok(solve_launch(h, h->d_in + o * h->n_in, n, h->d_x + o * h->n_var, h->d_fm + o * VSMPC_FM_SIZE, h->d_status + o,
-                             h->d_iters + o, o, ps))) break;
+                             h->d_iters + o, o, ps, dt))) break;
         if (x) ok(hipMemcpyAsync(x + o * h->n_var, h->d_x + o * h->n_var, N * h->n_var * sizeof(double), hipMemcpyDeviceToHost, ps));
         if (first_move)
             ok(hipMemcpyAsync(first_move + o * VSMPC_FM_SIZE, h->d_fm + o * VSMPC_FM_SIZE,
@@ -436,12 +501,69 @@ int vsmpc_solve_batch(vsmpc_handle* h, const double* in, int batch, double* x, d
     return VSMPC_OK;
 }
 
-int vsmpc_num_throttle_unknowns(const vsmpc_handle* h) { return h ? h->rt.nv : VSMPC_ERR_INVALID_ARG; }
+}  // namespace
+
+extern "C" {
+
+int vsmpc_solve_batch(vsmpc_handle* h, const double* in, int batch, double* x, double* first_move, int* status,
+                      int* iters, void* stream) {
+    if (h == nullptr || in == nullptr || status == nullptr || batch < 0) return invalid_arg();
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    if (batch == 0) return VSMPC_OK;
+    return solve_batch_host(h, in, nullptr, batch, x, first_move, status, iters, stream);
+}
+
+int vsmpc_pack_tunables(const vsmpc_handle* h, const vsmpc_config* cfgs, int n, double* out) {
+    if (h == nullptr || n < 0 || (n > 0 && (cfgs == nullptr || out == nullptr))) {
+        snprintf(g_arg_msg, sizeof(g_arg_msg), "invalid argument (vsmpc_pack_tunables: null pointer or negative count)");
+        return VSMPC_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < n; ++i) {
+        const char* field = structural_mismatch(cfgs[i], h->cfg);
+        if (field != nullptr) {
+            snprintf(g_arg_msg, sizeof(g_arg_msg),
+                     "invalid argument (vsmpc_pack_tunables: configuration %d differs from the handle in the structural field %s)",
+                     i, field);
+            return VSMPC_ERR_INVALID_ARG;
+        }
+        field = tunables_invalid(cfgs[i]);
+        if (field != nullptr) {
+            snprintf(g_arg_msg, sizeof(g_arg_msg), "invalid argument (vsmpc_pack_tunables: configuration %d has an invalid %s)", i,
+                     field);
+            return VSMPC_ERR_INVALID_ARG;
+        }
+    }
+    for (int i = 0; i < n; ++i) fill_tunables(cfgs[i], out + size_t(i) * VSMPC_TUNE_SIZE);
+    g_arg_msg[0] = '\0';
+    return VSMPC_OK;
+}
+
+int vsmpc_solve_batch_tuned_device(vsmpc_handle* h, const double* d_in, const double* d_tunables, int batch, double* d_x,
+                                   double* d_first_move, int* d_status, int* d_iters, void* stream) {
+    if (h == nullptr || d_in == nullptr || d_tunables == nullptr || d_status == nullptr || batch < 0) return invalid_arg();
+    if ((reinterpret_cast<size_t>(d_tunables) & 15) != 0) return invalid_arg();   // the kernels load 16 bytes per lane
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    if (batch == 0) return VSMPC_OK;
+    ON_DEVICE(h->device);
+    HIP_TRY(solve_launch(h, d_in, batch, d_x, d_first_move, d_status, d_iters, 0, static_cast<hipStream_t>(stream), d_tunables));
+    return VSMPC_OK;
+}
+
+int vsmpc_solve_batch_tuned(vsmpc_handle* h, const double* in, const double* tunables, int batch, double* x,
+                            double* first_move, int* status, int* iters, void* stream) {
+    if (h == nullptr || in == nullptr || tunables == nullptr || status == nullptr || batch < 0) return invalid_arg();
+    if (!h->tunables) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    if (batch == 0) return VSMPC_OK;
+    return solve_batch_host(h, in, tunables, batch, x, first_move, status, iters, stream);
+}
+
+int vsmpc_num_throttle_unknowns(const vsmpc_handle* h) { return h ? h->rt.nv : invalid_arg(); }
 
 int vsmpc_sensitivity_batch_device(vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_first_move,
                                    int* d_status, int* d_iters, double* d_dx_dx0, double* d_dfm_dx0, int* d_active,
                                    int* d_sens_flags, void* stream) {
-    if (h == nullptr || d_in == nullptr || d_status == nullptr || batch < 0) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr || d_in == nullptr || d_status == nullptr || batch < 0) return invalid_arg();
     if (!h->sens) return VSMPC_ERR_UNSUPPORTED_CONFIG;
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (batch == 0) return VSMPC_OK;
@@ -453,7 +575,7 @@ int vsmpc_sensitivity_batch_device(vsmpc_handle* h, const double* d_in, int batc
 
 int vsmpc_sensitivity_batch(vsmpc_handle* h, const double* in, int batch, double* x, double* first_move, int* status,
                             int* iters, double* dx_dx0, double* dfm_dx0, int* active, int* sens_flags, void* stream) {
-    if (h == nullptr || in == nullptr || status == nullptr || batch < 0) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr || in == nullptr || status == nullptr || batch < 0) return invalid_arg();
     if (!h->sens) return VSMPC_ERR_UNSUPPORTED_CONFIG;
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (batch == 0) return VSMPC_OK;
@@ -493,7 +615,7 @@ int vsmpc_sensitivity_batch(vsmpc_handle* h, const double* in, int batch, double
 
 int vsmpc_linearize_batch(vsmpc_handle* h, const double* in, int batch, double* A, double* Bj, double* Bt,
                           double* c, double* dt) {
-    if (h == nullptr || in == nullptr || batch < 0) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr || in == nullptr || batch < 0) return invalid_arg();
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (dt) fill_dt(h->cfg, dt);
     if (batch == 0) return VSMPC_OK;
@@ -520,7 +642,7 @@ int vsmpc_assemble_dense(vsmpc_handle* h, const double* in_one, double* H, doubl
                          double* hi) {
     if (h == nullptr || in_one == nullptr || H == nullptr || g == nullptr || Ac == nullptr || lo == nullptr ||
         hi == nullptr)
-        return VSMPC_ERR_INVALID_ARG;
+        return invalid_arg();
     std::vector<double> A(NX * NX), Bj(NX * NJ), Bt(NX * NTH), c(NX), dt(MAX_STAGES);
     int rc = vsmpc_linearize_batch(h, in_one, 1, A.data(), Bj.data(), Bt.data(), c.data(), dt.data());
     if (rc != VSMPC_OK) return rc;
@@ -607,7 +729,7 @@ int vsmpc_assemble_dense(vsmpc_handle* h, const double* in_one, double* H, doubl
 }
 
 int vsmpc_debug_condensed(vsmpc_handle* h, const double* in_one, double* M, double* Lfac) {
-    if (h == nullptr || in_one == nullptr) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr || in_one == nullptr) return invalid_arg();
     if (h->runtime) return VSMPC_ERR_UNSUPPORTED_CONFIG;
     ON_DEVICE(h->device);
     const size_t np2 = size_t(h->n_p) * h->n_p;
@@ -622,7 +744,7 @@ int vsmpc_debug_condensed(vsmpc_handle* h, const double* in_one, double* M, doub
 }
 
 int vsmpc_kinematics_batch(vsmpc_handle* h, const double* kin, int batch, double* out, double* records) {
-    if (h == nullptr || kin == nullptr || out == nullptr || batch < 0) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr || kin == nullptr || out == nullptr || batch < 0) return invalid_arg();
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (batch == 0) return VSMPC_OK;
     ON_DEVICE(h->device);
@@ -645,7 +767,7 @@ int vsmpc_kinematics_batch(vsmpc_handle* h, const double* kin, int batch, double
 // One tick of the reference's drop-in surface in ONE submission: kinematics terms -> record -> solve, one synchronisation.
 int vsmpc_tick(vsmpc_handle* h, const double* kin, double* in, int batch, double* x, double* first_move, int* status,
                int* iters, void* stream) {
-    if (h == nullptr || kin == nullptr || in == nullptr || status == nullptr || batch < 0) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr || kin == nullptr || in == nullptr || status == nullptr || batch < 0) return invalid_arg();
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (batch == 0) return VSMPC_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -683,19 +805,19 @@ int vsmpc_tick(vsmpc_handle* h, const double* kin, double* in, int batch, double
 
 int vsmpc_provider_batch(vsmpc_handle* h, const vsmpc_tree* tree, const double* state, int batch, double* kin,
                          double* robot, double* records) {
-    if (h == nullptr || tree == nullptr || state == nullptr || batch < 0) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr || tree == nullptr || state == nullptr || batch < 0) return invalid_arg();
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (batch == 0) return VSMPC_OK;
     // the provider delivers the CURRENT frame Jacobians; jointsLambdaOption "constant" re-reads those slots as the
     // configure-time relative Jacobians and thrusts (vsmpc_set_kinematics_options): the combination has no meaning
     if (records != nullptr && h->kin.constant_lambda) return VSMPC_ERR_UNSUPPORTED_CONFIG;
-    if (tree->parent[0] != -1) return VSMPC_ERR_INVALID_ARG;
+    if (tree->parent[0] != -1) return invalid_arg();
     for (int b = 1; b < VSMPC_TREE_NB; ++b)
-        if (tree->parent[b] < 0 || tree->parent[b] >= b) return VSMPC_ERR_INVALID_ARG;      // parents precede children
+        if (tree->parent[b] < 0 || tree->parent[b] >= b) return invalid_arg();      // parents precede children
     for (int j = 0; j < VSMPC_TREE_NJ; ++j)
-        if (tree->robot_joint[j] < 0 || tree->robot_joint[j] >= VSMPC_KIN_NJ) return VSMPC_ERR_INVALID_ARG;
+        if (tree->robot_joint[j] < 0 || tree->robot_joint[j] >= VSMPC_KIN_NJ) return invalid_arg();
     for (int i = 0; i < VSMPC_N_THRUSTS; ++i)
-        if (tree->jet_body[i] < 0 || tree->jet_body[i] >= VSMPC_TREE_NB) return VSMPC_ERR_INVALID_ARG;
+        if (tree->jet_body[i] < 0 || tree->jet_body[i] >= VSMPC_TREE_NB) return invalid_arg();
     ON_DEVICE(h->device);
     // scratch: the state records go through d_lin (1014 doubles per instance), the Robot-level outputs through d_x
     // (n_var >= 67 doubles per instance), the kinematics record through d_kin
@@ -717,10 +839,10 @@ int vsmpc_provider_batch(vsmpc_handle* h, const vsmpc_tree* tree, const double* 
 }
 
 int vsmpc_set_kinematics_options(vsmpc_handle* h, const int* joint_selector, int constant_lambda) {
-    if (h == nullptr) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr) return invalid_arg();
     if (joint_selector != nullptr) {
         for (int i = 0; i < VSMPC_N_JOINTS; ++i)
-            if (joint_selector[i] < 0 || joint_selector[i] >= VSMPC_KIN_NJ) return VSMPC_ERR_INVALID_ARG;
+            if (joint_selector[i] < 0 || joint_selector[i] >= VSMPC_KIN_NJ) return invalid_arg();
         for (int i = 0; i < VSMPC_N_JOINTS; ++i) h->kin.sel[i] = joint_selector[i];
     }
     h->kin.constant_lambda = constant_lambda ? 1 : 0;
@@ -728,7 +850,7 @@ int vsmpc_set_kinematics_options(vsmpc_handle* h, const int* joint_selector, int
 }
 
 int vsmpc_debug_phase_cycles(vsmpc_handle* h, const double* in, int batch, unsigned long long* stamps16) {
-    if (h == nullptr || in == nullptr || stamps16 == nullptr || batch <= 0) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr || in == nullptr || stamps16 == nullptr || batch <= 0) return invalid_arg();
     if (h->runtime) return VSMPC_ERR_UNSUPPORTED_CONFIG;
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     ON_DEVICE(h->device);
@@ -744,13 +866,13 @@ int vsmpc_debug_phase_cycles(vsmpc_handle* h, const double* in, int batch, unsig
 }
 
 int vsmpc_timing_begin(vsmpc_handle* h, void* stream) {
-    if (h == nullptr) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr) return invalid_arg();
     HIP_TRY(hipEventRecord(h->ev0, static_cast<hipStream_t>(stream)));
     return VSMPC_OK;
 }
 
 int vsmpc_timing_end(vsmpc_handle* h, void* stream, int launches, float* ms_per_launch) {
-    if (h == nullptr || ms_per_launch == nullptr || launches <= 0) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr || ms_per_launch == nullptr || launches <= 0) return invalid_arg();
     HIP_TRY(hipEventRecord(h->ev1, static_cast<hipStream_t>(stream)));
     HIP_TRY(hipEventSynchronize(h->ev1));
     float ms = 0.f;
@@ -765,7 +887,7 @@ int vsmpc_rollout_create(vsmpc_handle* h, int batch, const double* traj_pos, con
                          const double* traj_alpha, int n_alpha, double alpha_dt, vsmpc_rollout** out) {
     if (h == nullptr || out == nullptr || traj_pos == nullptr || traj_vel == nullptr || traj_alpha == nullptr ||
         batch <= 0 || n_traj <= 0 || n_alpha <= 0 || !(alpha_dt > 0.0))
-        return VSMPC_ERR_INVALID_ARG;
+        return invalid_arg();
     *out = nullptr;
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     ON_DEVICE(h->device);
@@ -785,7 +907,7 @@ int vsmpc_rollout_create(vsmpc_handle* h, int batch, const double* traj_pos, con
     {   // TrajectoryManager::configure(.., 1 / periodMPC): des_fps truncated to int (systemDynamicsVSMPC.cpp:272), integer
         // up-sampling factor against the track's own rate
         const int des_fps = int(1.0 / h->cfg.period_mpc + 1e-9), fps = int(std::lround(1.0 / alpha_dt));
-        if (fps <= 0 || des_fps < fps || des_fps % fps != 0) { delete r; return VSMPC_ERR_INVALID_ARG; }
+        if (fps <= 0 || des_fps < fps || des_fps % fps != 0) { delete r; return invalid_arg(); }
         r->rd.alpha_up = des_fps / fps;
     }
     r->substeps = std::min(16, std::max(1, int(std::lround(h->cfg.period_mpc / 1e-3))));  // 1 kHz plant, as the MuJoCo harness
@@ -831,13 +953,14 @@ void vsmpc_rollout_destroy(vsmpc_rollout* r) {
     if (r->d_tstate) (void)hipFree(r->d_tstate);
     if (r->d_rs) (void)hipFree(r->d_rs);
     if (r->d_ro) (void)hipFree(r->d_ro);
+    if (r->d_tun) (void)hipFree(r->d_tun);
     if (r->gexec) (void)hipGraphExecDestroy(r->gexec);
     if (r->own_stream) (void)hipStreamDestroy(r->own_stream);
     delete r;
 }
 
 int vsmpc_rollout_reset(vsmpc_rollout* r, const double* state, const double* params) {
-    if (r == nullptr || state == nullptr || params == nullptr) return VSMPC_ERR_INVALID_ARG;
+    if (r == nullptr || state == nullptr || params == nullptr) return invalid_arg();
     ON_DEVICE(r->h->device);
     const size_t B = size_t(r->batch);
     HIP_TRY(hipMemcpy(r->d_state, state, B * VSMPC_PLANT_STATE * sizeof(double), hipMemcpyHostToDevice));
@@ -856,7 +979,7 @@ int vsmpc_rollout_reset(vsmpc_rollout* r, const double* state, const double* par
 }
 
 int vsmpc_rollout_set_attitude_tracks(vsmpc_rollout* r, const double* traj_rpy, const double* traj_rpy_dot) {
-    if (r == nullptr) return VSMPC_ERR_INVALID_ARG;
+    if (r == nullptr) return invalid_arg();
     ON_DEVICE(r->h->device);
     const size_t bytes = size_t(r->rd.n_traj) * 3 * sizeof(double);
     // whatever happens below, the captured ticks and the record of the next tick refer to the old tracks: drop them first
@@ -885,7 +1008,7 @@ int vsmpc_rollout_set_attitude_tracks(vsmpc_rollout* r, const double* traj_rpy, 
 }
 
 int vsmpc_rollout_set_tree(vsmpc_rollout* r, const vsmpc_tree* tree) {
-    if (r == nullptr) return VSMPC_ERR_INVALID_ARG;
+    if (r == nullptr) return invalid_arg();
     ON_DEVICE(r->h->device);
     if (r->gexec) { (void)hipGraphExecDestroy(r->gexec); r->gexec = nullptr; }   // the captured ticks have other launches
     r->graph_state = 0;
@@ -893,13 +1016,13 @@ int vsmpc_rollout_set_tree(vsmpc_rollout* r, const vsmpc_tree* tree) {
     r->use_tree = 0;
     r->rd.tree = 0;
     if (tree == nullptr) return VSMPC_OK;
-    if (tree->parent[0] != -1) return VSMPC_ERR_INVALID_ARG;
+    if (tree->parent[0] != -1) return invalid_arg();
     for (int b = 1; b < VSMPC_TREE_NB; ++b)
-        if (tree->parent[b] < 0 || tree->parent[b] >= b) return VSMPC_ERR_INVALID_ARG;
+        if (tree->parent[b] < 0 || tree->parent[b] >= b) return invalid_arg();
     for (int j = 0; j < VSMPC_TREE_NJ; ++j)
-        if (tree->robot_joint[j] < 0 || tree->robot_joint[j] >= VSMPC_KIN_NJ) return VSMPC_ERR_INVALID_ARG;
+        if (tree->robot_joint[j] < 0 || tree->robot_joint[j] >= VSMPC_KIN_NJ) return invalid_arg();
     for (int i = 0; i < VSMPC_N_THRUSTS; ++i)
-        if (tree->jet_body[i] < 0 || tree->jet_body[i] >= VSMPC_TREE_NB) return VSMPC_ERR_INVALID_ARG;
+        if (tree->jet_body[i] < 0 || tree->jet_body[i] >= VSMPC_TREE_NB) return invalid_arg();
     const size_t B = size_t(r->batch);
     if (r->d_rs == nullptr) HIP_TRY(hipMalloc(&r->d_rs, B * VSMPC_RS_SIZE * sizeof(double)));
     if (r->d_ro == nullptr) HIP_TRY(hipMalloc(&r->d_ro, B * VSMPC_RO_SIZE * sizeof(double)));
@@ -912,16 +1035,34 @@ int vsmpc_rollout_set_tree(vsmpc_rollout* r, const vsmpc_tree* tree) {
     return VSMPC_OK;
 }
 
+int vsmpc_rollout_set_tunables(vsmpc_rollout* r, const double* tunables) {
+    if (r == nullptr) return invalid_arg();
+    ON_DEVICE(r->h->device);
+    if (tunables != nullptr) {   // first, what can fail: a refused call leaves the rollout as it was
+        const size_t bytes = size_t(r->batch) * VSMPC_TUNE_SIZE * sizeof(double);
+        if (r->d_tun == nullptr) {
+            const hipError_t e = hipMalloc(&r->d_tun, bytes);   // on first use, like the buffers of set_tree
+            if (e != hipSuccess) { r->d_tun = nullptr; return hip_fail(e, "hipMalloc(rollout tunables)"); }
+        }
+        HIP_TRY(hipMemcpy(r->d_tun, tunables, bytes, hipMemcpyHostToDevice));
+    }
+    if (r->gexec) { (void)hipGraphExecDestroy(r->gexec); r->gexec = nullptr; }   // the captured ticks hold the other solve launch
+    r->graph_state = 0;
+    r->valid = 0;                                                                // vsmpc_rollout_reset before the next run
+    r->use_tun = tunables != nullptr;
+    return VSMPC_OK;
+}
+
 // include/vsmpc_jet.h
 int vsmpc_rollout_set_jet_plant(vsmpc_rollout* r, vsmpc_jet* j, const double* Q, const double* R) {
-    if (r == nullptr || (j != nullptr && (Q == nullptr || R == nullptr))) return VSMPC_ERR_INVALID_ARG;
+    if (r == nullptr || (j != nullptr && (Q == nullptr || R == nullptr))) return invalid_arg();
     RolloutDev rd = r->rd;
     rd.jet_nn = 0;
     rd.jet_w = nullptr;
     if (j != nullptr) {
         int dev = -1;
         jet_plant_view(j, &rd.jet_w, &rd.jet_hidden, rd.jet_norm, &dev);
-        if (dev != r->h->device) return VSMPC_ERR_INVALID_ARG;
+        if (dev != r->h->device) return invalid_arg();
         rd.jet_nn = 1;
         for (int k = 0; k < 4; ++k) { rd.ekf_q[k] = Q[k]; rd.ekf_r[k] = R[k]; }
     }
@@ -944,7 +1085,8 @@ constexpr int GRAPH_TICKS = 25;  // ticks per captured graph (50 kernel nodes)
 // synchronisation the loop needs
 hipError_t enqueue_tick(vsmpc_rollout* r, hipStream_t s) {
     vsmpc_handle* h = r->h;
-    hipError_t e = solve_launch(h, r->d_rec, r->batch, h->d_x, h->d_fm, h->d_status, h->d_iters, 0, s);
+    hipError_t e = solve_launch(h, r->d_rec, r->batch, h->d_x, h->d_fm, h->d_status, h->d_iters, 0, s,
+                                r->use_tun ? r->d_tun : nullptr);
     if (e == hipSuccess && r->use_tree) e = enqueue_tree(r, h->d_fm, h->d_status, s);   // A_mom, I_B of the joints after the move
     if (e == hipSuccess)
         e = launch_advance(r->rd, r->batch, r->d_state, r->d_params, r->d_tick, h->d_fm, h->d_status, h->d_iters,
@@ -976,8 +1118,8 @@ void build_tick_graph(vsmpc_rollout* r, hipStream_t s) {
 extern "C" {
 
 int vsmpc_rollout_run(vsmpc_rollout* r, int ticks, double* log, void* stream) {
-    if (r == nullptr || ticks < 0) return VSMPC_ERR_INVALID_ARG;
-    if (!r->valid) return VSMPC_ERR_INVALID_ARG;   // never reset, or a previous run failed half-way: reset() first
+    if (r == nullptr || ticks < 0) return invalid_arg();
+    if (!r->valid) return invalid_arg();   // never reset, or a previous run failed half-way: reset() first
     if (ticks == 0) return VSMPC_OK;
     vsmpc_handle* h = r->h;
     ON_DEVICE(h->device);
@@ -1012,21 +1154,21 @@ int vsmpc_rollout_run(vsmpc_rollout* r, int ticks, double* log, void* stream) {
 }
 
 int vsmpc_rollout_get_state(vsmpc_rollout* r, double* state) {
-    if (r == nullptr || state == nullptr) return VSMPC_ERR_INVALID_ARG;
+    if (r == nullptr || state == nullptr) return invalid_arg();
     ON_DEVICE(r->h->device);
     HIP_TRY(hipMemcpy(state, r->d_state, size_t(r->batch) * VSMPC_PLANT_STATE * sizeof(double), hipMemcpyDeviceToHost));
     return VSMPC_OK;
 }
 
 int vsmpc_rollout_get_records(vsmpc_rollout* r, double* records) {
-    if (r == nullptr || records == nullptr) return VSMPC_ERR_INVALID_ARG;
+    if (r == nullptr || records == nullptr) return invalid_arg();
     ON_DEVICE(r->h->device);
     HIP_TRY(hipMemcpy(records, r->d_rec, size_t(r->batch) * r->h->n_in * sizeof(double), hipMemcpyDeviceToHost));
     return VSMPC_OK;
 }
 
 int vsmpc_set_kernel_form(vsmpc_handle* h, int form) {
-    if (h == nullptr || form < 0 || form > 2) return VSMPC_ERR_INVALID_ARG;
+    if (h == nullptr || form < 0 || form > 2) return invalid_arg();
     if (h->runtime && form != 0) return VSMPC_ERR_UNSUPPORTED_CONFIG;   // the runtime kernel has one form
     if (form == 1 && !variant_has_structured(h->variant)) return VSMPC_ERR_UNSUPPORTED_CONFIG;
     const int prev = h->form;
@@ -1047,7 +1189,7 @@ void vsmpc_free_host(void* p) {
 const char* vsmpc_strerror(int code) {
     switch (code) {
         case VSMPC_OK: return "ok";
-        case VSMPC_ERR_INVALID_ARG: return "invalid argument";
+        case VSMPC_ERR_INVALID_ARG: return g_arg_msg[0] ? g_arg_msg : "invalid argument";
         case VSMPC_ERR_UNSUPPORTED_CONFIG: return "unsupported MPC configuration (no kernel instantiation)";
         case VSMPC_ERR_BATCH_TOO_LARGE: return "batch exceeds max_batch of the handle";
         case VSMPC_ERR_HIP: return g_hip_msg[0] ? g_hip_msg : "HIP runtime error";

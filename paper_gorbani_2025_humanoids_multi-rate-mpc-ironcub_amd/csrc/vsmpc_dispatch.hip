@@ -185,6 +185,26 @@ hipError_t launch_solve(int variant, int form, const DevCfg& cfg, const double* 
     return hipErrorInvalidValue;
 }
 
+template <int N, int NS, int HC>
+static hipError_t launch_solve_tuned_pick(int form, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
+                                          double* d_x, double* d_fm, int* d_status, int* d_iters, hipStream_t stream) {
+    if constexpr (Dims<N, NS, HC>::STRUCT_P1) {
+        if (form != 2)
+            return launch_solve_tuned_dims<N, NS, HC, 1>(cfg, d_in, d_tun, batch, d_x, d_fm, d_status, d_iters, stream);
+    }
+    return launch_solve_tuned_dims<N, NS, HC, 0>(cfg, d_in, d_tun, batch, d_x, d_fm, d_status, d_iters, stream);
+}
+
+hipError_t launch_solve_tuned(int variant, int form, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
+                              double* d_x, double* d_fm, int* d_status, int* d_iters, hipStream_t stream) {
+    int id = 0;
+#define X(N, NS, HC) \
+    if (variant == ++id) return launch_solve_tuned_pick<N, NS, HC>(form, cfg, d_in, d_tun, batch, d_x, d_fm, d_status, d_iters, stream);
+#include "vsmpc_horizons.def"
+#undef X
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_linearize(int variant, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,
                             double* Bt, double* c, hipStream_t stream) {
     int id = 0;

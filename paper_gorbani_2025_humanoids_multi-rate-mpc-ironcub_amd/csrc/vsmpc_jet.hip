@@ -190,11 +190,11 @@ int vsmpc_jet_create(const float* w_ih, const float* w_hh, const float* b_ih, co
                      const float* fc_b, const double* norm, int hidden, int device, int max_series, vsmpc_jet** out) {
     if (!w_ih || !w_hh || !b_ih || !b_hh || !fc_w || !fc_b || !norm || !out || hidden <= 0 || hidden > JET_HMAX ||
         max_series <= 0 || !(norm[1] > 0.0) || !(norm[3] > 0.0))
-        return VSMPC_ERR_INVALID_ARG;
+        return invalid_arg();
     *out = nullptr;
     int ndev = 0;
     JET_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return VSMPC_ERR_INVALID_ARG;
+    if (device < 0 || device >= ndev) return invalid_arg();
     vsmpc::DeviceScope _scope(device); JET_TRY(_scope.err);
     vsmpc_jet* j = new (std::nothrow) vsmpc_jet();
     if (!j) return VSMPC_ERR_ALLOC;
@@ -253,7 +253,7 @@ void vsmpc_jet_destroy(vsmpc_jet* j) {
 
 int vsmpc_jet_nn_step(vsmpc_jet* j, const float* thrust, const float* throttle, int n, float dt, float* T_next,
                       float* T_dot, float* h_out, float* c_out) {
-    if (!j || !thrust || !throttle || !T_next || !T_dot || n < 0) return VSMPC_ERR_INVALID_ARG;
+    if (!j || !thrust || !throttle || !T_next || !T_dot || n < 0) return invalid_arg();
     if (n > j->max_series) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (n == 0) return VSMPC_OK;
     vsmpc::DeviceScope _scope(j->device); JET_TRY(_scope.err);
@@ -273,7 +273,7 @@ int vsmpc_jet_nn_step(vsmpc_jet* j, const float* thrust, const float* throttle, 
 
 int vsmpc_jet_nn_sequence(vsmpc_jet* j, const float* x, int n, int L, float dt, float* T_next_norm, float* T_dot_norm,
                           float* h_n, float* c_n) {
-    if (!j || !x || !T_next_norm || !T_dot_norm || n < 0 || L <= 0) return VSMPC_ERR_INVALID_ARG;
+    if (!j || !x || !T_next_norm || !T_dot_norm || n < 0 || L <= 0) return invalid_arg();
     if (n > j->max_series) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (n == 0) return VSMPC_OK;
     vsmpc::DeviceScope _scope(j->device); JET_TRY(_scope.err);
@@ -299,7 +299,7 @@ int vsmpc_jet_nn_sequence(vsmpc_jet* j, const float* x, int n, int L, float dt, 
 
 int vsmpc_jet_ekf_update(vsmpc_jet* j, double* x, double* P, const double* u, const double* z, int n, double dt,
                          const double* Q, const double* R) {
-    if (!j || !x || !P || !u || !z || !Q || !R || n < 0 || !(dt > 0.0)) return VSMPC_ERR_INVALID_ARG;
+    if (!j || !x || !P || !u || !z || !Q || !R || n < 0 || !(dt > 0.0)) return invalid_arg();
     if (n > j->max_series) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (n == 0) return VSMPC_OK;
     vsmpc::DeviceScope _scope(j->device); JET_TRY(_scope.err);
@@ -322,7 +322,7 @@ int vsmpc_jet_plant_run_device(vsmpc_jet* j, float* d_T_nn, double* d_x_est, dou
                                double* d_log, void* stream) {
     if (!j || !d_T_nn || !d_x_est || !d_P || !d_throttle || !Q || !R || n < 0 || steps < 0 || !(dt > 0.0) ||
         (throttle_steps != 1 && throttle_steps != steps))
-        return VSMPC_ERR_INVALID_ARG;
+        return invalid_arg();
     if (n == 0 || steps == 0) return VSMPC_OK;
     vsmpc::DeviceScope _scope(j->device); JET_TRY(_scope.err);
     hipLaunchKernelGGL(jet_plant_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), j->d_w,
@@ -335,7 +335,7 @@ int vsmpc_jet_plant_run(vsmpc_jet* j, float* T_nn, double* x_est, double* P, con
                         int n, int steps, double dt, const double* Q, const double* R, double* log) {
     if (!j || !T_nn || !x_est || !P || !throttle || !Q || !R || n < 0 || steps < 0 ||
         (throttle_steps != 1 && throttle_steps != steps))
-        return VSMPC_ERR_INVALID_ARG;
+        return invalid_arg();
     if (n > j->max_series) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (n == 0 || steps == 0) return VSMPC_OK;
     vsmpc::DeviceScope _scope(j->device); JET_TRY(_scope.err);

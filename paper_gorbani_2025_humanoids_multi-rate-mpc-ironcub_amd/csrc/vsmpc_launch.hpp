@@ -23,6 +23,10 @@ struct DeviceScope {
     DeviceScope& operator=(const DeviceScope&) = delete;
 };
 
+// VSMPC_ERR_INVALID_ARG for every entry but vsmpc_pack_tunables (vsmpc_capi.hip): it also drops the text a refused pack
+// left on this thread, so that vsmpc_strerror describes the call that failed last
+int invalid_arg();
+
 enum Variant { VARIANT_NONE = 0 };  // 1.. = position in csrc/vsmpc_horizons.def
 
 int select_variant(int n_iter, int n_iter_small, int control_horizon);
@@ -47,6 +51,13 @@ template <int N, int NS, int HC, bool STAMPS>
 hipError_t launch_solve_dims(int form, const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm,
                              int* d_status, int* d_iters, double* dbgM, double* dbgL, unsigned long long* stamps,
                              hipStream_t stream);
+// the per-instance-tunables kind (solve_kernel_tuned; one unit of vsmpc_kernels.hip per horizon and condensing form, FORM
+// 1 = structured): d_tun [batch][VSMPC_TUNE_SIZE], rows of vsmpc_pack_tunables, 16-byte aligned
+hipError_t launch_solve_tuned(int variant, int form, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
+                              double* d_x, double* d_fm, int* d_status, int* d_iters, hipStream_t stream);
+template <int N, int NS, int HC, int FORM>
+hipError_t launch_solve_tuned_dims(const DevCfg& cfg, const double* d_in, const double* d_tun, int batch, double* d_x,
+                                   double* d_fm, int* d_status, int* d_iters, hipStream_t stream);
 template <int N, int NS, int HC>
 hipError_t launch_linearize_dims(const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj, double* Bt,
                                  double* c, hipStream_t stream);
@@ -71,6 +82,10 @@ hipError_t launch_solve_runtime(const RtDims& d, const DevCfg& cfg, const double
                                 double* d_fm, int* d_status, int* d_iters, hipStream_t stream);
 // sens_kernel_rt (vsmpc_sensitivity_batch): the solve outputs plus dx_dx0 [batch][nVar][26], dfm_dx0 [batch][24][26],
 // active [batch][NV] and the VSMPC_SENS_* flags [batch]; d from runtime_dims(.., true), d_ws as for the solve
+// solve_kernel_rt_tuned: the same body with every tunable read from the instance's row of d_tun
+hipError_t launch_solve_runtime_tuned(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
+                                      double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters,
+                                      hipStream_t stream);
 hipError_t launch_sensitivity_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws,
                                       double* d_x, double* d_fm, int* d_status, int* d_iters, double* d_dx, double* d_dfm,
                                       int* d_active, int* d_flags, hipStream_t stream);

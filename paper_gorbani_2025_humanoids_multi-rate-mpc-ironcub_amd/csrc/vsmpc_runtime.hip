@@ -27,6 +27,8 @@
 // LDS holds the record, the linearisation, one stage of Y, the compacted S_FF of the box QP and the vectors.
 // No private array is indexed by a runtime value: the two columns of a thread are unrolled at compile time.
 //
+// solve_kernel_rt_tuned (vsmpc_solve_batch_tuned) is the same body with the weights and the throttle box read from the
+// instance's row of tunables in LDS instead of the kernel argument.
 // sens_kernel_rt (vsmpc_sensitivity_batch) is the same body (vsmpc_runtime_body.inc) with SENS = true; solve_kernel_rt's
 // code is not changed by it.  X0 enters the QP only through the initial-state rows, so the solution's Jacobian with
 // respect to X0 is that of the final active set's affine piece ("Sensitivities"; executable model:
@@ -41,6 +43,7 @@
 //   P6  dX_0 = I, dX_{k+1} = dX_k + dt_k (A dX_k + Bj dU + Bt dV)
 // The 26 right-hand sides of P4 / P5 are solved in place in the parameter rows of the workspace, which then hold dz/dX0.
 #include <atomic>
+#include <cstddef>
 
 #include "vsmpc_launch.hpp"
 #include "vsmpc_p0.hpp"
@@ -155,6 +158,51 @@ __global__ __launch_bounds__(RT_BLOCK) void sens_kernel_rt(DevCfg cfg, RtDims d,
 #include "vsmpc_runtime_body.inc"
 }
 
+// solve_kernel_rt with per-instance tunables (vsmpc_solve_batch_tuned on a runtime handle): the instance's row of `tun`
+// ([batch][VSMPC_TUNE_SIZE], sCfg order) is staged in LDS and stands where the body reads the weights and the throttle box
+// of the kernel argument; cfg.dt, cfg.use_jet and cfg.max_as_iter stay the handle's.
+struct RtTunCfg {   // LDS image: the row (CFG_* order), then what the body reads of the handle's DevCfg
+    double sq[NWROWS], wj[NJ], w_reg, w_thr, w_init, vmin, vmax, pad_;
+    double dt[MAX_STAGES];
+    int use_jet, max_as_iter;
+};
+static_assert(offsetof(RtTunCfg, wj) == CFG_WJ * sizeof(double) && offsetof(RtTunCfg, vmax) == CFG_VMAX * sizeof(double) &&
+              offsetof(RtTunCfg, dt) == CFG_SIZE * sizeof(double) && CFG_SIZE == VSMPC_TUNE_SIZE && sizeof(RtTunCfg) % 8 == 0,
+              "a row of tunables is the head of RtTunCfg");
+__global__ __launch_bounds__(RT_BLOCK) void solve_kernel_rt_tuned(DevCfg hcfg, RtDims d, const double* __restrict__ in,
+                                                                  double* __restrict__ ws, double* __restrict__ xout,
+                                                                  double* __restrict__ fmout, int* __restrict__ status_out,
+                                                                  int* __restrict__ iters_out,
+                                                                  const double* __restrict__ tun) {
+    constexpr bool SENS = false;
+    double* const dxout = nullptr;
+    double* const dfmout = nullptr;
+    int* const active_out = nullptr;
+    int* const flags_out = nullptr;
+    extern __shared__ __attribute__((aligned(16))) double smem_tuned[];
+    double* const sTun = smem_tuned + d.lds_doubles;   // behind the body's carve-up (the launcher adds sizeof(RtTunCfg))
+    RtTunCfg& tcfg = *reinterpret_cast<RtTunCfg*>(sTun);
+    {
+        const int t = threadIdx.x;
+        double2 v = make_double2(0.0, 0.0);
+        if (t < CFG_SIZE / 2) {
+            v = reinterpret_cast<const double2*>(tun + size_t(blockIdx.x) * CFG_SIZE)[t];
+            sTun[2 * t] = v.x;
+            sTun[2 * t + 1] = v.y;
+        }
+        if (t >= 64 && t < 64 + MAX_STAGES) tcfg.dt[t - 64] = hcfg.dt[t - 64];
+        if (t == 128) { tcfg.use_jet = hcfg.use_jet; tcfg.max_as_iter = hcfg.max_as_iter; }
+        // a non-finite tunable ends like a non-finite record: the first square-root weight is made NaN, so that the first pivot
+        // fails and the status is Numerical (the pad entry of the row is not looked at)
+        const bool fin = isfinite(v.x) && (isfinite(v.y) || t == CFG_SIZE / 2 - 1);
+        __syncthreads();
+        if (!fin) tcfg.sq[0] = __builtin_nan("");
+        __syncthreads();
+    }
+    const RtTunCfg& cfg = tcfg;
+#include "vsmpc_runtime_body.inc"
+}
+
 __global__ __launch_bounds__(256) void linearize_kernel_rt(DevCfg cfg, int n_in, const double* __restrict__ in,
                                                            double* __restrict__ A, double* __restrict__ Bj,
                                                            double* __restrict__ Bt, double* __restrict__ c) {
@@ -207,6 +255,19 @@ hipError_t launch_solve_runtime(const RtDims& d, const DevCfg& cfg, const double
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(solve_kernel_rt, dim3(batch), dim3(RT_BLOCK), runtime_lds_bytes(d), stream, cfg, d, d_in, d_ws, d_x,
                        d_fm, d_status, d_iters);
+    return hipGetLastError();
+}
+
+hipError_t launch_solve_runtime_tuned(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
+                                      double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters,
+                                      hipStream_t stream) {
+    static std::atomic<bool> attr_set[RT_MAX_DEV];
+    const size_t lds = runtime_lds_bytes(d) + sizeof(RtTunCfg);            // the staged row lies behind the body's carve-up
+    if (lds > RT_MAX_LDS) return hipErrorInvalidValue;                      // (the largest valid horizon needs 129 KB)
+    const hipError_t e = rt_allow_lds(reinterpret_cast<const void*>(&solve_kernel_rt_tuned), attr_set, d);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(solve_kernel_rt_tuned, dim3(batch), dim3(RT_BLOCK), lds, stream, cfg, d, d_in, d_ws,
+                       d_x, d_fm, d_status, d_iters, d_tun);
     return hipGetLastError();
 }
 

@@ -73,6 +73,10 @@ SENS_BOUND_TOL = 1e-9
 SENS_KERNEL_NAME = "sens_kernel_rt"
 ACTIVE_FREE, ACTIVE_LOWER, ACTIVE_UPPER, ACTIVE_PINNED = 0, -1, 1, 2   # final throttle states (`active`)
 
+# per-instance tunables (vsmpc_pack_tunables / vsmpc_solve_batch_tuned in include/vsmpc.h)
+CREATE_TUNABLES = 0x8
+TUNE_SIZE = 32
+
 # closed-loop rollout: plant state / parameter layouts (VSMPC_PS_* / VSMPC_PP_* in include/vsmpc.h)
 PS_P, PS_HLIN, PS_RPY, PS_HANG, PS_T, PS_TD, PS_Q, PS_U, PS_TDES, PS_TDDES = 0, 3, 6, 9, 12, 16, 20, 28, 32, 36
 PS_TNN, PS_EST, PS_EKFP = 40, 44, 52     # jet plant option (LSTM thrust, EKF estimates (T, Tdot) x 4, covariances 2x2 x 4)

@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib
 from . import layout as L
 from .jet_model import JetModel
-from .solver import BatchedVSMPC, _ptr
+from .solver import BatchedVSMPC, _ptr, pack_tunables
 from .synth import GRAVITY, NOMINAL_MASS, alpha_gravity_profile, takeoff_profile
 
 _JET = JetModel()
@@ -222,6 +222,21 @@ class ClosedLoopRollout:
         self._ctree = None if tree is None else RT.to_c(tree)    # (kept alive; the library copies it anyway)
         _lib.check(self.lib.vsmpc_rollout_set_tree(self._r, None if tree is None else ctypes.byref(self._ctree)),
                    "vsmpc_rollout_set_tree")
+
+    def set_tunables(self, configs=None, tunables=None):
+        """Per-instance weights and throttle box for the loops' solves (vsmpc_rollout_set_tunables): `configs` = one
+        MPCConfig per loop, or `tunables` = their packed rows [batch, L.TUNE_SIZE] (solver.pack_tunables); neither = back
+        to the shared configuration.  Call reset() afterwards."""
+        if configs is not None and tunables is not None:
+            raise ValueError("give configs or tunables, not both")
+        rows = None
+        if configs is not None:
+            rows = pack_tunables(self.mpc, configs)
+        elif tunables is not None:
+            rows = np.ascontiguousarray(tunables, dtype=np.float64)
+        if rows is not None and rows.shape != (self.batch, L.TUNE_SIZE):
+            raise ValueError(f"one configuration / one row of {L.TUNE_SIZE} tunables per loop ({self.batch})")
+        _lib.check(self.lib.vsmpc_rollout_set_tunables(self._r, _ptr(rows)), "vsmpc_rollout_set_tunables")
 
     def set_jet_plant(self, jet_model=None, Q=None, R=None):
         """Jet plant option (vsmpc_rollout_set_jet_plant): `jet_model` = a jet_plant.JetModelTotal (the LSTM thrust model;

@@ -27,26 +27,41 @@ def _ptr(a):
 KERNEL_FORM_AUTO, KERNEL_FORM_STRUCTURED, KERNEL_FORM_SYRK = 0, 1, 2
 
 
+def pack_tunables(handle_or_solver, configs) -> np.ndarray:
+    """vsmpc_pack_tunables: the per-instance rows [len(configs), L.TUNE_SIZE] of `configs` (MPCConfig objects) for a
+    handle (a BatchedVSMPC, or its raw handle).  A row is opaque: the weights and the throttle box in the form the kernels
+    keep them in.  A configuration that differs from the handle's in a structural field (horizon sizes, periods,
+    use_jet_dynamic) or fails the value checks raises VsmpcError naming the field."""
+    h = getattr(handle_or_solver, "_h", handle_or_solver)
+    configs = list(configs)
+    arr = (L.CConfig * max(1, len(configs)))(*[c.to_c() for c in configs])
+    out = np.empty((len(configs), L.TUNE_SIZE))
+    _lib.check(_lib.load().vsmpc_pack_tunables(h, arr, len(configs), _ptr(out)), "vsmpc_pack_tunables")
+    return out
+
+
 class BatchedVSMPC:
     """`max_batch` independent MPC instances on one GPU (one workgroup per instance)."""
 
     def __init__(self, cfg: L.MPCConfig | None = None, device: int = 0, max_batch: int = 256, runtime: str = "never",
-                 sensitivity: bool = False):
+                 sensitivity: bool = False, tunables: bool = False):
         """runtime: "never" -- the tuned kernel of a tabled horizon, other horizons are refused (vsmpc_create);
         "fallback" -- the runtime-sized kernel where the table has no instantiation; "always" -- the runtime-sized kernel
         for every horizon (vsmpc_create_ex, include/vsmpc.h).  sensitivity: also allocate what solve_sensitivity needs
-        (VSMPC_CREATE_SENSITIVITY)."""
+        (VSMPC_CREATE_SENSITIVITY).  tunables: also allocate the staging of solve(records, configs=...), one row of
+        weights and throttle box per instance (VSMPC_CREATE_TUNABLES)."""
         if runtime not in L.RUNTIME_MODES:
             raise ValueError(f"runtime must be one of {sorted(L.RUNTIME_MODES)}, not {runtime!r}")
         self.cfg = cfg or L.paper_config()
         self.lib = _lib.load()
         self._ccfg = self.cfg.to_c()
         self._h = ctypes.c_void_p()
-        if runtime == "never" and not sensitivity:
+        if runtime == "never" and not sensitivity and not tunables:
             _lib.check(self.lib.vsmpc_create(ctypes.byref(self._ccfg), device, max_batch, ctypes.byref(self._h)),
                        "vsmpc_create")
         else:
-            flags = L.RUNTIME_MODES[runtime] | (L.CREATE_SENSITIVITY if sensitivity else 0)
+            flags = (L.RUNTIME_MODES[runtime] | (L.CREATE_SENSITIVITY if sensitivity else 0)
+                     | (L.CREATE_TUNABLES if tunables else 0))
             _lib.check(self.lib.vsmpc_create_ex(ctypes.byref(self._ccfg), device, max_batch, flags, ctypes.byref(self._h)),
                        "vsmpc_create_ex")
         self.device = device
@@ -87,7 +102,10 @@ class BatchedVSMPC:
         return self.kernel_name == L.RUNTIME_KERNEL_NAME
 
     # ---- host-buffer entry (vsmpc_solve_batch)
-    def solve(self, inputs: np.ndarray):
+    def solve(self, inputs: np.ndarray, configs=None, tunables=None):
+        """vsmpc_solve_batch; with `configs` (one MPCConfig per instance) or `tunables` (their packed rows, pack_tunables)
+        vsmpc_solve_batch_tuned: instance i is solved under its own weights and throttle box (needs tunables=True at
+        construction)."""
         inputs = np.ascontiguousarray(inputs, dtype=np.float64)
         if inputs.ndim != 2 or inputs.shape[1] != self.n_in:
             raise ValueError(f"inputs must be [batch, {self.n_in}]")
@@ -96,6 +114,15 @@ class BatchedVSMPC:
         fm = np.empty((B, L.FM_SIZE))
         status = np.empty(B, dtype=np.int32)
         iters = np.empty(B, dtype=np.int32)
+        if configs is not None or tunables is not None:
+            if configs is not None and tunables is not None:
+                raise ValueError("give configs or tunables, not both")
+            rows = pack_tunables(self, configs) if configs is not None else np.ascontiguousarray(tunables, dtype=np.float64)
+            if rows.shape != (B, L.TUNE_SIZE):
+                raise ValueError(f"one configuration / one row of {L.TUNE_SIZE} tunables per instance ({B})")
+            _lib.check(self.lib.vsmpc_solve_batch_tuned(self._h, _ptr(inputs), _ptr(rows), B, _ptr(x), _ptr(fm), _ptr(status),
+                                                        _ptr(iters), None), "vsmpc_solve_batch_tuned")
+            return x, fm, status, iters
         _lib.check(self.lib.vsmpc_solve_batch(self._h, _ptr(inputs), B, _ptr(x), _ptr(fm), _ptr(status),
                                               _ptr(iters), None), "vsmpc_solve_batch")
         return x, fm, status, iters
@@ -113,6 +140,23 @@ class BatchedVSMPC:
             ctypes.c_void_p(d_status.data_ptr()),
             ctypes.c_void_p(d_iters.data_ptr()) if d_iters is not None else None,
             ctypes.c_void_p(s.cuda_stream)), "vsmpc_solve_batch_device")
+
+    def solve_device_tuned(self, d_in, d_tun, d_x, d_fm, d_status, d_iters, stream=None):
+        """vsmpc_solve_batch_tuned_device: solve_device with d_tun [batch, L.TUNE_SIZE], the rows of pack_tunables on the
+        device (needs no construction flag)"""
+        import torch
+        assert d_in.is_cuda and d_in.dtype == torch.float64 and d_in.is_contiguous()
+        assert d_tun.is_cuda and d_tun.dtype == torch.float64 and d_tun.is_contiguous()
+        B = d_in.shape[0]
+        assert tuple(d_tun.shape) == (B, L.TUNE_SIZE)
+        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
+        _lib.check(self.lib.vsmpc_solve_batch_tuned_device(
+            self._h, ctypes.c_void_p(d_in.data_ptr()), ctypes.c_void_p(d_tun.data_ptr()), B,
+            ctypes.c_void_p(d_x.data_ptr()) if d_x is not None else None,
+            ctypes.c_void_p(d_fm.data_ptr()) if d_fm is not None else None,
+            ctypes.c_void_p(d_status.data_ptr()),
+            ctypes.c_void_p(d_iters.data_ptr()) if d_iters is not None else None,
+            ctypes.c_void_p(s.cuda_stream)), "vsmpc_solve_batch_tuned_device")
 
     # ---- sensitivities of the solution to X0 (vsmpc_sensitivity_batch); needs sensitivity=True at construction
     def solve_sensitivity(self, inputs: np.ndarray, jacobian: bool = True) -> dict:
