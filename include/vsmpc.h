@@ -148,6 +148,9 @@ int vsmpc_create(const vsmpc_config* cfg, int device, int max_batch, vsmpc_handl
 #define VSMPC_CREATE_RUNTIME_ONLY 0x2u
 #define VSMPC_CREATE_SENSITIVITY 0x4u
 #define VSMPC_CREATE_TUNABLES 0x8u      /* device staging of vsmpc_solve_batch_tuned: max_batch x VSMPC_TUNE_SIZE doubles */
+#define VSMPC_CREATE_CERTIFY 0x20u      /* device staging of vsmpc_certify_batch: max_batch x (nCon + VSMPC_CERT_SIZE) doubles
+                                           for y and the certificate, max_batch x nVar for x, max_batch x VSMPC_TUNE_SIZE
+                                           for the rows.  Bit 0x10 is reserved (refused like every unknown bit) */
 int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned flags, vsmpc_handle** out);
 void vsmpc_destroy(vsmpc_handle* h);
 
@@ -234,6 +237,52 @@ int vsmpc_sensitivity_batch(vsmpc_handle* h, const double* in, int batch, double
 int vsmpc_sensitivity_batch_device(vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_first_move,
                                    int* d_status, int* d_iters, double* d_dx_dx0, double* d_dfm_dx0, int* d_active,
                                    int* d_sens_flags, void* stream);
+
+/*
+ * Duals and a KKT certificate of a GIVEN primal, for every instance of a batch.  The QP is the reference-ordered dense one
+ * (oracle/vsmpc_ref.py assemble_dense; IMPCProblem.cpp:150-194): min 1/2 x'Hx + g'x subject to lo <= Ac x <= hi.  `x` is an
+ * input ([batch][nVar], reference variable order): usually what vsmpc_solve_batch returned, but the check never runs the
+ * solver's code and judges any x.  With x given, stationarity of the state columns defines the equality duals (one
+ * backward costate recursion through A), stationarity of the throttle columns defines the box multipliers, and the joint
+ * columns' gradient is what is left ("Duals and certificate"): O(N) work on 26-vectors per instance.
+ *
+ * y[batch][nCon], nCon = vsmpc_num_constraints(h), in the reference's row order (dynamics blocks 0..N-1 | initial state |
+ * throttle blocks) and with the sign of oracle/vsmpc_ref.py solve_exact, which is OSQP's: y > 0 where the upper bound of a
+ * row is active, y < 0 where the lower one is.  The throttle rows behind block controlHorizon - nIterSmall are exactly 0
+ * (constraintsVSMPC.cpp:338-365 leaves them [0, 0] with an empty row).  y may be NULL when only the certificate is wanted.
+ *
+ * cert[batch][VSMPC_CERT_SIZE] restates oracle/vsmpc_ref.py kkt_certificate on (x, y):
+ *   STATIONARITY     max over the joint blocks j of |(W_dq + w_reg I) U_j + w_reg q_err + sum_{i: jb(i) = j} dt_i Bj' y_i|_inf.
+ *                    Every other entry of Hx + g + Ac'y is zero by the construction of y (to the rounding of the recursion),
+ *                    so this is |Hx + g + Ac'y|_inf
+ *   STAT_SCALE       max(1, |g|_inf, |Hx|_inf), the oracle's scale of `stationarity_rel`
+ *   PRIMAL           max over all rows of max(0, lo - Ac x, Ac x - hi): dynamics rows, X_0 = x0, the throttle box, and
+ *                    the hold pin when in[VSMPC_IN_HOLD] != 0
+ *   COMPLEMENTARITY  max over the throttle rows with lo < hi of max(y+ (hi - v), y- (v - lo)); pinned rows are excluded,
+ *                    as in the oracle
+ *   OBJECTIVE        1/2 x'Hx + g'x, the oracle's value (no constant term), summed in a fixed order
+ *   DUAL_MAX         |y|_inf
+ * and two reserved entries that are 0.  A non-finite record, tunable or x makes STATIONARITY and PRIMAL NaN.  Results do not
+ * depend on an instance's position in the batch: repeated and permuted batches are bit-identical.
+ * The certificate is a statement about this restated QP, not about the reference's solver output (parity unpinned).
+ * tunables: rows of vsmpc_pack_tunables, one per instance, or NULL = the handle's configuration for every instance.
+ */
+#define VSMPC_CERT_STATIONARITY 0
+#define VSMPC_CERT_STAT_SCALE 1
+#define VSMPC_CERT_PRIMAL 2
+#define VSMPC_CERT_COMPLEMENTARITY 3
+#define VSMPC_CERT_OBJECTIVE 4
+#define VSMPC_CERT_DUAL_MAX 5
+#define VSMPC_CERT_SIZE 8
+/* Host buffers; returns after the results are in them.  Needs a handle created with VSMPC_CREATE_CERTIFY (otherwise
+ * VSMPC_ERR_UNSUPPORTED_CONFIG, and vsmpc_strerror names the flag).  NULL handle, in, x or cert: VSMPC_ERR_INVALID_ARG;
+ * batch 0: VSMPC_OK, nothing touched; batch > vsmpc_max_batch(h): VSMPC_ERR_BATCH_TOO_LARGE.  Tuned and runtime handles. */
+int vsmpc_certify_batch(vsmpc_handle* h, const double* in, const double* x, const double* tunables, int batch, double* y,
+                        double* cert);
+/* Same, all pointers are DEVICE pointers (d_in, d_x, d_tunables, d_y 16-byte aligned) and the call only enqueues one
+ * launch on `stream`.  Needs no create flag: it uses no staging. */
+int vsmpc_certify_batch_device(vsmpc_handle* h, const double* d_in, const double* d_x, const double* d_tunables, int batch,
+                               double* d_y, double* d_cert, void* stream);
 
 /* Parity split of the path: only the per-tick linearisation + discretisation, i.e.
  * SystemDynamicVS::updateDynamicMatrices/getAMatrix/getBJointsMatrix/getBThrottleMatrix/getCVector

@@ -21,7 +21,7 @@ EXPORTS = (
     "vsmpc_set_kernel_form", "vsmpc_set_kinematics_options", "vsmpc_provider_batch", "vsmpc_rollout_set_attitude_tracks",
     "vsmpc_tick", "vsmpc_rollout_set_tree", "vsmpc_num_throttle_unknowns", "vsmpc_sensitivity_batch",
     "vsmpc_sensitivity_batch_device", "vsmpc_pack_tunables", "vsmpc_solve_batch_tuned", "vsmpc_solve_batch_tuned_device",
-    "vsmpc_rollout_set_tunables",
+    "vsmpc_rollout_set_tunables", "vsmpc_certify_batch", "vsmpc_certify_batch_device",
     # include/vsmpc_jet.h
     "vsmpc_jet_create", "vsmpc_jet_destroy", "vsmpc_jet_nn_step", "vsmpc_jet_nn_sequence", "vsmpc_jet_ekf_update",
     "vsmpc_jet_plant_run", "vsmpc_jet_plant_run_device", "vsmpc_rollout_set_jet_plant",
@@ -71,6 +71,11 @@ def load():
     lib.vsmpc_solve_batch_tuned_device.restype = c_int
     lib.vsmpc_rollout_set_tunables.argtypes = [vp, dp]
     lib.vsmpc_rollout_set_tunables.restype = c_int
+    # h, in, x, tunables, batch, y, cert (, stream)
+    lib.vsmpc_certify_batch.argtypes = [vp, dp, dp, dp, c_int, dp, dp]
+    lib.vsmpc_certify_batch.restype = c_int
+    lib.vsmpc_certify_batch_device.argtypes = [vp, dp, dp, dp, c_int, dp, dp, vp]
+    lib.vsmpc_certify_batch_device.restype = c_int
     # h, in, batch, x, first_move, status, iters, dx_dx0, dfm_dx0, active, sens_flags, stream
     lib.vsmpc_sensitivity_batch.argtypes = [vp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp, vp]
     lib.vsmpc_sensitivity_batch.restype = c_int

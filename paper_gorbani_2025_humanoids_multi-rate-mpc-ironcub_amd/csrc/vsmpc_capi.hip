@@ -33,6 +33,12 @@ struct vsmpc_handle {
     // VSMPC_CREATE_TUNABLES: device staging of the rows of vsmpc_solve_batch_tuned, max_batch x VSMPC_TUNE_SIZE
     int tunables;
     double* d_tun;
+    // VSMPC_CREATE_CERTIFY: device staging of vsmpc_certify_batch for max_batch instances: x, y | certificate, tunables
+    int certify;
+    double* d_cx;
+    double* d_cy;
+    double* d_ccert;
+    double* d_ctun;
     int form;       // condensing form of the solve kernel (vsmpc_set_kernel_form)
     KinOpts kin;     // vsmpc_set_kinematics_options
     int device;
@@ -254,6 +260,15 @@ bool config_valid(const vsmpc_config& c) {
 
 thread_local char g_arg_msg[160] = "";   // the last refusal of vsmpc_pack_tunables on this thread (vsmpc_strerror)
 
+// VSMPC_ERR_UNSUPPORTED_CONFIG with the plain text, or with `why` for the entries whose refusal names a create flag
+// (vsmpc_strerror describes the call that failed last on this thread).  Every return of that code in this library goes
+// through here: a site that returned the bare constant would leave the text of an earlier refusal standing.
+thread_local const char* g_unsupported_msg = nullptr;
+int unsupported(const char* why = nullptr) {
+    g_unsupported_msg = why;
+    return VSMPC_ERR_UNSUPPORTED_CONFIG;
+}
+
 // the name of the first structural field in which `c` differs from the handle's configuration, or nullptr
 const char* structural_mismatch(const vsmpc_config& c, const vsmpc_config& h) {
     if (c.n_iter != h.n_iter) return "n_iter";
@@ -286,18 +301,19 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     if (cfg == nullptr || out == nullptr || max_batch <= 0) return invalid_arg();
     *out = nullptr;
     const unsigned kernel_flags = VSMPC_CREATE_RUNTIME_FALLBACK | VSMPC_CREATE_RUNTIME_ONLY;
-    if ((flags & ~(kernel_flags | VSMPC_CREATE_SENSITIVITY | VSMPC_CREATE_TUNABLES)) != 0u) return invalid_arg();
+    if ((flags & ~(kernel_flags | VSMPC_CREATE_SENSITIVITY | VSMPC_CREATE_TUNABLES | VSMPC_CREATE_CERTIFY)) != 0u)
+        return invalid_arg();
     if (!config_valid(*cfg)) return invalid_arg();
     const int variant = (flags & VSMPC_CREATE_RUNTIME_ONLY)
                             ? int(VARIANT_NONE)
                             : select_variant(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon);
-    if (variant == VARIANT_NONE && (flags & kernel_flags) == 0u) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    if (variant == VARIANT_NONE && (flags & kernel_flags) == 0u) return unsupported();
     const bool runtime = variant == VARIANT_NONE;
     const RtDims rt = runtime_dims(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon);
-    if (runtime && runtime_lds_bytes(rt) > RT_MAX_LDS) return VSMPC_ERR_UNSUPPORTED_CONFIG;   // (not for a valid config)
+    if (runtime && runtime_lds_bytes(rt) > RT_MAX_LDS) return unsupported();   // (not for a valid config)
     const bool sens = (flags & VSMPC_CREATE_SENSITIVITY) != 0u;
     const RtDims rts = runtime_dims(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon, true);
-    if (sens && runtime_lds_bytes(rts) > RT_MAX_LDS) return VSMPC_ERR_UNSUPPORTED_CONFIG;     // (not for a valid config)
+    if (sens && runtime_lds_bytes(rts) > RT_MAX_LDS) return unsupported();     // (not for a valid config)
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return invalid_arg();
@@ -314,6 +330,7 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     h->sens = sens ? 1 : 0;
     h->rts = rts;
     h->tunables = (flags & VSMPC_CREATE_TUNABLES) != 0u ? 1 : 0;
+    h->certify = (flags & VSMPC_CREATE_CERTIFY) != 0u ? 1 : 0;
     h->form = runtime ? 0 : initial_kernel_form();
     for (int i = 0; i < VSMPC_N_JOINTS; ++i) h->kin.sel[i] = 3 + i;   // the shipped robot: joints 3..10
     h->kin.constant_lambda = 0;
@@ -348,6 +365,12 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
         if (e == hipSuccess) e = hipMalloc(&h->d_sflags, C * sizeof(int));
     }
     if (e == hipSuccess && h->tunables) e = hipMalloc(&h->d_tun, B * VSMPC_TUNE_SIZE * sizeof(double));
+    if (h->certify) {
+        if (e == hipSuccess) e = hipMalloc(&h->d_cx, B * h->n_var * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(&h->d_cy, B * h->n_con * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(&h->d_ccert, B * VSMPC_CERT_SIZE * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(&h->d_ctun, B * VSMPC_TUNE_SIZE * sizeof(double));
+    }
     for (int i = 0; i < PIPE_STREAMS && e == hipSuccess; ++i) {
         e = hipStreamCreateWithFlags(&h->pipe[i], hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&h->pipe_done[i], hipEventDisableTiming);
@@ -389,6 +412,10 @@ void vsmpc_destroy(vsmpc_handle* h) {
     if (h->d_sact) (void)hipFree(h->d_sact);
     if (h->d_sflags) (void)hipFree(h->d_sflags);
     if (h->d_tun) (void)hipFree(h->d_tun);
+    if (h->d_cx) (void)hipFree(h->d_cx);
+    if (h->d_cy) (void)hipFree(h->d_cy);
+    if (h->d_ccert) (void)hipFree(h->d_ccert);
+    if (h->d_ctun) (void)hipFree(h->d_ctun);
     for (int i = 0; i < PIPE_STREAMS; ++i) {
         if (h->pipe[i]) (void)hipStreamDestroy(h->pipe[i]);
         if (h->pipe_done[i]) (void)hipEventDestroy(h->pipe_done[i]);
@@ -552,7 +579,7 @@ int vsmpc_solve_batch_tuned_device(vsmpc_handle* h, const double* d_in, const do
 int vsmpc_solve_batch_tuned(vsmpc_handle* h, const double* in, const double* tunables, int batch, double* x,
                             double* first_move, int* status, int* iters, void* stream) {
     if (h == nullptr || in == nullptr || tunables == nullptr || status == nullptr || batch < 0) return invalid_arg();
-    if (!h->tunables) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    if (!h->tunables) return unsupported();
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (batch == 0) return VSMPC_OK;
     return solve_batch_host(h, in, tunables, batch, x, first_move, status, iters, stream);
@@ -564,7 +591,7 @@ int vsmpc_sensitivity_batch_device(vsmpc_handle* h, const double* d_in, int batc
                                    int* d_status, int* d_iters, double* d_dx_dx0, double* d_dfm_dx0, int* d_active,
                                    int* d_sens_flags, void* stream) {
     if (h == nullptr || d_in == nullptr || d_status == nullptr || batch < 0) return invalid_arg();
-    if (!h->sens) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    if (!h->sens) return unsupported();
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (batch == 0) return VSMPC_OK;
     ON_DEVICE(h->device);
@@ -576,7 +603,7 @@ int vsmpc_sensitivity_batch_device(vsmpc_handle* h, const double* d_in, int batc
 int vsmpc_sensitivity_batch(vsmpc_handle* h, const double* in, int batch, double* x, double* first_move, int* status,
                             int* iters, double* dx_dx0, double* dfm_dx0, int* active, int* sens_flags, void* stream) {
     if (h == nullptr || in == nullptr || status == nullptr || batch < 0) return invalid_arg();
-    if (!h->sens) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    if (!h->sens) return unsupported();
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (batch == 0) return VSMPC_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -610,6 +637,42 @@ int vsmpc_sensitivity_batch(vsmpc_handle* h, const double* in, int batch, double
     const hipError_t e = hipStreamSynchronize(s);   // nothing returns while copies into the caller's buffers are queued
     if (err == hipSuccess) err = e;
     if (err != hipSuccess) return hip_fail(err, "vsmpc_sensitivity_batch");
+    return VSMPC_OK;
+}
+
+// Duals and KKT certificate of given primals: certify_kernel restates the oracle's solve_exact (the duals, OSQP's sign:
+// y > 0 upper-active, y < 0 lower-active) and its kkt_certificate on the QP of assemble_dense (module cited in include/vsmpc.h)
+int vsmpc_certify_batch_device(vsmpc_handle* h, const double* d_in, const double* d_x, const double* d_tunables, int batch,
+                               double* d_y, double* d_cert, void* stream) {
+    if (h == nullptr || d_in == nullptr || d_x == nullptr || d_cert == nullptr || batch < 0) return invalid_arg();
+    // the kernel loads and stores 16 bytes per lane
+    if (((reinterpret_cast<size_t>(d_in) | reinterpret_cast<size_t>(d_x) | reinterpret_cast<size_t>(d_tunables) |
+          reinterpret_cast<size_t>(d_y)) & 15) != 0 || (reinterpret_cast<size_t>(d_cert) & 7) != 0)
+        return invalid_arg();
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    if (batch == 0) return VSMPC_OK;
+    ON_DEVICE(h->device);
+    HIP_TRY(launch_certify(h->rt, h->dev, d_in, d_x, d_tunables, batch, d_y, d_cert, static_cast<hipStream_t>(stream)));
+    return VSMPC_OK;
+}
+
+int vsmpc_certify_batch(vsmpc_handle* h, const double* in, const double* x, const double* tunables, int batch, double* y,
+                        double* cert) {
+    if (h == nullptr || in == nullptr || x == nullptr || cert == nullptr || batch < 0) return invalid_arg();
+    if (!h->certify)
+        return unsupported("vsmpc_certify_batch needs a handle created with VSMPC_CREATE_CERTIFY (vsmpc_create_ex)");
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    if (batch == 0) return VSMPC_OK;
+    ON_DEVICE(h->device);
+    const size_t B = size_t(batch);
+    HIP_TRY(hipMemcpy(h->d_in, in, B * h->n_in * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_cx, x, B * h->n_var * sizeof(double), hipMemcpyHostToDevice));
+    if (tunables) HIP_TRY(hipMemcpy(h->d_ctun, tunables, B * VSMPC_TUNE_SIZE * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(launch_certify(h->rt, h->dev, h->d_in, h->d_cx, tunables ? h->d_ctun : nullptr, batch, y ? h->d_cy : nullptr,
+                           h->d_ccert, nullptr));
+    // (copies on the null stream: ordered behind the launch, and complete on return)
+    if (y) HIP_TRY(hipMemcpy(y, h->d_cy, B * h->n_con * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cert, h->d_ccert, B * VSMPC_CERT_SIZE * sizeof(double), hipMemcpyDeviceToHost));
     return VSMPC_OK;
 }
 
@@ -730,7 +793,7 @@ int vsmpc_assemble_dense(vsmpc_handle* h, const double* in_one, double* H, doubl
 
 int vsmpc_debug_condensed(vsmpc_handle* h, const double* in_one, double* M, double* Lfac) {
     if (h == nullptr || in_one == nullptr) return invalid_arg();
-    if (h->runtime) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    if (h->runtime) return unsupported();
     ON_DEVICE(h->device);
     const size_t np2 = size_t(h->n_p) * h->n_p;
     HIP_TRY(hipMemcpy(h->d_in, in_one, h->n_in * sizeof(double), hipMemcpyHostToDevice));
@@ -810,7 +873,7 @@ int vsmpc_provider_batch(vsmpc_handle* h, const vsmpc_tree* tree, const double* 
     if (batch == 0) return VSMPC_OK;
     // the provider delivers the CURRENT frame Jacobians; jointsLambdaOption "constant" re-reads those slots as the
     // configure-time relative Jacobians and thrusts (vsmpc_set_kinematics_options): the combination has no meaning
-    if (records != nullptr && h->kin.constant_lambda) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    if (records != nullptr && h->kin.constant_lambda) return unsupported();
     if (tree->parent[0] != -1) return invalid_arg();
     for (int b = 1; b < VSMPC_TREE_NB; ++b)
         if (tree->parent[b] < 0 || tree->parent[b] >= b) return invalid_arg();      // parents precede children
@@ -851,7 +914,7 @@ int vsmpc_set_kinematics_options(vsmpc_handle* h, const int* joint_selector, int
 
 int vsmpc_debug_phase_cycles(vsmpc_handle* h, const double* in, int batch, unsigned long long* stamps16) {
     if (h == nullptr || in == nullptr || stamps16 == nullptr || batch <= 0) return invalid_arg();
-    if (h->runtime) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    if (h->runtime) return unsupported();
     if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
     ON_DEVICE(h->device);
     unsigned long long* d_st = h->d_stamps;
@@ -1169,8 +1232,8 @@ int vsmpc_rollout_get_records(vsmpc_rollout* r, double* records) {
 
 int vsmpc_set_kernel_form(vsmpc_handle* h, int form) {
     if (h == nullptr || form < 0 || form > 2) return invalid_arg();
-    if (h->runtime && form != 0) return VSMPC_ERR_UNSUPPORTED_CONFIG;   // the runtime kernel has one form
-    if (form == 1 && !variant_has_structured(h->variant)) return VSMPC_ERR_UNSUPPORTED_CONFIG;
+    if (h->runtime && form != 0) return unsupported();   // the runtime kernel has one form
+    if (form == 1 && !variant_has_structured(h->variant)) return unsupported();
     const int prev = h->form;
     h->form = form;
     return prev;
@@ -1190,7 +1253,8 @@ const char* vsmpc_strerror(int code) {
     switch (code) {
         case VSMPC_OK: return "ok";
         case VSMPC_ERR_INVALID_ARG: return g_arg_msg[0] ? g_arg_msg : "invalid argument";
-        case VSMPC_ERR_UNSUPPORTED_CONFIG: return "unsupported MPC configuration (no kernel instantiation)";
+        case VSMPC_ERR_UNSUPPORTED_CONFIG:
+            return g_unsupported_msg ? g_unsupported_msg : "unsupported MPC configuration (no kernel instantiation)";
         case VSMPC_ERR_BATCH_TOO_LARGE: return "batch exceeds max_batch of the handle";
         case VSMPC_ERR_HIP: return g_hip_msg[0] ? g_hip_msg : "HIP runtime error";
         case VSMPC_ERR_ALLOC: return "allocation failed";

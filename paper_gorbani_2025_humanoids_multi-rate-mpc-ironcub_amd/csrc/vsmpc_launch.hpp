@@ -92,6 +92,12 @@ hipError_t launch_sensitivity_runtime(const RtDims& d, const DevCfg& cfg, const 
 hipError_t launch_linearize_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,
                                     double* Bt, double* c, hipStream_t stream);
 
+// certify_kernel (vsmpc_certify.hip): duals y [batch][nCon] (or nullptr) and certificate [batch][VSMPC_CERT_SIZE] of the
+// primals d_x [batch][nvar] for the records d_in; d from runtime_dims(.., false) on every handle; d_tun rows of
+// per-instance tunables or nullptr (the handle's configuration).  d_in, d_x, d_tun, d_y 16-byte aligned.
+hipError_t launch_certify(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_x, const double* d_tun,
+                          int batch, double* d_y, double* d_cert, hipStream_t stream);
+
 struct KinOpts {
     int sel[VSMPC_N_JOINTS];   // robot joint index of every controlled joint (Lambda_ang columns)
     int constant_lambda;       // jointsLambdaOption "constant"

@@ -77,6 +77,12 @@ ACTIVE_FREE, ACTIVE_LOWER, ACTIVE_UPPER, ACTIVE_PINNED = 0, -1, 1, 2   # final t
 CREATE_TUNABLES = 0x8
 TUNE_SIZE = 32
 
+# duals and KKT certificate (vsmpc_certify_batch, VSMPC_CERT_* in include/vsmpc.h)
+CREATE_CERTIFY = 0x20
+CERT_STATIONARITY, CERT_STAT_SCALE, CERT_PRIMAL, CERT_COMPLEMENTARITY, CERT_OBJECTIVE, CERT_DUAL_MAX = 0, 1, 2, 3, 4, 5
+CERT_SIZE = 8
+CERTIFY_KERNEL_NAME = "certify_kernel"
+
 # closed-loop rollout: plant state / parameter layouts (VSMPC_PS_* / VSMPC_PP_* in include/vsmpc.h)
 PS_P, PS_HLIN, PS_RPY, PS_HANG, PS_T, PS_TD, PS_Q, PS_U, PS_TDES, PS_TDDES = 0, 3, 6, 9, 12, 16, 20, 28, 32, 36
 PS_TNN, PS_EST, PS_EKFP = 40, 44, 52     # jet plant option (LSTM thrust, EKF estimates (T, Tdot) x 4, covariances 2x2 x 4)

@@ -25,6 +25,24 @@ def _ptr(a):
 
 
 KERNEL_FORM_AUTO, KERNEL_FORM_STRUCTURED, KERNEL_FORM_SYRK = 0, 1, 2
+# columns of the certificate of BatchedVSMPC.certify (VSMPC_CERT_* in include/vsmpc.h)
+CERT_STATIONARITY, CERT_STAT_SCALE, CERT_PRIMAL = L.CERT_STATIONARITY, L.CERT_STAT_SCALE, L.CERT_PRIMAL
+CERT_COMPLEMENTARITY, CERT_OBJECTIVE, CERT_DUAL_MAX = L.CERT_COMPLEMENTARITY, L.CERT_OBJECTIVE, L.CERT_DUAL_MAX
+CERT_SIZE = L.CERT_SIZE
+
+
+def certified(cert: np.ndarray, x_scale, tol: float = 1e-9) -> np.ndarray:
+    """Per instance: does the certificate `cert` [batch, CERT_SIZE] of BatchedVSMPC.certify pass the three relative tests
+    STATIONARITY <= tol STAT_SCALE, PRIMAL <= tol max(1, x_scale), COMPLEMENTARITY <= tol max(1, DUAL_MAX)?  `x_scale`
+    is |x|_inf per instance (or the primals [batch, n_var] themselves).  A NaN field (non-finite data) fails."""
+    cert = np.asarray(cert, dtype=np.float64)
+    xs = np.asarray(x_scale, dtype=np.float64)
+    if xs.ndim == 2:
+        xs = np.abs(xs).max(axis=1)
+    with np.errstate(invalid="ignore"):
+        return ((cert[:, CERT_STATIONARITY] <= tol * cert[:, CERT_STAT_SCALE])
+                & (cert[:, CERT_PRIMAL] <= tol * np.maximum(1.0, xs))
+                & (cert[:, CERT_COMPLEMENTARITY] <= tol * np.maximum(1.0, cert[:, CERT_DUAL_MAX])))
 
 
 def pack_tunables(handle_or_solver, configs) -> np.ndarray:
@@ -44,24 +62,25 @@ class BatchedVSMPC:
     """`max_batch` independent MPC instances on one GPU (one workgroup per instance)."""
 
     def __init__(self, cfg: L.MPCConfig | None = None, device: int = 0, max_batch: int = 256, runtime: str = "never",
-                 sensitivity: bool = False, tunables: bool = False):
+                 sensitivity: bool = False, tunables: bool = False, certify: bool = False):
         """runtime: "never" -- the tuned kernel of a tabled horizon, other horizons are refused (vsmpc_create);
         "fallback" -- the runtime-sized kernel where the table has no instantiation; "always" -- the runtime-sized kernel
         for every horizon (vsmpc_create_ex, include/vsmpc.h).  sensitivity: also allocate what solve_sensitivity needs
         (VSMPC_CREATE_SENSITIVITY).  tunables: also allocate the staging of solve(records, configs=...), one row of
-        weights and throttle box per instance (VSMPC_CREATE_TUNABLES)."""
+        weights and throttle box per instance (VSMPC_CREATE_TUNABLES).  certify: also allocate the staging of
+        certify(records, x) (VSMPC_CREATE_CERTIFY)."""
         if runtime not in L.RUNTIME_MODES:
             raise ValueError(f"runtime must be one of {sorted(L.RUNTIME_MODES)}, not {runtime!r}")
         self.cfg = cfg or L.paper_config()
         self.lib = _lib.load()
         self._ccfg = self.cfg.to_c()
         self._h = ctypes.c_void_p()
-        if runtime == "never" and not sensitivity and not tunables:
+        if runtime == "never" and not sensitivity and not tunables and not certify:
             _lib.check(self.lib.vsmpc_create(ctypes.byref(self._ccfg), device, max_batch, ctypes.byref(self._h)),
                        "vsmpc_create")
         else:
             flags = (L.RUNTIME_MODES[runtime] | (L.CREATE_SENSITIVITY if sensitivity else 0)
-                     | (L.CREATE_TUNABLES if tunables else 0))
+                     | (L.CREATE_TUNABLES if tunables else 0) | (L.CREATE_CERTIFY if certify else 0))
             _lib.check(self.lib.vsmpc_create_ex(ctypes.byref(self._ccfg), device, max_batch, flags, ctypes.byref(self._h)),
                        "vsmpc_create_ex")
         self.device = device
@@ -157,6 +176,46 @@ class BatchedVSMPC:
             ctypes.c_void_p(d_status.data_ptr()),
             ctypes.c_void_p(d_iters.data_ptr()) if d_iters is not None else None,
             ctypes.c_void_p(s.cuda_stream)), "vsmpc_solve_batch_tuned_device")
+
+    # ---- duals and KKT certificate of given primals (vsmpc_certify_batch); needs certify=True at construction
+    def certify(self, records: np.ndarray, x: np.ndarray, configs=None, tunables=None, duals: bool = True):
+        """vsmpc_certify_batch: (y [B, n_con], cert [B, CERT_SIZE]) of the primals `x` [B, n_var] for `records` -- the
+        duals in the reference's row order and OSQP's sign, and the certificate columns CERT_* (include/vsmpc.h).  `x` is
+        usually solve()'s, but any x is judged.  With `configs` (one MPCConfig per instance, through pack_tunables) or
+        `tunables` (their packed rows) instance i is certified under its own weights and throttle box.  duals=False: y is
+        not wanted (returned as None)."""
+        records = np.ascontiguousarray(records, dtype=np.float64)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if records.ndim != 2 or records.shape[1] != self.n_in:
+            raise ValueError(f"records must be [batch, {self.n_in}]")
+        B = records.shape[0]
+        if x.shape != (B, self.n_var):
+            raise ValueError(f"x must be [{B}, {self.n_var}]")
+        rows = None
+        if configs is not None or tunables is not None:
+            if configs is not None and tunables is not None:
+                raise ValueError("give configs or tunables, not both")
+            rows = pack_tunables(self, configs) if configs is not None else np.ascontiguousarray(tunables, dtype=np.float64)
+            if rows.shape != (B, L.TUNE_SIZE):
+                raise ValueError(f"one configuration / one row of {L.TUNE_SIZE} tunables per instance ({B})")
+        y = np.empty((B, self.n_con)) if duals else None
+        cert = np.empty((B, L.CERT_SIZE))
+        _lib.check(self.lib.vsmpc_certify_batch(self._h, _ptr(records), _ptr(x), _ptr(rows), B, _ptr(y), _ptr(cert)),
+                   "vsmpc_certify_batch")
+        return y, cert
+
+    def certify_device(self, d_in, d_x, d_tun, d_y, d_cert, stream=None):
+        """vsmpc_certify_batch_device: torch CUDA tensors (d_tun and d_y may be None), enqueue only; needs no
+        construction flag"""
+        import torch
+        for t in (d_in, d_x, d_tun, d_y, d_cert):
+            assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
+
+        def p(t):
+            return None if t is None else ctypes.c_void_p(t.data_ptr())
+        _lib.check(self.lib.vsmpc_certify_batch_device(self._h, p(d_in), p(d_x), p(d_tun), d_in.shape[0], p(d_y), p(d_cert),
+                                                       ctypes.c_void_p(s.cuda_stream)), "vsmpc_certify_batch_device")
 
     # ---- sensitivities of the solution to X0 (vsmpc_sensitivity_batch); needs sensitivity=True at construction
     def solve_sensitivity(self, inputs: np.ndarray, jacobian: bool = True) -> dict:
