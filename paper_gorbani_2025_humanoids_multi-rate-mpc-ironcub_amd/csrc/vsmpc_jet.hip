@@ -188,10 +188,10 @@ const char* vsmpc_jet_last_error(void) { return g_jet_msg; }
 
 int vsmpc_jet_create(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* fc_w,
                      const float* fc_b, const double* norm, int hidden, int device, int max_series, vsmpc_jet** out) {
+    if (out) *out = nullptr;               // a refused create leaves no stale handle behind
     if (!w_ih || !w_hh || !b_ih || !b_hh || !fc_w || !fc_b || !norm || !out || hidden <= 0 || hidden > JET_HMAX ||
         max_series <= 0 || !(norm[1] > 0.0) || !(norm[3] > 0.0))
         return invalid_arg();
-    *out = nullptr;
     int ndev = 0;
     JET_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return invalid_arg();
@@ -333,7 +333,7 @@ int vsmpc_jet_plant_run_device(vsmpc_jet* j, float* d_T_nn, double* d_x_est, dou
 
 int vsmpc_jet_plant_run(vsmpc_jet* j, float* T_nn, double* x_est, double* P, const float* throttle, int throttle_steps,
                         int n, int steps, double dt, const double* Q, const double* R, double* log) {
-    if (!j || !T_nn || !x_est || !P || !throttle || !Q || !R || n < 0 || steps < 0 ||
+    if (!j || !T_nn || !x_est || !P || !throttle || !Q || !R || n < 0 || steps < 0 || !(dt > 0.0) ||
         (throttle_steps != 1 && throttle_steps != steps))
         return invalid_arg();
     if (n > j->max_series) return VSMPC_ERR_BATCH_TOO_LARGE;
