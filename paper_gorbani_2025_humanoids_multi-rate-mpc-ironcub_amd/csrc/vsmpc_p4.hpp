@@ -4,6 +4,23 @@
 
 namespace vsmpc {
 
+// Measurement build (-DVS_DIAG_QP, diagnostic instantiation only): the box QP of the dual form in four parts, cycles of
+// wavefront 0 added up in qt[0..3] = set-up / columns of P / system solves / updates and checks (tools/qp_tail.py).
+#ifdef VS_DIAG_QP
+#define VS_QP_TIC() do { if (qt != nullptr) qt_mark = __builtin_amdgcn_s_memtime(); } while (0)
+#define VS_QP_TOC(i)                                                   \
+    do {                                                               \
+        if (qt != nullptr) {                                           \
+            const unsigned long long qt_now = __builtin_amdgcn_s_memtime(); \
+            qt[i] += qt_now - qt_mark;                                 \
+            qt_mark = qt_now;                                          \
+        }                                                              \
+    } while (0)
+#else
+#define VS_QP_TIC() do { } while (0)
+#define VS_QP_TOC(i) do { } while (0)
+#endif
+
 // ------------------------------------------------------------------------------------------------
 // K x K symmetric positive definite system (P_AA mu = rhs_A of the dual box QP, S_FF v_F = b_F of the primal), K <= 12, all lanes redundantly on
 // wave-uniform values (symmetric elimination on the lower triangle).  sP[b * NVS + i] = P[i][b]; the K set bits of
@@ -88,7 +105,8 @@ VS_DEV void schur_rhs(const double* __restrict__ Lb, double* __restrict__ sSvec,
 // used instead of held in 2 NV registers: with the accumulator tiles live through P4 the box QP must stay small in
 // registers, or tiles get spilled for EVERY instance.
 //   XTiles  two throttle tile rows (the paper horizon): rows 0..15 are the tile X6 = inverse of the first throttle
-//           diagonal tile (formed in P3), rows 16.. are formed at the top of the box QP (sXr[a * NVS + j] = X[16 + a][j])
+//           diagonal tile (formed in P3), rows 16.. are formed beside the throttle sweep (dual_setup_beside_sweep) and, for
+//           their first sixteen columns, at the top of the box QP (sXr[a * NVS + j] = X[16 + a][j])
 //   XDense  three throttle tile rows: sXd[j * NVS + i] = X[j][i], zero above the diagonal
 // col(j, r, n) = X[j][r] restricted to the rows j < n of N; pcol(b, r, n) = P[r][b] = sum_{j < n} X[j][r] X[j][b].
 // ------------------------------------------------------------------------------------------------
@@ -191,6 +209,83 @@ VS_DEV double mid_spd_solve(int ka, const double* __restrict__ sP, unsigned long
     return mu;
 }
 
+// orders this wavefront's LDS stores before its later LDS loads of other lanes' words, for the compiler (the hardware executes a
+// wavefront's LDS operations in order: no instruction)
+VS_DEV void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Set-up of the dual form at two throttle tile rows, by wavefronts 1..3 BESIDE wavefront 0's throttle sweep (P4a), for
+// every instance: all of its inputs (the corner tiles, X66, 1/diagonal, row NZ of the factor) are final when P3 ends, its
+// outputs lie in arrays that nothing else touches before P5, and the three wavefronts have nothing else to do there.
+//   wavefront 1   T = L76 X66 (NR2 x 16)                    -> sT (head of sQP, dead before the copy of P_AA is used)
+//   wavefront 2   X77 = L77^-1, one column per lane          -> sXr[a * NVS + 16 + c] = X[16 + a][16 + c]
+//   wavefront 3   s = L22 (L^-1 g)_v -> sSvec, then max |s|  -> sSvec[0]
+// No workgroup barrier (wavefront 0 must not wait) and no value crosses from one wavefront to another in here: the barrier
+// behind the violation check publishes everything.  The one product that needs two of the pieces, X76 = -X77 T, is
+// left to box_qp (NR2 multiply-adds per thread and one barrier, for the instances that enter): a wavefront that forms
+// more than one piece outlasts the sweep, and then every instance waits for it.  Same expressions and summation orders
+// as when all of this ran at the top of box_qp (through v33): the values are bit-identical.
+// ------------------------------------------------------------------------------------------------
+template <class D>
+VS_DEV void dual_setup_beside_sweep(int wave, int lane) {
+    using S = Smem<D>;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int PV = D::PVT, NVS = D::NV + 1, NR2 = D::NV - 16;
+    static_assert(S::DUALQP && NR2 >= 1 && NR2 <= 16, "two throttle tile rows");
+    double* Lb = smem + S::oM;
+    double* sQP = smem + S::oQP;
+    double* sXr = sQP + D::NV * NVS;                              // sXr[a * NVS + j] = X[16 + a][j]
+    double* sT = sQP;                                             // T = L76 X66, NR2 x 16 (dead before sK is used)
+    if (wave == 1) {
+        const double* X6 = smem + S::oXinv + PV * D::TS;
+        const double* L76 = Lb + tile_off<D>(PV + 1, PV);
+        constexpr int RND = (16 * NR2 + 63) / 64;
+#pragma unroll
+        for (int rd = 0; rd < RND; ++rd) {
+            const int e = lane + 64 * rd;
+            if (e < 16 * NR2) {
+                const int a2 = e >> 4, j = e & 15;
+                double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+                for (int k = 0; k < 16; k += 2) {                     // X66[k][j] = 0 for k < j (stored zeros)
+                    t0 = fma(L76[a2 * 17 + k], X6[k * 17 + j], t0);
+                    t1 = fma(L76[a2 * 17 + k + 1], X6[(k + 1) * 17 + j], t1);
+                }
+                sT[a2 * 16 + j] = t0 + t1;
+            }
+        }
+    } else if (wave == 2) {
+        const double* sInvD = smem + S::oInvD;
+        const double* L77 = Lb + tile_off<D>(PV + 1, PV + 1);
+        if (lane < NR2) {
+            const int c = lane;                                       // column c of X77 = L77^-1
+            double x[NR2];
+#pragma unroll
+            for (int i = 0; i < NR2; ++i) {
+                double sum = 0.0;
+#pragma unroll
+                for (int k = 0; k < i; ++k) sum = fma(L77[i * 17 + k], (k >= c) ? x[k] : 0.0, sum);
+                const double di = sInvD[D::NU + 16 + i];
+                x[i] = (i == c) ? di : ((i > c) ? -di * sum : 0.0);
+                sXr[i * NVS + 16 + c] = x[i];
+            }
+        }
+    } else {
+        double* sSvec = smem + S::oSvec;
+        schur_rhs<D>(Lb, sSvec, lane);
+        wave_lds_sync();
+        double gm = 0.0;
+#pragma unroll
+        for (int c = 0; c < D::NV; ++c) gm = fmax(gm, fabs(sSvec[c]));  // uniform addresses: LDS broadcasts
+        wave_lds_sync();
+        if (lane == 0) sSvec[0] = gm;   // every lane of this wavefront has read sSvec[0] (in-order LDS)
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Dual active-set iteration of the box QP by ONE wavefront (lane = throttle).  With N = the throttles that are not
 // pinned by the hold, P = S_NN^-1 = X^T X and v_u = the sweep's solution (sZ), fixing the set A at its bounds b_A gives
@@ -202,7 +297,10 @@ template <class D, class XA>
 VS_DEV void dual_active_set(const XA& xa, bool hold, int lane, double* __restrict__ sSv, double* __restrict__ sQP,
                             const double* __restrict__ sSvec, const double* __restrict__ sVprev,
                             const double* __restrict__ sCfg, double* __restrict__ sZ, int* __restrict__ sFlags,
-                            unsigned long long have0 = 0ull) {
+                            unsigned long long have0 = 0ull, unsigned long long* qt = nullptr) {
+    unsigned long long qt_mark = 0;
+    (void)qt; (void)qt_mark;
+    VS_QP_TIC();
     constexpr int NVS = D::NV + 1;          // row stride of the LDS work arrays
     double* sP = sSv;                       // sP[b * NVS + i] = P[i][b] for the columns b formed so far (have0: on entry)
     double* sK = sQP;                       // working copy of P_AA
@@ -242,6 +340,7 @@ VS_DEV void dual_active_set(const XA& xa, bool hold, int lane, double* __restric
             const double pb = xa.pcol(b, r, n);
             if (valid) sP[b * NVS + r] = pb;
         }
+        VS_QP_TOC(1);
         double bb = isA ? vu - (state < 0 ? lo : hi) : 0.0;  // right-hand side v_u,A - b_A
         double mu = 0.0;
         const int ka = __popcll(Amask);
@@ -284,6 +383,7 @@ VS_DEV void dual_active_set(const XA& xa, bool hold, int lane, double* __restric
                 if (isA && lane < j) bb -= sK[r * NVS + j] * xj;
             }
         }
+        VS_QP_TOC(2);
         if (bad) { status = VSMPC_STATUS_NUMERICAL; break; }
         // v_N = v_u,N - P[:,A] mu
         v = vu;
@@ -308,7 +408,9 @@ VS_DEV void dual_active_set(const XA& xa, bool hold, int lane, double* __restric
         else if (patience > 0) { --patience; }
         else { pick = inf && (lane == 63 - __clzll(imask)); }  // least-index fallback (largest index)
         if (pick) state = vlo ? -1 : (vhi ? 1 : 0);
+        VS_QP_TOC(3);
     }
+    VS_QP_TOC(3);
     if (valid) {
         v = fixed ? lo : (state < 0 ? lo : (state > 0 ? hi : v));  // bound variables sit exactly on their bound
         sZ[D::NU + lane] = v;
@@ -323,9 +425,18 @@ VS_DEV void dual_active_set(const XA& xa, bool hold, int lane, double* __restric
 // real call it costs the slowest instance of a launch ~4 us in saved / restored registers.)  Few saturated throttles (the usual case): dual
 // form, cost grows with the number of active bounds; many: primal form on the Schur complement, cost grows with the
 // number of free throttles.  Called by all wavefronts (it contains workgroup barriers); result in sZ[NU..NZ), sFlags.
+// Two throttle tile rows (the paper horizon): the pieces of the dual form's set-up -- T = L76 X66, X77, s, max |s| -- are NOT
+// formed here: wavefronts 1..3 form them beside the throttle sweep of every instance (dual_setup_beside_sweep); an instance
+// that does enter has one product (X76 = -X77 T) and one barrier in front of the columns of P.  sFlags[4] = which
+// throttles the sweep left outside their box (that form only): for two to four of them the columns of P are formed one
+// per wavefront behind one barrier; one column is formed by wavefront 0 without a barrier; more than four take all
+// columns up front.
 // ------------------------------------------------------------------------------------------------
 template <class D>
-VS_DEV void box_qp(int n_violated, bool hold, int wave) {
+VS_DEV void box_qp(int n_violated, bool hold, int wave, unsigned long long* qt = nullptr) {
+    unsigned long long qt_mark = 0;
+    (void)qt; (void)qt_mark;
+    VS_QP_TIC();
     using S = Smem<D>;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     double* sVprev = smem + S::oVprev;
@@ -353,53 +464,16 @@ VS_DEV void box_qp(int n_violated, bool hold, int wave) {
         // (S = L22 L22^T, so the factor of S_NN is the leading block of L22) and v_u = the sweep's solution, fixing the
         // set A at its bounds b_A gives  mu = P_AA^-1 (v_u,A - b_A),  v_N = v_u,N - P[:,A] mu,  gradient_A = -mu.
         // P = X^T X with X = L22^-1: rows 0..15 of X are the inverse of the first throttle diagonal tile (formed by an
-        // idle wavefront during P3), the remaining rows are formed here; a column of P then is 24 multiply-adds per
-        // lane with no chain, and only the columns some active set needs are ever formed.  The |A| x |A| system is
+        // idle wavefront during P3), the remaining rows are started beside the throttle sweep and finished below; a
+        // column of P then is 24 multiply-adds per lane with no chain, and only the columns some active set needs are ever formed.  The |A| x |A| system is
         // tiny for the usual one to three saturated throttles.  The sequence of active sets is exactly the
         // block-pivoting sequence of the primal form.
         {
-            // second tile row of X by all wavefronts:  [X76 | X77] = [-X77 (L76 X66) | L77^-1]
+            // what is left of the set-up: X76 = -X77 T from the two pieces wavefronts 1 and 2 formed beside the sweep
             constexpr int NVS = D::NV + 1, NR2 = D::NV - 16;
             double* sXr = sQP + D::NV * NVS;                              // sXr[a * NVS + j] = X[16 + a][j]
-            double* sT = sQP;                                             // T = L76 X66, NR2 x 16 (dead before sK is used)
-            const double* X6 = sXinv + PV * D::TS;
-            const double* L76 = Lb + tile_off<D>(PV + 1, PV);
-            const double* L77 = Lb + tile_off<D>(PV + 1, PV + 1);
-            // threads of the columns of X77: behind the 16 NR2 threads of T where that leaves wavefront 3 alone (it forms the
-            // right-hand side meanwhile), else the upper lanes of wavefront 3 (throttle blocks of more than 24: both run there)
-            constexpr int XT0 = 17 * NR2 <= 192 ? 16 * NR2 : 224;
-            static_assert(XT0 + NR2 <= D::BLOCK && D::NV <= 32, "threads of the X77 columns");
-            if (tid < 16 * NR2) {
-                const int a2 = tid >> 4, j = tid & 15;
-                double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-                for (int k = 0; k < 16; k += 2) {                         // X66[k][j] = 0 for k < j (stored zeros)
-                    t0 = fma(L76[a2 * 17 + k], X6[k * 17 + j], t0);
-                    t1 = fma(L76[a2 * 17 + k + 1], X6[(k + 1) * 17 + j], t1);
-                }
-                sT[a2 * 16 + j] = t0 + t1;
-            } else if (tid >= XT0 && tid < XT0 + NR2) {
-                const int c = tid - XT0;                                  // column c of X77 = L77^-1
-                double x[NR2];
-#pragma unroll
-                for (int i = 0; i < NR2; ++i) {
-                    double sum = 0.0;
-#pragma unroll
-                    for (int k = 0; k < i; ++k) sum = fma(L77[i * 17 + k], (k >= c) ? x[k] : 0.0, sum);
-                    const double di = sInvD[D::NU + 16 + i];
-                    x[i] = (i == c) ? di : ((i > c) ? -di * sum : 0.0);
-                    sXr[i * NVS + 16 + c] = x[i];
-                }
-            } else if (wave == 3) {
-                schur_rhs<D>(Lb, sSvec, lane);
-            }
-            __syncthreads();
-            if (wave == 3) {  // max |s| while wavefronts 0..1 finish X (keeps it off wavefront 0's path)
-                double gm = 0.0;
-#pragma unroll
-                for (int c = 0; c < D::NV; ++c) gm = fmax(gm, fabs(sSvec[c]));  // uniform addresses: LDS broadcasts
-                if (lane == 0) sSvec[0] = gm;   // every lane of this wavefront has read sSvec[0] (in-order LDS)
-            }
+            const double* sT = sQP;                                       // T = L76 X66, NR2 x 16 (dead before sK is used)
+            static_assert(16 * NR2 <= D::BLOCK, "one entry of X76 per thread");
             if (tid < 16 * NR2) {
                 const int a2 = tid >> 4, j = tid & 15;
                 double t = 0.0;
@@ -409,12 +483,17 @@ VS_DEV void box_qp(int n_violated, bool hold, int wave) {
             }
             __syncthreads();
         }
+        VS_QP_TOC(0);
         static_assert(D::NU % 16 == 0 && D::NV > 16 && D::NV <= 32, "throttle block: tile aligned, two tile rows");
         const XTiles<D> xa{sXinv + PV * D::TS, sQP + D::NV * (D::NV + 1)};   // rows 16.. of X behind the copy of P_AA
         // Many violated bounds (the take-off instances enter with ten to sixteen): all columns of P up front, by all four
         // wavefronts -- 2.25 of them per thread, ~1 k cycles -- instead of one by one in the wavefront that iterates (~0.43 k each:
         // profiles/r04_v27_qp_dist_paper.txt, 24.6 k cycles for a two-iteration solve).  Same expression, same sums.
         const bool all_cols = n_violated > 4;   // workgroup-uniform
+        // Two to four: the columns of the first active set (sFlags[4]: the throttles the sweep left outside their box), one
+        // per wavefront, instead of one after the other in wavefront 0 while the other three wait.  Same expression, same sums.
+        // (A single one stays where it was: wavefront 0 forms it without a barrier.)
+        const bool first_cols = !all_cols && n_violated >= 2;   // workgroup-uniform
         if (all_cols) {
             const int n = hold ? D::NV - 4 : D::NV;
             for (int e = tid; e < D::NV * D::NV; e += D::BLOCK) {
@@ -422,9 +501,23 @@ VS_DEV void box_qp(int n_violated, bool hold, int wave) {
                 sSv[b * (D::NV + 1) + r] = xa.pcol(b, r, n);
             }
             __syncthreads();
+        } else if (first_cols) {
+            const int n = hold ? D::NV - 4 : D::NV;
+            unsigned m = unsigned(sFlags[4]);            // the violation check's mask (NV <= 32 bits)
+            for (int q = 0; q < wave; ++q) m &= m - 1;   // wavefront w takes the w-th violated throttle
+            if (m) {
+                const int b = __ffs(int(m)) - 1;
+                const int r = lane < D::NV ? lane : D::NV - 1;
+                const double pb = xa.pcol(b, r, n);
+                if (lane < D::NV) sSv[b * (D::NV + 1) + r] = pb;
+            }
+            __syncthreads();
         }
+        VS_QP_TOC(1);
         if (wave == 0)
-            dual_active_set<D>(xa, hold, lane, sSv, sQP, sSvec, sVprev, sCfg, sZ, sFlags, all_cols ? ((1ull << D::NV) - 1ull) : 0ull);
+            dual_active_set<D>(xa, hold, lane, sSv, sQP, sSvec, sVprev, sCfg, sZ, sFlags,
+                               all_cols ? ((1ull << D::NV) - 1ull) : (first_cols ? (unsigned long long)unsigned(sFlags[4]) : 0ull),
+                               qt);
        }
       } else if (few && DUAL3) {
        if constexpr (DUAL3) {
@@ -674,5 +767,8 @@ VS_DEV void box_qp(int n_violated, bool hold, int wave) {
         }
       }
 }
+
+#undef VS_QP_TIC
+#undef VS_QP_TOC
 
 }  // namespace vsmpc

@@ -61,6 +61,8 @@ struct Smem {
     static constexpr int oDt = oV + D::NV;           // per-stage dt (copied out of the kernel arguments once)
     static constexpr int oCfg = oDt + MAX_STAGES;    // configuration scalars (CFG_* offsets)
     static constexpr int oFlags = oCfg + CFG_SIZE;   // 4 doubles worth of int flags
+    static constexpr int NFLAGS = 5;                 // [0] numerical failure, [1] status, [2] iterations, [3] bounds violated, [4] which
+    static_assert(NFLAGS * sizeof(int) <= 4 * sizeof(double), "the int flags fit their four doubles (oQR follows)");
     // X_p = L_pp^-1 of the joint diagonal tiles and of the first throttle tile, produced by wavefronts that idle
     // during the panel factorisations of P3
     // joint reduction (p0_joint_reduction): the six Householder vectors, their betas, the reduced gradient Q^T b, the null

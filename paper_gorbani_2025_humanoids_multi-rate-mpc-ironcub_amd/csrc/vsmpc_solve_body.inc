@@ -50,7 +50,7 @@
     double* sF = smem + S::oF;
     double* sDt = smem + S::oDt;
     double* sCfg = smem + S::oCfg;
-    int* sFlags = reinterpret_cast<int*>(smem + S::oFlags);  // [0] numerical failure, [1] status, [2] iters, [3] bound violated
+    int* sFlags = reinterpret_cast<int*>(smem + S::oFlags);  // [0] numerical failure, [1] status, [2] iters, [3] bound violated, [4] which
     double* sY = smem + S::oY;
     double* Lb = smem + S::oM;        // tile storage: ring of two panel columns + throttle corner (see Dims)
     double* sXinv = smem + S::oXinv;  // inverses of the joint diagonal tiles and of the first throttle tile
@@ -679,6 +679,11 @@
 #pragma unroll
             for (int i = 0; i < 16; ++i) z6 = fma(x6[i], readlane_f64(w6, i), z6);
             if (lane < 16) { sZ[gj] = z; sZ[16 * PV + j] = z6; }
+        } else {
+            // wavefronts 1..3 meanwhile: the pieces of the dual box QP's set-up (T, X77, s and max |s|), for every instance -- its
+            // inputs are final since P3 and its arrays (sQP, sSvec) are not used by anything else before P5.  No barrier
+            // inside: the one behind the violation check publishes it.
+            dual_setup_beside_sweep<D>(wave, lane);
         }
         // (no barrier here: the only reader of these throttles before the next barrier is the violation check below, in this
         // same wavefront -- LDS operations of one wavefront execute in order)
@@ -741,14 +746,24 @@
         const bool viol = valid && !fixed && (v < sCfg[CFG_VMIN] - tolv || v > sCfg[CFG_VMAX] + tolv);
         const unsigned long long vm = __ballot(viol);
         if (lane == 0) { sFlags[3] = __popcll(vm); sFlags[1] = VSMPC_STATUS_SOLVED; sFlags[2] = 1; }
+        if constexpr (DUALQP) {   // which ones: the first active set of the box QP, whose columns of P all wavefronts form
+            if (lane == 0) sFlags[4] = int(unsigned(vm));
+        }
     }
     __syncthreads();
     const bool need_qp = sFlags[3] != 0;
     VS_STAMP(5);
     VS_REFRESH_IDS();
 
+#ifdef VS_DIAG_QP   // measurement build: the box QP in four parts -> t_acc[0..3] (see vsmpc_p4.hpp)
+    for (int i = 0; i < 4; ++i) t_acc[i] = 0;
+#endif
     if (need_qp) {
+#ifdef VS_DIAG_QP
+        box_qp<D>(sFlags[3], hold, wave, STAMPS ? t_acc : nullptr);
+#else
         box_qp<D>(sFlags[3], hold, wave);
+#endif
         __syncthreads();
         VS_STAMP(6);
         VS_REFRESH_IDS();
