@@ -17,8 +17,8 @@
 
 #include "vsmpc_device.hpp"
 #include "vsmpc_jet_device.hpp"
-#include "vsmpc_launch.hpp"
-#include "../../include/vsmpc_jet.h"
+#define VSMPC_HIP_FAIL jet_fail   // HIP_TRY reports through vsmpc_jet_last_error, not vsmpc_strerror
+#include "vsmpc_host.hpp"
 
 namespace vsmpc {
 
@@ -143,28 +143,21 @@ using namespace vsmpc;
 struct vsmpc_jet {
     int device, hidden, max_series;
     JetNorm nm;
-    float* d_w;      // wih col 0 [4H] | wih col 1 [4H] | b_ih [4H] | b_hh [4H] | fc_w [H] | fc_b
-    float* d_whhT;   // [H][4H]
-    float *d_f0, *d_f1, *d_f2, *d_f3;   // float staging, max_series each
-    float *d_h, *d_c;                    // [max_series][H]
-    double *d_x, *d_P, *d_u, *d_z;       // EKF staging
-    double* d_log;
+    DevBuf<float> d_w;      // wih col 0 [4H] | wih col 1 [4H] | b_ih [4H] | b_hh [4H] | fc_w [H] | fc_b
+    DevBuf<float> d_whhT;   // [H][4H]
+    DevBuf<float> d_f0, d_f1, d_f2, d_f3;   // float staging, max_series each
+    DevBuf<float> d_h, d_c;                 // [max_series][H]
+    DevBuf<double> d_x, d_P, d_u, d_z;      // EKF staging
+    DevBuf<double> d_log;
     size_t log_doubles;
-    float* d_thr_steps;
+    DevBuf<float> d_thr_steps;
     size_t thr_floats;
 };
 
 namespace {
 thread_local char g_jet_msg[256] = "";
-int jet_fail(hipError_t e, const char* what) {
-    snprintf(g_jet_msg, sizeof(g_jet_msg), "HIP error in %s: %s", what, hipGetErrorString(e));
-    return VSMPC_ERR_HIP;
-}
-#define JET_TRY(expr)                                     \
-    do {                                                  \
-        hipError_t _e = (expr);                           \
-        if (_e != hipSuccess) return jet_fail(_e, #expr); \
-    } while (0)
+int jet_fail(hipError_t e, const char* what) { return hip_fail_into(g_jet_msg, e, what); }
+static_assert(&VSMPC_HIP_FAIL == &jet_fail, "vsmpc_host.hpp was included before VSMPC_HIP_FAIL was set");
 
 Ekf2 make_cov(const double* Q, const double* R) {
     Ekf2 cv;
@@ -193,12 +186,11 @@ int vsmpc_jet_create(const float* w_ih, const float* w_hh, const float* b_ih, co
         max_series <= 0 || !(norm[1] > 0.0) || !(norm[3] > 0.0))
         return invalid_arg();
     int ndev = 0;
-    JET_TRY(hipGetDeviceCount(&ndev));
+    HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return invalid_arg();
-    vsmpc::DeviceScope _scope(device); JET_TRY(_scope.err);
+    ON_DEVICE(device);
     vsmpc_jet* j = new (std::nothrow) vsmpc_jet();
     if (!j) return VSMPC_ERR_ALLOC;
-    *j = vsmpc_jet{};
     j->device = device;
     j->hidden = hidden;
     j->max_series = max_series;
@@ -218,21 +210,19 @@ int vsmpc_jet_create(const float* w_ih, const float* w_hh, const float* b_ih, co
     for (int r = 0; r < 4 * H; ++r)
         for (int k = 0; k < H; ++k) hT[size_t(k) * 4 * H + r] = w_hh[size_t(r) * H + k];
     const size_t S = size_t(max_series);
-    hipError_t e = hipMalloc(&j->d_w, (17 * H + 1) * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&j->d_whhT, size_t(H) * 4 * H * sizeof(float));
+    hipError_t e = j->d_w.alloc(17 * H + 1);
+    if (e == hipSuccess) e = j->d_whhT.alloc(size_t(H) * 4 * H);
     if (e == hipSuccess) e = hipMemcpy(j->d_w, hw, (17 * H + 1) * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(j->d_whhT, hT, size_t(H) * 4 * H * sizeof(float), hipMemcpyHostToDevice);
     delete[] hw;
-    if (e == hipSuccess) e = hipMalloc(&j->d_f0, S * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&j->d_f1, S * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&j->d_f2, S * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&j->d_f3, S * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&j->d_h, S * H * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&j->d_c, S * H * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&j->d_x, S * 2 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&j->d_P, S * 4 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&j->d_u, S * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&j->d_z, S * 2 * sizeof(double));
+    for (DevBuf<float>* f : {&j->d_f0, &j->d_f1, &j->d_f2, &j->d_f3})
+        if (e == hipSuccess) e = f->alloc(S);
+    if (e == hipSuccess) e = j->d_h.alloc(S * H);
+    if (e == hipSuccess) e = j->d_c.alloc(S * H);
+    if (e == hipSuccess) e = j->d_x.alloc(S * 2);
+    if (e == hipSuccess) e = j->d_P.alloc(S * 4);
+    if (e == hipSuccess) e = j->d_u.alloc(S);
+    if (e == hipSuccess) e = j->d_z.alloc(S * 2);
     if (e != hipSuccess) {
         vsmpc_jet_destroy(j);
         return e == hipErrorOutOfMemory ? VSMPC_ERR_ALLOC : jet_fail(e, "vsmpc_jet_create");
@@ -244,11 +234,7 @@ int vsmpc_jet_create(const float* w_ih, const float* w_hh, const float* b_ih, co
 void vsmpc_jet_destroy(vsmpc_jet* j) {
     if (!j) return;
     vsmpc::DeviceScope _scope(j->device);
-    void* ptrs[] = {j->d_w, j->d_whhT, j->d_f0, j->d_f1, j->d_f2, j->d_f3, j->d_h, j->d_c, j->d_x, j->d_P, j->d_u, j->d_z,
-                    j->d_log, j->d_thr_steps};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    delete j;
+    delete j;   // the owners free on the current device
 }
 
 int vsmpc_jet_nn_step(vsmpc_jet* j, const float* thrust, const float* throttle, int n, float dt, float* T_next,
@@ -256,18 +242,19 @@ int vsmpc_jet_nn_step(vsmpc_jet* j, const float* thrust, const float* throttle, 
     if (!j || !thrust || !throttle || !T_next || !T_dot || n < 0) return invalid_arg();
     if (n > j->max_series) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (n == 0) return VSMPC_OK;
-    vsmpc::DeviceScope _scope(j->device); JET_TRY(_scope.err);
+    ON_DEVICE(j->device);
     const size_t N = size_t(n);
-    JET_TRY(hipMemcpy(j->d_f0, thrust, N * sizeof(float), hipMemcpyHostToDevice));
-    JET_TRY(hipMemcpy(j->d_f1, throttle, N * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(jet_nn_step_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, j->d_w, j->hidden, j->nm, j->d_f0,
-                       j->d_f1, n, dt, j->d_f2, j->d_f3, h_out ? j->d_h : nullptr, c_out ? j->d_c : nullptr);
-    JET_TRY(hipGetLastError());
-    JET_TRY(hipDeviceSynchronize());
-    JET_TRY(hipMemcpy(T_next, j->d_f2, N * sizeof(float), hipMemcpyDeviceToHost));
-    JET_TRY(hipMemcpy(T_dot, j->d_f3, N * sizeof(float), hipMemcpyDeviceToHost));
-    if (h_out) JET_TRY(hipMemcpy(h_out, j->d_h, N * j->hidden * sizeof(float), hipMemcpyDeviceToHost));
-    if (c_out) JET_TRY(hipMemcpy(c_out, j->d_c, N * j->hidden * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(j->d_f0, thrust, N * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(j->d_f1, throttle, N * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(jet_nn_step_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, j->d_w.get(), j->hidden, j->nm,
+                       j->d_f0.get(), j->d_f1.get(), n, dt, j->d_f2.get(), j->d_f3.get(), h_out ? j->d_h : nullptr,
+                       c_out ? j->d_c : nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(T_next, j->d_f2, N * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(T_dot, j->d_f3, N * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_out) HIP_TRY(hipMemcpy(h_out, j->d_h, N * j->hidden * sizeof(float), hipMemcpyDeviceToHost));
+    if (c_out) HIP_TRY(hipMemcpy(c_out, j->d_c, N * j->hidden * sizeof(float), hipMemcpyDeviceToHost));
     return VSMPC_OK;
 }
 
@@ -276,24 +263,24 @@ int vsmpc_jet_nn_sequence(vsmpc_jet* j, const float* x, int n, int L, float dt, 
     if (!j || !x || !T_next_norm || !T_dot_norm || n < 0 || L <= 0) return invalid_arg();
     if (n > j->max_series) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (n == 0) return VSMPC_OK;
-    vsmpc::DeviceScope _scope(j->device); JET_TRY(_scope.err);
-    float* d_x = nullptr;                       // sequences are a parity / offline entry: sized per call
-    JET_TRY(hipMalloc(&d_x, size_t(n) * L * 2 * sizeof(float)));
+    ON_DEVICE(j->device);
+    DevBuf<float> d_x;                          // sequences are a parity / offline entry: sized per call
+    HIP_TRY(d_x.alloc(size_t(n) * L * 2));
     hipError_t e = hipMemcpy(d_x, x, size_t(n) * L * 2 * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const int threads = ((j->hidden + 63) / 64) * 64;
-        hipLaunchKernelGGL(jet_nn_sequence_kernel, dim3(n), dim3(threads), 0, nullptr, j->d_w, j->d_whhT, j->hidden, d_x, n, L,
-                           dt, j->d_f2, j->d_f3, h_n ? j->d_h : nullptr, c_n ? j->d_c : nullptr);
+        hipLaunchKernelGGL(jet_nn_sequence_kernel, dim3(n), dim3(threads), 0, nullptr, j->d_w.get(), j->d_whhT.get(), j->hidden,
+                           d_x.get(), n, L, dt, j->d_f2.get(), j->d_f3.get(), h_n ? j->d_h : nullptr, c_n ? j->d_c : nullptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(d_x);
+    d_x.reset();
     if (e != hipSuccess) return jet_fail(e, "vsmpc_jet_nn_sequence");
     const size_t N = size_t(n);
-    JET_TRY(hipMemcpy(T_next_norm, j->d_f2, N * sizeof(float), hipMemcpyDeviceToHost));
-    JET_TRY(hipMemcpy(T_dot_norm, j->d_f3, N * sizeof(float), hipMemcpyDeviceToHost));
-    if (h_n) JET_TRY(hipMemcpy(h_n, j->d_h, N * j->hidden * sizeof(float), hipMemcpyDeviceToHost));
-    if (c_n) JET_TRY(hipMemcpy(c_n, j->d_c, N * j->hidden * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(T_next_norm, j->d_f2, N * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(T_dot_norm, j->d_f3, N * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_n) HIP_TRY(hipMemcpy(h_n, j->d_h, N * j->hidden * sizeof(float), hipMemcpyDeviceToHost));
+    if (c_n) HIP_TRY(hipMemcpy(c_n, j->d_c, N * j->hidden * sizeof(float), hipMemcpyDeviceToHost));
     return VSMPC_OK;
 }
 
@@ -302,18 +289,18 @@ int vsmpc_jet_ekf_update(vsmpc_jet* j, double* x, double* P, const double* u, co
     if (!j || !x || !P || !u || !z || !Q || !R || n < 0 || !(dt > 0.0)) return invalid_arg();
     if (n > j->max_series) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (n == 0) return VSMPC_OK;
-    vsmpc::DeviceScope _scope(j->device); JET_TRY(_scope.err);
+    ON_DEVICE(j->device);
     const size_t N = size_t(n);
-    JET_TRY(hipMemcpy(j->d_x, x, N * 2 * sizeof(double), hipMemcpyHostToDevice));
-    JET_TRY(hipMemcpy(j->d_P, P, N * 4 * sizeof(double), hipMemcpyHostToDevice));
-    JET_TRY(hipMemcpy(j->d_u, u, N * sizeof(double), hipMemcpyHostToDevice));
-    JET_TRY(hipMemcpy(j->d_z, z, N * 2 * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(jet_ekf_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, j->d_x, j->d_P, j->d_u, j->d_z, n, dt,
-                       make_cov(Q, R));
-    JET_TRY(hipGetLastError());
-    JET_TRY(hipDeviceSynchronize());
-    JET_TRY(hipMemcpy(x, j->d_x, N * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    JET_TRY(hipMemcpy(P, j->d_P, N * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(j->d_x, x, N * 2 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(j->d_P, P, N * 4 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(j->d_u, u, N * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(j->d_z, z, N * 2 * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(jet_ekf_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, j->d_x.get(), j->d_P.get(), j->d_u.get(),
+                       j->d_z.get(), n, dt, make_cov(Q, R));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(x, j->d_x, N * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(P, j->d_P, N * 4 * sizeof(double), hipMemcpyDeviceToHost));
     return VSMPC_OK;
 }
 
@@ -324,10 +311,10 @@ int vsmpc_jet_plant_run_device(vsmpc_jet* j, float* d_T_nn, double* d_x_est, dou
         (throttle_steps != 1 && throttle_steps != steps))
         return invalid_arg();
     if (n == 0 || steps == 0) return VSMPC_OK;
-    vsmpc::DeviceScope _scope(j->device); JET_TRY(_scope.err);
-    hipLaunchKernelGGL(jet_plant_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), j->d_w,
+    ON_DEVICE(j->device);
+    hipLaunchKernelGGL(jet_plant_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), j->d_w.get(),
                        j->hidden, j->nm, d_T_nn, d_x_est, d_P, d_throttle, throttle_steps, n, steps, dt, make_cov(Q, R), d_log);
-    JET_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return VSMPC_OK;
 }
 
@@ -338,35 +325,31 @@ int vsmpc_jet_plant_run(vsmpc_jet* j, float* T_nn, double* x_est, double* P, con
         return invalid_arg();
     if (n > j->max_series) return VSMPC_ERR_BATCH_TOO_LARGE;
     if (n == 0 || steps == 0) return VSMPC_OK;
-    vsmpc::DeviceScope _scope(j->device); JET_TRY(_scope.err);
+    ON_DEVICE(j->device);
     const size_t N = size_t(n), TS = size_t(throttle_steps) * N;
     if (TS > j->thr_floats) {              // grows only when a longer schedule than ever before is passed
-        if (j->d_thr_steps) (void)hipFree(j->d_thr_steps);
-        j->d_thr_steps = nullptr;
         j->thr_floats = 0;
-        JET_TRY(hipMalloc(&j->d_thr_steps, TS * sizeof(float)));
+        HIP_TRY(j->d_thr_steps.alloc(TS));   // (frees the shorter one first)
         j->thr_floats = TS;
     }
     const size_t LG = log ? size_t(steps) * N * 2 : 0;
     if (LG > j->log_doubles) {
-        if (j->d_log) (void)hipFree(j->d_log);
-        j->d_log = nullptr;
         j->log_doubles = 0;
-        JET_TRY(hipMalloc(&j->d_log, LG * sizeof(double)));
+        HIP_TRY(j->d_log.alloc(LG));   // (frees the shorter one first)
         j->log_doubles = LG;
     }
-    JET_TRY(hipMemcpy(j->d_f0, T_nn, N * sizeof(float), hipMemcpyHostToDevice));
-    JET_TRY(hipMemcpy(j->d_x, x_est, N * 2 * sizeof(double), hipMemcpyHostToDevice));
-    JET_TRY(hipMemcpy(j->d_P, P, N * 4 * sizeof(double), hipMemcpyHostToDevice));
-    JET_TRY(hipMemcpy(j->d_thr_steps, throttle, TS * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(j->d_f0, T_nn, N * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(j->d_x, x_est, N * 2 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(j->d_P, P, N * 4 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(j->d_thr_steps, throttle, TS * sizeof(float), hipMemcpyHostToDevice));
     int rc = vsmpc_jet_plant_run_device(j, j->d_f0, j->d_x, j->d_P, j->d_thr_steps, throttle_steps, n, steps, dt, Q, R,
                                         log ? j->d_log : nullptr, nullptr);
     if (rc != VSMPC_OK) return rc;
-    JET_TRY(hipDeviceSynchronize());
-    JET_TRY(hipMemcpy(T_nn, j->d_f0, N * sizeof(float), hipMemcpyDeviceToHost));
-    JET_TRY(hipMemcpy(x_est, j->d_x, N * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    JET_TRY(hipMemcpy(P, j->d_P, N * 4 * sizeof(double), hipMemcpyDeviceToHost));
-    if (log) JET_TRY(hipMemcpy(log, j->d_log, LG * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(T_nn, j->d_f0, N * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(x_est, j->d_x, N * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(P, j->d_P, N * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    if (log) HIP_TRY(hipMemcpy(log, j->d_log, LG * sizeof(double), hipMemcpyDeviceToHost));
     return VSMPC_OK;
 }
 

@@ -23,8 +23,9 @@ struct DeviceScope {
     DeviceScope& operator=(const DeviceScope&) = delete;
 };
 
-// VSMPC_ERR_INVALID_ARG for every entry but vsmpc_pack_tunables (vsmpc_capi.hip): it also drops the text a refused pack
-// left on this thread, so that vsmpc_strerror describes the call that failed last
+// VSMPC_ERR_INVALID_ARG for every entry but vsmpc_pack_tunables (defined beside it in vsmpc_capi.hip; the other codes that
+// carry a text are declared in vsmpc_host.hpp): it also drops the text a refused pack left on this thread, so that
+// vsmpc_strerror describes the call that failed last
 int invalid_arg();
 
 enum Variant { VARIANT_NONE = 0 };  // 1.. = position in csrc/vsmpc_horizons.def
