@@ -30,8 +30,7 @@ int vsmpc_linearize_batch(vsmpc_handle* h, const double* in, int batch, double* 
     double* dBt = dBj + size_t(h->max_batch) * NX * NJ;
     double* dC = dBt + size_t(h->max_batch) * NX * NTH;
     HIP_TRY(hipMemcpy(h->d_in, in, B * h->n_in * sizeof(double), hipMemcpyHostToDevice));
-    if (h->runtime) HIP_TRY(launch_linearize_runtime(h->rt, h->dev, h->d_in, batch, dA, dBj, dBt, dC, nullptr));
-    else HIP_TRY(launch_linearize(h->variant, h->dev, h->d_in, batch, dA, dBj, dBt, dC, nullptr));
+    HIP_TRY(launch_linearize_runtime(h->rt, h->dev, h->d_in, batch, dA, dBj, dBt, dC, nullptr));   // on every handle
     HIP_TRY(hipDeviceSynchronize());
     if (A) HIP_TRY(hipMemcpy(A, dA, B * NX * NX * sizeof(double), hipMemcpyDeviceToHost));
     if (Bj) HIP_TRY(hipMemcpy(Bj, dBj, B * NX * NJ * sizeof(double), hipMemcpyDeviceToHost));

@@ -29,33 +29,13 @@
 // and PRIMAL NaN.
 #include "vsmpc_launch.hpp"
 #include "vsmpc_p0.hpp"
+#include "vsmpc_structure.hpp"
 
 namespace vsmpc {
 
 namespace {
 
 constexpr int CB = 256;
-constexpr int CERT_LIN = NX * NX + NX * NJ + NX * NTH + 28;   // A | Bj | Bt | c (p0_linearize's contiguous block)
-struct CertTag {};                                            // p0_linearize does not use its dimension parameter
-
-VS_DEV int cert_joint_block(const RtDims& d, int k) { return k < d.hc ? k : d.hc - 1; }                 // constraintsVSMPC.cpp:89-103
-VS_DEV int cert_throttle_block(const RtDims& d, int k) {                                               // :104-128
-    return k < d.ns ? 0 : (k < d.hc ? k - (d.ns - 1) : d.hc - d.ns);
-}
-
-// Columns of row r of A that p0_linearize can make non-zero, as two ranges [a0, a1) and [b0, b1) (vsmpc_p0.hpp;
-// systemDynamicsVSMPC.cpp:79-103,288-319,384-429): 142 of the 676 entries.
-VS_DEV void a_row_ranges(int r, int& a0, int& a1, int& b0, int& b1) {
-    b0 = b1 = 0;
-    if (r < 3) { a0 = 3; a1 = 6; }                          // CoM    <- h_lin
-    else if (r < 6) { a0 = 3; a1 = 6; b0 = 12; b1 = 16; }   // h_lin  <- h_lin, T
-    else if (r < 9) { a0 = 9; a1 = 12; }                    // RPY    <- h_ang
-    else if (r < 12) { a0 = 9; a1 = 16; }                   // h_ang  <- h_ang, T
-    else if (r < 20) { a0 = 12; a1 = 20; }                  // T, Tdot <- T, Tdot
-    else if (r < 23) { a0 = 0; a1 = 3; }                    // e_pos  <- CoM
-    else { a0 = 6; a1 = 9; }                                // e_rpy  <- RPY
-}
-
 // diagonal of Q on state row r (costsVSMPC.cpp:78-93): the squared square-root weight of the weighted rows, 0 on T, Tdot
 VS_DEV double q_diag(const double* __restrict__ sCfg, int r) {
     const double s = sCfg[CFG_SQ + (r < 12 ? r : (r >= 20 ? r - 8 : 0))];   // loaded unconditionally, selected afterwards
@@ -84,7 +64,7 @@ VS_DEV CertSmem cert_smem(const RtDims& d, int ncon, double* base) {
     CertSmem s;
     double* p = base;
     s.in = p;    p += (d.nin + 1) & ~1;
-    s.lin = p;   p += CERT_LIN;
+    s.lin = p;   p += LIN_DOUBLES;
     s.vprev = p; p += 4;
     s.cfg = p;   p += CFG_SIZE;
     s.dt = p;    p += MAX_STAGES;
@@ -96,7 +76,7 @@ VS_DEV CertSmem cert_smem(const RtDims& d, int ncon, double* base) {
 
 VS_HD int cert_ncon(const RtDims& d) { return d.nxs + NTH * (d.n - d.ns + 1); }
 VS_HD int cert_lds_doubles(const RtDims& d) {
-    return ((d.nin + 1) & ~1) + CERT_LIN + 4 + CFG_SIZE + MAX_STAGES + ((d.nvar + 1) & ~1) + ((cert_ncon(d) + 1) & ~1) +
+    return ((d.nin + 1) & ~1) + LIN_DOUBLES + 4 + CFG_SIZE + MAX_STAGES + ((d.nvar + 1) & ~1) + ((cert_ncon(d) + 1) & ~1) +
            4 * VSMPC_CERT_SIZE;
 }
 
@@ -155,7 +135,7 @@ __global__ __launch_bounds__(CB) void certify_kernel(DevCfg cfg, RtDims d, const
         for (int i = (N + 1) * NX + d.nv + tid; i < ncon; i += CB) s.y[i] = 0.0;
     }
     __syncthreads();
-    p0_linearize<CertTag>(cfg.use_jet, s.in, s.lin, s.lin + NX * NX, s.lin + NX * NX + NX * NJ,
+    p0_linearize(cfg.use_jet, s.in, s.lin, s.lin + NX * NX, s.lin + NX * NX + NX * NJ,
                           s.lin + NX * NX + NX * NJ + NX * NTH, s.vprev, tid, CB);
 
     // per-lane partials of the certificate
@@ -217,12 +197,12 @@ __global__ __launch_bounds__(CB) void certify_kernel(DevCfg cfg, RtDims d, const
             for (int c = a0; c < a1; ++c) acc = fma(sA[r * NX + c], xi[c], acc);
             for (int c = b0; c < b1; ++c) acc = fma(sA[r * NX + c], xi[c], acc);
             if ((r >= 3 && r < 6) || (r >= 9 && r < 12)) {                        // rows of Lambda_lin,B / Lambda_ang,B
-                const double* __restrict__ u = s.x + offJ + cert_joint_block(d, i) * NJ;
+                const double* __restrict__ u = s.x + offJ + joint_block(d, i) * NJ;
 #pragma unroll
                 for (int k = 0; k < NJ; ++k) acc = fma(sBj[r * NJ + k], u[k], acc);
             }
             if (r >= 12 && r < 20) {                                              // thrust or thrust-rate rows
-                const double* __restrict__ v = s.x + offV + cert_throttle_block(d, i) * NTH;
+                const double* __restrict__ v = s.x + offV + throttle_block(d, i) * NTH;
 #pragma unroll
                 for (int k = 0; k < NTH; ++k) acc = fma(sBt[r * NTH + k], v[k], acc);
             }
@@ -263,7 +243,7 @@ __global__ __launch_bounds__(CB) void certify_kernel(DevCfg cfg, RtDims d, const
             const int f = e - d.nu, t = f >> 2, k = f & 3;
             double sum = 0.0;
             for (int i = 0; i < N; ++i) {
-                if (cert_throttle_block(d, i) != t) continue;
+                if (throttle_block(d, i) != t) continue;
                 const double* __restrict__ yi = s.y + i * NX;
                 double c = 0.0;
 #pragma unroll

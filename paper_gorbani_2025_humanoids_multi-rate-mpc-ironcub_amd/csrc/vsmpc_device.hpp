@@ -27,6 +27,9 @@ constexpr int NTH = VSMPC_N_THRUSTS; // 4
 constexpr int NJC = 6;
 constexpr int NWROWS = 18;           // weighted state rows: 0..11 and 20..25 (costsVSMPC.cpp:78-93)
 constexpr int MAX_STAGES = 40;
+// box QP of every solve kernel (block principal pivoting): non-improving block steps tolerated before the least-index
+// fallback (the oracle's value)
+constexpr int AS_PATIENCE = 10;
 
 // Compile-time problem dimensions (variableSamplingMPC.cpp:42-45).
 template <int N_, int NS_, int HC_>

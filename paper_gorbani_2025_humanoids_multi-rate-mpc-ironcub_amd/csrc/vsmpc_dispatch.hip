@@ -205,14 +205,4 @@ hipError_t launch_solve_tuned(int variant, int form, const DevCfg& cfg, const do
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_linearize(int variant, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,
-                            double* Bt, double* c, hipStream_t stream) {
-    int id = 0;
-#define X(N, NS, HC) \
-    if (variant == ++id) return launch_linearize_dims<N, NS, HC>(cfg, d_in, batch, A, Bj, Bt, c, stream);
-#include "vsmpc_horizons.def"
-#undef X
-    return hipErrorInvalidValue;
-}
-
 }  // namespace vsmpc

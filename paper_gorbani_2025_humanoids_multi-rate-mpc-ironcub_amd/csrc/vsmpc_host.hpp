@@ -84,7 +84,7 @@ struct vsmpc_handle {
     vsmpc::DevCfg dev;
     int variant;     // tuned instantiation (1..), or VARIANT_NONE on a runtime handle
     int runtime;     // solve with the runtime-sized kernel (vsmpc_create_ex)
-    vsmpc::RtDims rt;               // its sizes (runtime handles only)
+    vsmpc::RtDims rt;               // its sizes; on every handle: the linearise and certify kernels are sized by them too
     vsmpc::DevBuf<double> d_ws;     // its per-instance workspace, max_batch x rt.ws_doubles
     // VSMPC_CREATE_SENSITIVITY: sizes of sens_kernel_rt, its workspace (max_batch x rts.ws_doubles) and the staging of the
     // host-pointer entry (SENS_CHUNK instances at a time)

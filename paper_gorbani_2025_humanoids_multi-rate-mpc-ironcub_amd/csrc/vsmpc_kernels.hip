@@ -188,30 +188,6 @@ VS_DEV void joint_expand(const double* __restrict__ sQR, const double* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
-// linearise-only kernel (vsmpc_linearize_batch)
-// ------------------------------------------------------------------------------------------------
-template <class D>
-__global__ __launch_bounds__(256) void linearize_kernel(DevCfg cfg, const double* __restrict__ in,
-                                                         double* __restrict__ A, double* __restrict__ Bj,
-                                                         double* __restrict__ Bt, double* __restrict__ c) {
-    __shared__ double sIn[(D::NIN + 3) & ~3];
-    __shared__ double sLin[NX * NX + NX * NJ + NX * NTH + 28 + 4];
-    const int tid = threadIdx.x, b = blockIdx.x;
-    for (int i = tid; i < D::NIN; i += 256) sIn[i] = in[size_t(b) * D::NIN + i];
-    __syncthreads();
-    double* sA = sLin;
-    double* sBj = sA + NX * NX;
-    double* sBt = sBj + NX * NJ;
-    double* sC = sBt + NX * NTH;
-    double* sVprev = sC + 28;
-    p0_linearize<D>(cfg.use_jet, sIn, sA, sBj, sBt, sC, sVprev, tid, 256);
-    for (int i = tid; i < NX * NX; i += 256) A[size_t(b) * NX * NX + i] = sA[i];
-    for (int i = tid; i < NX * NJ; i += 256) Bj[size_t(b) * NX * NJ + i] = sBj[i];
-    for (int i = tid; i < NX * NTH; i += 256) Bt[size_t(b) * NX * NTH + i] = sBt[i];
-    for (int i = tid; i < NX; i += 256) c[size_t(b) * NX + i] = sC[i];
-}
-
-// ------------------------------------------------------------------------------------------------
 // the solve kernel
 // ------------------------------------------------------------------------------------------------
 // Kernel-argument block as it lies in the kernarg segment.  Everything but `in` and `batch` is needed late (outputs) or
@@ -272,30 +248,20 @@ __global__ __launch_bounds__(D::BLOCK, D::WG_PER_CU) void solve_kernel_tuned(Dev
 // launchers of ONE horizon.  The kernels are straight-line template instantiations over Dims<nIter, nIterSmall,
 // controlHorizon>, ~10 instantiations of a 30 k-instruction kernel per horizon, so build.py compiles this file once per
 // horizon of csrc/vsmpc_horizons.def and kind, in parallel:
-//   -DVS_TU_HORIZON=N,NS,HC -DVS_TU_STAMPS=0|1   the production (0) or diagnostic (1) solve kernels of that horizon (+ its
-//                                          linearise kernel in the production unit), as explicit instantiations of
-//                                          launch_solve_dims / launch_linearize_dims, which the dispatchers
+//   -DVS_TU_HORIZON=N,NS,HC -DVS_TU_STAMPS=0|1   the production (0) or diagnostic (1) solve kernels of that horizon, as
+//                                          explicit instantiations of launch_solve_dims, which the dispatchers
 //                                          (vsmpc_dispatch.hip) only see declared (vsmpc_launch.hpp)
 //   -DVS_TU_HORIZON=N,NS,HC -DVS_TU_STAMPS=2 -DVS_TU_FORM=0|1   the per-instance-tunables kind (solve_kernel_tuned) of that
 //                                          horizon and condensing form, as launch_solve_tuned_dims
 // ------------------------------------------------------------------------------------------------
-constexpr int MAX_DEVICES = 64;
-
 template <class D, bool STAMPS, int FORM>
-static hipError_t launch_solve_f(int dev, const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm,
+static hipError_t launch_solve_f(const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm,
                                  int* d_status, int* d_iters, double* dbgM, double* dbgL,
                                  unsigned long long* stamps, hipStream_t stream) {
-    // the dynamic-LDS limit is a per-device function attribute: one process may drive several devices
-    // (two host threads with their own handles may arrive here together: the flag is atomic, setting the attribute twice
-    // is harmless, and it is published only after the call has succeeded)
-    static std::atomic<bool> attr_set[MAX_DEVICES];
+    static std::atomic<bool> attr_set[MAX_DEVICES];   // (allow_dynamic_lds, vsmpc_launch.hpp)
     constexpr size_t lds = FORM == 1 ? Smem<D>::bytes_struct : Smem<D>::bytes;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel<D, STAMPS, FORM>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return e;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(&solve_kernel<D, STAMPS, FORM>), attr_set, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((solve_kernel<D, STAMPS, FORM>), dim3(batch), dim3(D::BLOCK), lds, stream,
                        cfg, d_in, batch, d_x, d_fm, d_status, d_iters, dbgM, dbgL, stamps);
     return hipGetLastError();
@@ -306,18 +272,12 @@ hipError_t launch_solve_dims(int form, const DevCfg& cfg, const double* d_in, in
                              int* d_status, int* d_iters, double* dbgM, double* dbgL, unsigned long long* stamps,
                              hipStream_t stream) {
     using D = Dims<N, NS, HC>;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= MAX_DEVICES) return hipErrorInvalidDevice;
     if constexpr (D::STRUCT_P1) {
         if (form != 2) {
-            return launch_solve_f<D, STAMPS, 1>(dev, cfg, d_in, batch, d_x, d_fm, d_status, d_iters, dbgM, dbgL, stamps,
-                                                stream);
+            return launch_solve_f<D, STAMPS, 1>(cfg, d_in, batch, d_x, d_fm, d_status, d_iters, dbgM, dbgL, stamps, stream);
         }
     }
-    return launch_solve_f<D, STAMPS, 0>(dev, cfg, d_in, batch, d_x, d_fm, d_status, d_iters, dbgM, dbgL, stamps,
-                                            stream);
+    return launch_solve_f<D, STAMPS, 0>(cfg, d_in, batch, d_x, d_fm, d_status, d_iters, dbgM, dbgL, stamps, stream);
 }
 
 template <int N, int NS, int HC, int FORM>
@@ -327,19 +287,11 @@ hipError_t launch_solve_tuned_dims(const DevCfg& cfg, const double* d_in, const 
     if constexpr (FORM == 1 && !D::STRUCT_P1) {
         return hipErrorInvalidValue;   // (launch_solve_tuned asks for the structured form only where the horizon has it)
     } else {
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        if (dev < 0 || dev >= MAX_DEVICES) return hipErrorInvalidDevice;
-        static std::atomic<bool> attr_set[MAX_DEVICES];   // (see launch_solve_f)
+        static std::atomic<bool> attr_set[MAX_DEVICES];
         constexpr size_t lds = FORM == 1 ? Smem<D>::bytes_struct : Smem<D>::bytes;
         static_assert(D::WG_PER_CU < 2 || lds <= 80 * 1024, "the tuned kind keeps two workgroups per CU");
-        if (!attr_set[dev].load(std::memory_order_acquire)) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel_tuned<D, FORM>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-            if (e != hipSuccess) return e;
-            attr_set[dev].store(true, std::memory_order_release);
-        }
+        const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(&solve_kernel_tuned<D, FORM>), attr_set, lds);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL((solve_kernel_tuned<D, FORM>), dim3(batch), dim3(D::BLOCK), lds, stream, cfg, d_in, batch, d_x, d_fm,
                            d_status, d_iters, static_cast<double*>(nullptr), static_cast<double*>(nullptr),
                            static_cast<unsigned long long*>(nullptr), d_tun);
@@ -347,19 +299,9 @@ hipError_t launch_solve_tuned_dims(const DevCfg& cfg, const double* d_in, const 
     }
 }
 
-template <int N, int NS, int HC>
-hipError_t launch_linearize_dims(const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj, double* Bt,
-                                 double* c, hipStream_t stream) {
-    hipLaunchKernelGGL((linearize_kernel<Dims<N, NS, HC>>), dim3(batch), dim3(256), 0, stream, cfg, d_in, A, Bj, Bt, c);
-    return hipGetLastError();
-}
-
 #define VS_INSTANTIATE_SOLVE(N, NS, HC, ST)                                                                              \
     template hipError_t launch_solve_dims<N, NS, HC, ST>(int, const DevCfg&, const double*, int, double*, double*, int*, \
                                                          int*, double*, double*, unsigned long long*, hipStream_t);
-#define VS_INSTANTIATE_LIN(N, NS, HC)                                                                                   \
-    template hipError_t launch_linearize_dims<N, NS, HC>(const DevCfg&, const double*, int, double*, double*, double*, \
-                                                         double*, hipStream_t);
 #define VS_INSTANTIATE_TUNED(N, NS, HC, F)                                                                                 \
     template hipError_t launch_solve_tuned_dims<N, NS, HC, F>(const DevCfg&, const double*, const double*, int, double*, \
                                                               double*, int*, int*, hipStream_t);
@@ -370,7 +312,6 @@ VS_TU_APPLY(VS_INSTANTIATE_TUNED, VS_TU_HORIZON, VS_TU_FORM)
 VS_TU_APPLY(VS_INSTANTIATE_SOLVE, VS_TU_HORIZON, true)
 #else
 VS_TU_APPLY(VS_INSTANTIATE_SOLVE, VS_TU_HORIZON, false)
-VS_TU_APPLY(VS_INSTANTIATE_LIN, VS_TU_HORIZON)
 #endif
 
 }  // namespace vsmpc

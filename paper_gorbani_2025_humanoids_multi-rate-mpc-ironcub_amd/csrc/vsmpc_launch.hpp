@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+
 #include "vsmpc_device.hpp"
 
 struct vsmpc_jet;   // include/vsmpc_jet.h
@@ -22,6 +24,24 @@ struct DeviceScope {
     DeviceScope(const DeviceScope&) = delete;
     DeviceScope& operator=(const DeviceScope&) = delete;
 };
+
+// The dynamic-LDS limit of a kernel is a per-device function attribute, and one process may drive several devices: allows
+// `bytes` of dynamic LDS for `kernel` on the current device, once per device.  `attr_set` is the kernel's own flag array, a
+// function-local static of its launcher.  Two host threads with their own handles may arrive together: the flag is atomic,
+// setting the attribute twice is harmless, and it is published only after the call has succeeded.
+constexpr int MAX_DEVICES = 64;
+inline hipError_t allow_dynamic_lds(const void* kernel, std::atomic<bool> (&attr_set)[MAX_DEVICES], size_t bytes) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= MAX_DEVICES) return hipErrorInvalidDevice;
+    if (!attr_set[dev].load(std::memory_order_acquire)) {
+        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
+        if (e != hipSuccess) return e;
+        attr_set[dev].store(true, std::memory_order_release);
+    }
+    return hipSuccess;
+}
 
 // VSMPC_ERR_INVALID_ARG for every entry but vsmpc_pack_tunables (defined beside it in vsmpc_capi.hip; the other codes that
 // carry a text are declared in vsmpc_host.hpp): it also drops the text a refused pack left on this thread, so that
@@ -44,10 +64,8 @@ bool variant_has_structured(int variant);
 hipError_t launch_solve(int variant, int form, const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm,
                         int* d_status, int* d_iters, double* dbgM, double* dbgL, unsigned long long* stamps,
                         hipStream_t stream);
-hipError_t launch_linearize(int variant, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,
-                            double* Bt, double* c, hipStream_t stream);
 // the launchers of one horizon: explicit instantiations in that horizon's units of vsmpc_kernels.hip (STAMPS: the diagnostic
-// one), which launch_solve / launch_linearize (vsmpc_dispatch.hip) dispatch onto
+// one), which launch_solve (vsmpc_dispatch.hip) dispatches onto
 template <int N, int NS, int HC, bool STAMPS>
 hipError_t launch_solve_dims(int form, const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm,
                              int* d_status, int* d_iters, double* dbgM, double* dbgL, unsigned long long* stamps,
@@ -59,9 +77,6 @@ hipError_t launch_solve_tuned(int variant, int form, const DevCfg& cfg, const do
 template <int N, int NS, int HC, int FORM>
 hipError_t launch_solve_tuned_dims(const DevCfg& cfg, const double* d_in, const double* d_tun, int batch, double* d_x,
                                    double* d_fm, int* d_status, int* d_iters, hipStream_t stream);
-template <int N, int NS, int HC>
-hipError_t launch_linearize_dims(const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj, double* Bt,
-                                 double* c, hipStream_t stream);
 
 // Runtime-sized solve kernel (vsmpc_runtime.hip): every horizon config_valid() accepts, sizes as kernel arguments.
 struct RtDims {
@@ -90,6 +105,7 @@ hipError_t launch_solve_runtime_tuned(const RtDims& d, const DevCfg& cfg, const 
 hipError_t launch_sensitivity_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws,
                                       double* d_x, double* d_fm, int* d_status, int* d_iters, double* d_dx, double* d_dfm,
                                       int* d_active, int* d_flags, hipStream_t stream);
+// linearize_kernel_rt (vsmpc_linearize_batch, on every handle): p0_linearize alone
 hipError_t launch_linearize_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,
                                     double* Bt, double* c, hipStream_t stream);
 

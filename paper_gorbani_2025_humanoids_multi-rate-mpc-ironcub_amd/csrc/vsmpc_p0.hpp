@@ -33,7 +33,7 @@ VS_DEV double fast_rcp(double d) {
 // ------------------------------------------------------------------------------------------------
 // LAMBDA_BJ = false (the solve kernel): Bj is not filled with Lambda here -- p0_joint_reduction writes the reduced input
 // matrix R^T into it instead.
-template <class D, bool ZERO = true, bool SYNC = true, bool LAMBDA_BJ = true>
+template <bool ZERO = true, bool SYNC = true, bool LAMBDA_BJ = true>
 VS_DEV void p0_linearize(int use_jet, const double* __restrict__ sIn, double* __restrict__ sA,
                          double* __restrict__ sBj, double* __restrict__ sBt, double* __restrict__ sC,
                          double* __restrict__ sVprev, int tid, int nthreads) {

@@ -67,8 +67,6 @@ VS_DEV double small_spd_solve(const double* __restrict__ sP, unsigned long long 
 
 // size dispatch for small_spd_solve (one straight-line instantiation per size)
 constexpr int SMALL_SOLVE_MAX = 6;
-// block principal pivoting: non-improving block steps tolerated before the least-index fallback (the oracle's value)
-constexpr int AS_PATIENCE = 10;
 constexpr int AS_MAX_ITER = 64;   // active-set iteration cap (status MAX_ITER beyond)
 template <int NVS, int K = SMALL_SOLVE_MAX>
 VS_DEV double small_spd_solve_n(int k, const double* __restrict__ sP, unsigned long long mask, double rhs, int lane, int& bad) {

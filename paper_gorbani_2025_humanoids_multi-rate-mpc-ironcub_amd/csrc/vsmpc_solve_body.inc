@@ -122,7 +122,7 @@
             __syncthreads();
         }
     }
-    p0_linearize<D, false, false, false>(cfg.use_jet, sIn, sA, sBj, sBt, sC, sVprev, tid, D::BLOCK);  // barrier: after P1a below
+    p0_linearize<false, false, false>(cfg.use_jet, sIn, sA, sBj, sBt, sC, sVprev, tid, D::BLOCK);  // barrier: after P1a below
     // joint reduction: 6 unknowns per joint block instead of 8 (NJC).  The SYRK form needs the reduced input matrix at the top
     // of its recursion: all six steps here, in wavefront 3, which has only copies to do in P0 (5.6 k cycles, of which ~2.8 k
     // lengthen P0).  The structured form needs it for the tile entries only: three steps here (hidden), the other three in a

@@ -9,8 +9,10 @@ solve_kernel<...> that only the OLD build has (the retired PLDS parameter) is dr
 
 Compared per kernel: the instruction text (mnemonic and operands; encodings and addresses are not; branch operands are
 PC-relative and so position independent as they stand; the literal of a PC-relative address -- s_getpc_b64 followed by
-s_add_u32 -- is replaced by the section and section offset it points to: where the constant tables lie relative to the
-code is layout, which table an instruction reads is not) and the resource notes of the code-object metadata.
+s_add_u32 -- is replaced by the data object it points into and the offset inside it, or by section and section offset
+where no object symbol covers the address: where the constant tables lie relative to the code, and behind how many
+kernel descriptors in .rodata, is layout; which table an instruction reads is not) and the resource notes of the
+code-object metadata.
 
 NOT compared: the constant data the kernels read (the tile tables and the kernel descriptors in .rodata).  A change that
 alters a table's CONTENTS and no instruction passes here: compare .rodata of the code objects beside it when a refactor
@@ -38,6 +40,7 @@ _INS = re.compile(r"^\s+(\S.*?)\s*//\s*([0-9A-Fa-f]+):")
 _GETPC = re.compile(r"^s_getpc_b64 s\[(\d+):\d+\]")
 _PCADD = re.compile(r"^(s_add_u32 s(\d+), s(\d+), )(0x[0-9a-f]+|-?\d+)$")
 _SECTION = re.compile(r"^\s*\d+\s+(\S+)\s+([0-9a-f]+)\s+([0-9a-f]+)\s")
+_OBJECT = re.compile(r"^([0-9a-f]+)\s+\S+\s+O\s+\S+\s+([0-9a-f]+)\s+(?:\.\S+\s+)?(\S+)\s*$")
 
 
 def demangle(names):
@@ -57,9 +60,15 @@ def kernels_of(obj: str) -> dict:
         notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True).stdout
         dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", co], capture_output=True, text=True).stdout
         hdr = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-h", co], capture_output=True, text=True).stdout
+        syms = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-t", co], capture_output=True, text=True).stdout
     sections = [(m.group(1), int(m.group(3), 16), int(m.group(2), 16)) for m in map(_SECTION.match, hdr.split("\n")) if m]
 
+    objects = [(m.group(3), int(m.group(1), 16), int(m.group(2), 16)) for m in map(_OBJECT.match, syms.split("\n")) if m]
+
     def located(addr):
+        for name, start, size in objects:
+            if size and start <= addr < start + size:
+                return f"<{name}+0x{addr - start:x}>"
         for name, start, size in sections:
             if size and start <= addr < start + size:
                 return f"<{name}+0x{addr - start:x}>"
