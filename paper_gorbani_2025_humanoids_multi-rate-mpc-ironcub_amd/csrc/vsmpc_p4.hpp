@@ -68,13 +68,89 @@ VS_DEV double small_spd_solve(const double* __restrict__ sP, unsigned long long 
 // size dispatch for small_spd_solve (one straight-line instantiation per size)
 constexpr int SMALL_SOLVE_MAX = 6;
 constexpr int AS_MAX_ITER = 64;   // active-set iteration cap (status MAX_ITER beyond)
-template <int NVS, int K = SMALL_SOLVE_MAX>
+template <int NVS, int K = SMALL_SOLVE_MAX, int KLO = 1>   // sizes KLO..K
 VS_DEV double small_spd_solve_n(int k, const double* __restrict__ sP, unsigned long long mask, double rhs, int lane, int& bad) {
-    if constexpr (K == 1) {
-        return small_spd_solve<1, NVS>(sP, mask, rhs, lane, bad);
+    if constexpr (K <= KLO) {
+        return small_spd_solve<KLO, NVS>(sP, mask, rhs, lane, bad);
     } else {
         if (k == K) return small_spd_solve<K, NVS>(sP, mask, rhs, lane, bad);
-        return small_spd_solve_n<NVS, K - 1>(k, sP, mask, rhs, lane, bad);
+        return small_spd_solve_n<NVS, K - 1, KLO>(k, sP, mask, rhs, lane, bad);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// One whole pass of dual_active_set for K active bounds, 1 <= K <= SMALL_PASS_MAX, as straight-line code: the solve of
+// small_spd_solve<K> (same operations, same order, same test on the pivots) AND the update v_N = v_u,N - P[:,A] mu behind
+// it.  A pass of the loop is a chain of dependent round trips, and the slowest instance of a batch-256 launch runs three of
+// them while 255 compute units wait; here
+//   * every LDS word of the pass -- the K (K + 1) / 2 entries of P_AA and this lane's K entries P[r][idx_q] of the active
+//     columns -- is requested in ONE batch in front of the arithmetic (the scheduling barrier pins the order): one LDS round
+//     trip per pass, where the loop has one in front of the solve and one per active bound behind it;
+//   * the update multiplies by the wave-uniform x[q] the solve holds -- the value readlane(mu, idx_q) returns -- in
+//     ascending index order with the loop's multiply-subtract: the results are bit for bit the loop's.
+// The columns must be complete in LDS for this wavefront (the caller orders its own stores with wave_lds_sync).  Lane
+// idx_q returns mu_q, every other lane 0; vn = the updated v for the lanes in N, v_u elsewhere.
+// ------------------------------------------------------------------------------------------------
+constexpr int SMALL_PASS_MAX = SMALL_SOLVE_MAX;
+template <int K, int NVS>
+VS_DEV double small_set_pass(const double* __restrict__ sP, unsigned long long mask, double rhs, int lane, int r, bool inN,
+                             double vu, double& vn, int& bad) {
+    int idx[K];
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+        idx[q] = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+    }
+    double A[K][K], pc[K], d[K];
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+#pragma unroll
+        for (int c = 0; c <= q; ++c) A[q][c] = sP[idx[c] * NVS + idx[q]];  // uniform address: LDS broadcast
+    }
+#pragma unroll
+    for (int q = 0; q < K; ++q) pc[q] = sP[idx[q] * NVS + r];              // P[r][idx_q]
+#pragma unroll
+    for (int q = 0; q < K; ++q) d[q] = readlane_f64(rhs, idx[q]);
+    __builtin_amdgcn_sched_barrier(0);
+    double ip[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        bad |= !(A[j][j] > 0.0);
+        ip[j] = fast_rcp(A[j][j]);
+#pragma unroll
+        for (int i = j + 1; i < K; ++i) {
+            const double f = A[i][j] * ip[j];
+            d[i] = fma(-f, d[j], d[i]);
+#pragma unroll
+            for (int c = j + 1; c <= i; ++c) A[i][c] = fma(-f, A[c][j], A[i][c]);
+        }
+    }
+    double x[K], mu = 0.0;
+#pragma unroll
+    for (int j = K - 1; j >= 0; --j) {
+        double t = d[j];
+#pragma unroll
+        for (int c = j + 1; c < K; ++c) t = fma(-A[c][j], x[c], t);
+        x[j] = t * ip[j];
+        mu = (lane == idx[j]) ? x[j] : mu;
+    }
+    double v = vu;
+#pragma unroll
+    for (int q = 0; q < K; ++q)
+        if (inN) v -= pc[q] * x[q];
+    vn = v;
+    return mu;
+}
+
+// size dispatch for small_set_pass, the small sizes first (the usual one to three saturated throttles)
+template <int NVS, int KS, int K = 1>
+VS_DEV double small_set_pass_n(int k, const double* __restrict__ sP, unsigned long long mask, double rhs, int lane, int r,
+                               bool inN, double vu, double& vn, int& bad) {
+    if constexpr (K >= KS) {
+        return small_set_pass<KS, NVS>(sP, mask, rhs, lane, r, inN, vu, vn, bad);
+    } else {
+        if (k == K) return small_set_pass<K, NVS>(sP, mask, rhs, lane, r, inN, vu, vn, bad);
+        return small_set_pass_n<NVS, KS, K + 1>(k, sP, mask, rhs, lane, r, inN, vu, vn, bad);
     }
 }
 
@@ -112,6 +188,7 @@ template <class D>
 struct XTiles {
     static constexpr int NVS = D::NV + 1, NR2 = D::NV - 16;
     static constexpr int KMAX = SMALL_SOLVE_MAX;   // largest system solved in registers (the accumulator tiles are in VGPRs here)
+    static constexpr int KPASS = SMALL_PASS_MAX;   // largest active set that takes the straight-line pass (small_set_pass)
     static constexpr int KMID = 16;                // compact row-per-lane solver for 7..16 active bounds (mid_spd_solve): it fits
                                                    // beside the accumulator tiles without a spilled register
     const double* X6;
@@ -138,6 +215,8 @@ template <class D>
 struct XDense {
     static constexpr int NVS = D::NV + 1;
     static constexpr int KMAX = 10;                // accumulator tiles live in AGPRs at these horizons: room for 10 x 10
+    static constexpr int KPASS = 0;                // no straight-line pass here: the loop as it was (with it for up to six bounds
+                                                   // the 2x horizon at batch 4096 measured 0.3-0.4 % slower, outside the noise)
     static constexpr int KMID = 24;                // and for the compact row-per-lane solver up to KMID x KMID (mid_spd_solve)
     const double* sXd;
     VS_DEV double col(int j, int r, int n) const { return j < n ? sXd[j * NVS + r] : 0.0; }
@@ -300,6 +379,8 @@ VS_DEV void dual_active_set(const XA& xa, bool hold, int lane, double* __restric
     (void)qt; (void)qt_mark;
     VS_QP_TIC();
     constexpr int NVS = D::NV + 1;          // row stride of the LDS work arrays
+    constexpr int KS = XA::KPASS;           // largest set that takes small_set_pass (0: none)
+    static_assert(KS <= XA::KMAX && KS <= SMALL_PASS_MAX, "the pass has an instantiation per size");
     double* sP = sSv;                       // sP[b * NVS + i] = P[i][b] for the columns b formed so far (have0: on entry)
     double* sK = sQP;                       // working copy of P_AA
     const int r = lane < D::NV ? lane : D::NV - 1;  // lanes >= NV shadow the last row (results unused)
@@ -338,15 +419,21 @@ VS_DEV void dual_active_set(const XA& xa, bool hold, int lane, double* __restric
             const double pb = xa.pcol(b, r, n);
             if (valid) sP[b * NVS + r] = pb;
         }
+        if constexpr (KS > 0) wave_lds_sync();   // the column stores above before the hoisted loads of other lanes' words (no instruction)
         VS_QP_TOC(1);
         double bb = isA ? vu - (state < 0 ? lo : hi) : 0.0;  // right-hand side v_u,A - b_A
         double mu = 0.0;
         const int ka = __popcll(Amask);
+        double vn = vu;                                      // v_N = v_u,N - P[:,A] mu
+        const bool small_pass = ka >= 1 && ka <= KS;
         if (ka == 0) {
             // every bound was released again: v = v_u, no multipliers
+        } else if (small_pass) {
+            // few active bounds: the whole pass (solve and update) straight-line on wave-uniform values, one LDS round trip
+            if constexpr (KS > 0) mu = small_set_pass_n<D::NV + 1, KS>(ka, sP, Amask, bb, lane, r, inN, vu, vn, bad);
         } else if (ka <= XA::KMAX) {
-            // few active bounds: solved redundantly in every lane on wave-uniform values
-            mu = small_spd_solve_n<D::NV + 1, XA::KMAX>(ka, sP, Amask, bb, lane, bad);
+            // solved redundantly in every lane on wave-uniform values
+            if constexpr (XA::KMAX > KS) mu = small_spd_solve_n<D::NV + 1, XA::KMAX, KS + 1>(ka, sP, Amask, bb, lane, bad);
         } else if (XA::KMID > 0 && ka <= XA::KMID) {
             if constexpr (XA::KMID > 0) mu = mid_spd_solve<XA::KMID, D::NV + 1>(ka, sP, Amask, bb, lane, isA, bad);
         } else {
@@ -383,13 +470,14 @@ VS_DEV void dual_active_set(const XA& xa, bool hold, int lane, double* __restric
         }
         VS_QP_TOC(2);
         if (bad) { status = VSMPC_STATUS_NUMERICAL; break; }
-        // v_N = v_u,N - P[:,A] mu
-        v = vu;
-        for (unsigned long long m = Amask; m; m &= m - 1) {
-            const int b = __ffsll((long long)m) - 1;
-            const double mub = readlane_f64(mu, b);
-            if (inN) v -= sP[b * NVS + r] * mub;
+        if (!small_pass) {
+            for (unsigned long long m = Amask; m; m &= m - 1) {
+                const int b = __ffsll((long long)m) - 1;
+                const double mub = readlane_f64(mu, b);
+                if (inN) vn -= sP[b * NVS + r] * mub;
+            }
         }
+        v = vn;
         const double grad = -mu;  // gradient of the QP at the throttles that sit on a bound
         const double tolv = 1e-12 * (1.0 + fabs(v));
         const bool isF = inN && state == 0;
