@@ -505,6 +505,25 @@ void vsmpc_free_host(void* p);
  * Returns the previous setting, VSMPC_ERR_INVALID_ARG, or VSMPC_ERR_UNSUPPORTED_CONFIG (form 1 without the instantiation). */
 int vsmpc_set_kernel_form(vsmpc_handle* h, int form);
 
+/* Which kernel serves small batches.  A horizon whose shipped kernel runs two workgroups per CU (the paper horizon 17/7/12)
+ * also has a SMALL-BATCH KIND of it, solve_kernel_small: when the batch does not exceed the compute units of the device a CU
+ * runs one workgroup anyway, so that kind takes the LDS of a whole CU, keeps the arrays of the condensing apart from the
+ * Cholesky's ring and forms most Hessian tiles beside the first two panel streams instead of in front of them.  Same
+ * arithmetic per tile, same outputs bit for bit.  `mode`: 0 auto -- the small-batch kind when batch <= CU count (read from the
+ * device at create) and the handle's form is structured; 1 never; 2 always where the horizon has the kind (measurements).  It
+ * applies to vsmpc_solve_batch, vsmpc_solve_batch_device, vsmpc_tick, the rollout (whose captured tick graph is rebuilt when
+ * the answer changes) and vsmpc_debug_phase_cycles; the per-instance-tunables entries (vsmpc_solve_batch_tuned*, a rollout
+ * with tunables), the SYRK form and vsmpc_debug_condensed keep the shipped kernel.  Per handle; a new handle starts with auto
+ * (or with VSMPC_SMALL_BATCH=auto|never|always from the environment).  Returns the previous setting, VSMPC_ERR_INVALID_ARG,
+ * or VSMPC_ERR_UNSUPPORTED_CONFIG (mode 2 on a horizon without the kind, or on a runtime handle). */
+int vsmpc_set_small_batch_kernel(vsmpc_handle* h, int mode);
+/* 1 when a solve of `batch` instances on this handle runs on the small-batch kind, 0 when on the shipped kernel;
+ * VSMPC_ERR_INVALID_ARG for a NULL handle or batch <= 0.  No device work. */
+int vsmpc_small_batch_kernel_for(const vsmpc_handle* h, int batch);
+/* Dynamic LDS (bytes) a workgroup of the small-batch kind is launched with at this horizon (at most the 160 KB of a CU), or
+ * 0 when the horizon is not in the build's table or has no such kind.  No handle, no device work. */
+size_t vsmpc_small_batch_lds_bytes(int n_iter, int n_iter_small, int control_horizon);
+
 const char* vsmpc_strerror(int code);
 const char* vsmpc_kernel_name(const vsmpc_handle* h);
 

@@ -22,6 +22,7 @@ EXPORTS = (
     "vsmpc_tick", "vsmpc_rollout_set_tree", "vsmpc_num_throttle_unknowns", "vsmpc_sensitivity_batch",
     "vsmpc_sensitivity_batch_device", "vsmpc_pack_tunables", "vsmpc_solve_batch_tuned", "vsmpc_solve_batch_tuned_device",
     "vsmpc_rollout_set_tunables", "vsmpc_certify_batch", "vsmpc_certify_batch_device",
+    "vsmpc_set_small_batch_kernel", "vsmpc_small_batch_kernel_for", "vsmpc_small_batch_lds_bytes",
     # include/vsmpc_jet.h
     "vsmpc_jet_create", "vsmpc_jet_destroy", "vsmpc_jet_nn_step", "vsmpc_jet_nn_sequence", "vsmpc_jet_ekf_update",
     "vsmpc_jet_plant_run", "vsmpc_jet_plant_run_device", "vsmpc_rollout_set_jet_plant",
@@ -113,6 +114,12 @@ def load():
     lib.vsmpc_free_host.restype = None
     lib.vsmpc_set_kernel_form.argtypes = [vp, c_int]
     lib.vsmpc_set_kernel_form.restype = c_int
+    lib.vsmpc_set_small_batch_kernel.argtypes = [vp, c_int]
+    lib.vsmpc_set_small_batch_kernel.restype = c_int
+    lib.vsmpc_small_batch_kernel_for.argtypes = [vp, c_int]
+    lib.vsmpc_small_batch_kernel_for.restype = c_int
+    lib.vsmpc_small_batch_lds_bytes.argtypes = [c_int, c_int, c_int]
+    lib.vsmpc_small_batch_lds_bytes.restype = ctypes.c_size_t
     lib.vsmpc_set_kinematics_options.argtypes = [vp, ip, c_int]
     lib.vsmpc_set_kinematics_options.restype = c_int
     lib.vsmpc_provider_batch.argtypes = [vp, vp, dp, c_int, dp, dp, dp]

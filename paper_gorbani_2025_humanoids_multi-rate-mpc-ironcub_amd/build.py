@@ -64,12 +64,14 @@ OBJ_DIR = os.path.join(HERE, "build")
 
 
 SCHED_MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+# the small-batch kind of the paper horizon: 32.4-32.8 us per 256-launch with max-ilp, 32.8-33.2 with the default strategy
+SMALL_SCHED = SCHED_MAX_ILP
 
 
 def _units():
-    """(object name, source, extra flags): vsmpc_kernels.hip is compiled four times per horizon (production, diagnostic and
-    the two condensing forms of the per-instance-tunables kind, see the note on the launchers in the file), everything
-    else once.  Which horizons have a structured form is decided in the C++ (Dims::STRUCT_P1), so the structured unit is
+    """(object name, source, extra flags): vsmpc_kernels.hip is compiled five times per horizon (production, diagnostic, the
+    two condensing forms of the per-instance-tunables kind and the small-batch kind, see the note on the launchers in the
+    file), everything else once.  Which horizons have a structured form is decided in the C++ (Dims::STRUCT_P1), so the structured unit is
     listed for every horizon: where the horizon has none (21,9,15 of the default table) it holds no kernel, only a
     launcher that returns hipErrorInvalidValue and that the dispatcher never calls."""
     units = []
@@ -84,6 +86,9 @@ def _units():
         for form in (0, 1):     # the per-instance-tunables kind: one unit per condensing form (1 = structured)
             units.append((f"kernels_{n}_{ns}_{hc}_tuned_{'struct' if form else 'syrk'}", SOLVE,
                           [f"-DVS_TU_HORIZON={n},{ns},{hc}", "-DVS_TU_STAMPS=2", f"-DVS_TU_FORM={form}"] + sched))
+        # the small-batch kind (solve_kernel_small, production + diagnostic; a horizon without it gets a launcher that
+        # refuses and that the dispatcher never calls).  Scheduler strategy: see SMALL_SCHED
+        units.append((f"kernels_{n}_{ns}_{hc}_small", SOLVE, [f"-DVS_TU_HORIZON={n},{ns},{hc}", "-DVS_TU_STAMPS=3"] + SMALL_SCHED))
     for src in SOURCES:
         if src != SOLVE:
             units.append((os.path.splitext(src)[0], src, []))

@@ -155,6 +155,12 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     if (h->form == 1 && !variant_has_structured(variant)) h->form = 0;
     h->device = device;
     h->max_batch = max_batch;
+    h->small_mode = initial_small_batch_mode();
+    h->cu_count = 0;
+    {
+        const hipError_t ea = hipDeviceGetAttribute(&h->cu_count, hipDeviceAttributeMultiprocessorCount, device);
+        if (ea != hipSuccess) { delete h; return hip_fail(ea, "vsmpc_create"); }
+    }
     const int N = cfg->n_iter, nS = cfg->n_iter_small, H = cfg->control_horizon;
     h->n_var = NX * (N + 1) + NJ * H + NTH * (H - nS + 1);
     h->n_con = NX * (N + 1) + NTH * (N - nS + 1);
@@ -256,6 +262,23 @@ int vsmpc_set_kernel_form(vsmpc_handle* h, int form) {
     const int prev = h->form;
     h->form = form;
     return prev;
+}
+
+int vsmpc_set_small_batch_kernel(vsmpc_handle* h, int mode) {
+    if (h == nullptr || mode < 0 || mode > 2) return invalid_arg();
+    if (mode == 2 && (h->runtime || !variant_has_small(h->variant))) return unsupported("this horizon has no small-batch kind of the solve kernel");
+    const int prev = h->small_mode;
+    h->small_mode = mode;
+    return prev;
+}
+
+int vsmpc_small_batch_kernel_for(const vsmpc_handle* h, int batch) {
+    if (h == nullptr || batch <= 0) return invalid_arg();
+    return small_batch_kernel(h, batch) ? 1 : 0;
+}
+
+size_t vsmpc_small_batch_lds_bytes(int n_iter, int n_iter_small, int control_horizon) {
+    return variant_small_lds_bytes(select_variant(n_iter, n_iter_small, control_horizon));
 }
 
 void* vsmpc_alloc_host(size_t bytes) {

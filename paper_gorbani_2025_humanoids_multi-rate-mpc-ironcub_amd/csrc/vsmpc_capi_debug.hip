@@ -138,6 +138,7 @@ int vsmpc_debug_condensed(vsmpc_handle* h, const double* in_one, double* M, doub
     const size_t np2 = size_t(h->n_p) * h->n_p;
     HIP_TRY(hipMemcpy(h->d_in, in_one, h->n_in * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(h->d_dbg, 0, 2 * np2 * sizeof(double)));   // the kernel writes the lower triangles only
+    // (always the shipped kernel: the small-batch kind never has all tiles of the condensed Hessian at one point)
     HIP_TRY(launch_solve(h->variant, h->form, h->dev, h->d_in, 1, h->d_x, h->d_fm, h->d_status, h->d_iters, h->d_dbg,
                          h->d_dbg + np2, nullptr, nullptr));
     HIP_TRY(hipDeviceSynchronize());
@@ -215,9 +216,11 @@ int vsmpc_debug_phase_cycles(vsmpc_handle* h, const double* in, int batch, unsig
     unsigned long long* d_st = h->d_stamps;
     HIP_TRY(hipMemset(d_st, 0, size_t(batch) * 16 * sizeof(unsigned long long)));
     HIP_TRY(hipMemcpy(h->d_in, in, size_t(batch) * h->n_in * sizeof(double), hipMemcpyHostToDevice));
+    const bool small = small_batch_kernel(h, batch);   // the stamps of the kernel a solve of this batch runs on
     for (int rep = 0; rep < 3; ++rep)  // warm instruction caches, keep the last run
-        HIP_TRY(launch_solve(h->variant, h->form, h->dev, h->d_in, batch, h->d_x, h->d_fm, h->d_status, h->d_iters, nullptr,
-                             nullptr, d_st, nullptr));
+        HIP_TRY(small ? launch_solve_small(h->variant, h->dev, h->d_in, batch, h->d_x, h->d_fm, h->d_status, h->d_iters, d_st, nullptr)
+                      : launch_solve(h->variant, h->form, h->dev, h->d_in, batch, h->d_x, h->d_fm, h->d_status, h->d_iters, nullptr,
+                                     nullptr, d_st, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(stamps16, d_st, size_t(batch) * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return VSMPC_OK;

@@ -218,6 +218,7 @@ hipError_t enqueue_tick(vsmpc_rollout* r, hipStream_t s) {
 void build_tick_graph(vsmpc_rollout* r, hipStream_t s) {
     r->graph_state = -1;
     r->graph_form = r->h->form;
+    r->graph_small = small_batch_kernel(r->h, r->batch) ? 1 : 0;
     if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return; }
     hipError_t e = hipSuccess;
     for (int t = 0; t < GRAPH_TICKS && e == hipSuccess; ++t) e = enqueue_tick(r, s);
@@ -254,7 +255,8 @@ int vsmpc_rollout_run(vsmpc_rollout* r, int ticks, double* log, void* stream) {
     HIP_TRY(hipStreamSynchronize(s));  // `ctl` lives on this stack frame
     r->valid = 0;                       // until the whole run has completed: a failure below leaves the counters ahead
     int t = 0;
-    if (r->graph_state != 0 && r->graph_form != h->form) invalidate(r);   // the captured launches are of the other condensing form
+    // the captured launches are of the other condensing form, or of the other kernel for this batch size
+    if (r->graph_state != 0 && (r->graph_form != h->form || r->graph_small != (small_batch_kernel(h, r->batch) ? 1 : 0))) invalidate(r);
     if (ticks >= GRAPH_TICKS && r->graph_state == 0) build_tick_graph(r, s);
     if (r->graph_state == 1)
         for (; ticks - t >= GRAPH_TICKS; t += GRAPH_TICKS) HIP_TRY(hipGraphLaunch(r->gexec, s));

@@ -15,6 +15,8 @@ hipError_t vsmpc::solve_launch(const vsmpc_handle* h, const double* d_in, int ba
     if (h->runtime)
         return launch_solve_runtime(h->rt, h->dev, d_in, batch, h->d_ws + first * size_t(h->rt.ws_doubles), d_x, d_fm,
                                     d_status, d_iters, s);
+    if (small_batch_kernel(h, batch))
+        return launch_solve_small(h->variant, h->dev, d_in, batch, d_x, d_fm, d_status, d_iters, nullptr, s);
     return launch_solve(h->variant, h->form, h->dev, d_in, batch, d_x, d_fm, d_status, d_iters, nullptr, nullptr, nullptr, s);
 }
 

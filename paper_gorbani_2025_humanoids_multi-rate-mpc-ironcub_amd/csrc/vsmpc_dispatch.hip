@@ -120,16 +120,31 @@ int initial_kernel_form() {
     return (v != nullptr && v[0] == 's' && v[1] == 't') ? 1 : (v != nullptr && v[0] == 's' && v[1] == 'y') ? 2 : 0;
 }
 
+// which kernel serves small batches (vsmpc_set_small_batch_kernel): 0 = the small-batch kind when the batch does not exceed
+// the device's CUs, 1 = never, 2 = always where the horizon has it.  VSMPC_SMALL_BATCH=auto|never|always is what a new handle
+// starts with.
+int initial_small_batch_mode() {
+    const char* v = getenv("VSMPC_SMALL_BATCH");
+    return (v != nullptr && v[0] == 'n') ? 1 : (v != nullptr && v[0] == 'a' && v[1] == 'l') ? 2 : 0;
+}
+
+template <class D>
+constexpr size_t small_lds_bytes() {
+    if constexpr (has_small_kind<D>()) return Smem<D, true>::bytes_struct;
+    else return 0;
+}
+
 struct HorizonEntry {
     int n_iter, n_iter_small, control_horizon, n_p;
     size_t lds_bytes;
     const char* name;
     bool structured;
+    size_t small_lds_bytes;   // 0: the horizon has no small-batch kind
 };
 #define VSMPC_STR2(x) #x
 #define VSMPC_STR(x) VSMPC_STR2(x)
 static const HorizonEntry kHorizons[] = {
-#define X(N, NS, HC) {N, NS, HC, Dims<N, NS, HC>::NP, Dims<N, NS, HC>::STRUCT_P1 ? Smem<Dims<N, NS, HC>>::bytes_struct : Smem<Dims<N, NS, HC>>::bytes, "solve_kernel<Dims<" VSMPC_STR(N) "," VSMPC_STR(NS) "," VSMPC_STR(HC) ">>", Dims<N, NS, HC>::STRUCT_P1},
+#define X(N, NS, HC) {N, NS, HC, Dims<N, NS, HC>::NP, Dims<N, NS, HC>::STRUCT_P1 ? Smem<Dims<N, NS, HC>>::bytes_struct : Smem<Dims<N, NS, HC>>::bytes, "solve_kernel<Dims<" VSMPC_STR(N) "," VSMPC_STR(NS) "," VSMPC_STR(HC) ">>", Dims<N, NS, HC>::STRUCT_P1, small_lds_bytes<Dims<N, NS, HC>>()},
 #include "vsmpc_horizons.def"
 #undef X
 };
@@ -162,6 +177,23 @@ int variant_condensed_dim(int variant) {
 
 bool variant_has_structured(int variant) {
     return variant >= 1 && variant <= kNumHorizons && kHorizons[variant - 1].structured;
+}
+
+bool variant_has_small(int variant) { return variant_small_lds_bytes(variant) != 0; }
+
+size_t variant_small_lds_bytes(int variant) {
+    return (variant >= 1 && variant <= kNumHorizons) ? kHorizons[variant - 1].small_lds_bytes : 0;
+}
+
+hipError_t launch_solve_small(int variant, const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm,
+                              int* d_status, int* d_iters, unsigned long long* stamps, hipStream_t stream) {
+    if (!variant_has_small(variant)) return hipErrorInvalidValue;
+    int id = 0;
+#define X(N, NS, HC) \
+    if (variant == ++id) return launch_solve_small_dims<N, NS, HC>(cfg, d_in, batch, d_x, d_fm, d_status, d_iters, stamps, stream);
+#include "vsmpc_horizons.def"
+#undef X
+    return hipErrorInvalidValue;
 }
 
 size_t variant_lds_bytes(int variant) {

@@ -99,6 +99,8 @@ struct vsmpc_handle {
     int certify;
     vsmpc::DevBuf<double> d_cx, d_cy, d_ccert, d_ctun;
     int form;       // condensing form of the solve kernel (vsmpc_set_kernel_form)
+    int small_mode; // which kernel serves small batches (vsmpc_set_small_batch_kernel): 0 auto, 1 never, 2 always
+    int cu_count;   // compute units of `device` (read once, at create): auto takes the small-batch kind up to this batch
     vsmpc::KinOpts kin;     // vsmpc_set_kinematics_options
     int device;
     int max_batch;
@@ -146,6 +148,7 @@ struct vsmpc_rollout {
     hipGraphExec_t gexec;     // GRAPH_TICKS ticks (3 launches each) captured once, replayed per chunk
     int graph_state;          // 0 not built yet, 1 ready, -1 capture unavailable (direct launches only)
     int graph_form;           // h->form the graph was captured with (vsmpc_set_kernel_form on the handle rebuilds it)
+    int graph_small;          // small_batch_kernel(h, batch) it was captured with (vsmpc_set_small_batch_kernel likewise)
     // kinematic-tree plant (vsmpc_rollout_set_tree)
     int use_tree;
     vsmpc_tree tree;
@@ -179,5 +182,12 @@ bool tree_valid(const vsmpc_tree& tree);            // vsmpc_capi_debug.hip: par
 // nullptr: the handle's configuration for all of them.
 hipError_t solve_launch(const vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_fm, int* d_status,
                         int* d_iters, size_t first, hipStream_t s, const double* d_tun = nullptr);
+// does a launch of `batch` instances of the handle's configuration run on the small-batch kind (solve_kernel_small)?  The
+// horizon has it, the handle's form is structured, and the mode says always, or auto with the batch within the CUs.  (The
+// per-instance-tunables entries keep the shipped kernel.)
+inline bool small_batch_kernel(const vsmpc_handle* h, int batch) {
+    return !h->runtime && h->form != 2 && variant_has_small(h->variant) &&
+           (h->small_mode == 2 || (h->small_mode == 0 && batch <= h->cu_count));
+}
 
 }  // namespace vsmpc

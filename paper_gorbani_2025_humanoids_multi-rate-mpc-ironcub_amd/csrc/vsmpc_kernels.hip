@@ -61,7 +61,7 @@
 #include "vsmpc_p5.hpp"
 
 #if !defined(VS_TU_HORIZON) || !defined(VS_TU_STAMPS)
-#error "one unit per horizon and kind: -DVS_TU_HORIZON=N,NS,HC -DVS_TU_STAMPS=0|1, or =2 -DVS_TU_FORM=0|1 (build.py)"
+#error "one unit per horizon and kind: -DVS_TU_HORIZON=N,NS,HC -DVS_TU_STAMPS=0|1, =2 -DVS_TU_FORM=0|1, or =3 (build.py)"
 #endif
 #if VS_TU_STAMPS == 2 && !defined(VS_TU_FORM)
 #error "a unit of the tuned kind holds one condensing form: -DVS_TU_FORM=0|1"
@@ -229,6 +229,7 @@ __global__ __launch_bounds__(D::BLOCK, D::WG_PER_CU) void solve_kernel(DevCfg cf
                                                          int* iters_out_, double* dbgM_, double* dbgL_,
                                                          unsigned long long* stamps_) {
     constexpr bool TUNED = false;
+    constexpr bool SMALL = false;
     const double* const tun = nullptr;
 #include "vsmpc_solve_body.inc"
 }
@@ -241,6 +242,26 @@ __global__ __launch_bounds__(D::BLOCK, D::WG_PER_CU) void solve_kernel_tuned(Dev
                                                          unsigned long long* stamps_, const double* __restrict__ tun) {
     constexpr bool STAMPS = false;
     constexpr bool TUNED = true;
+    constexpr bool SMALL = false;
+#include "vsmpc_solve_body.inc"
+}
+
+// the small-batch kind (horizons with has_small_kind<D>(), structured form): launched when the batch does not exceed the
+// device's CUs, where a CU runs one workgroup whatever the kernel needs -- so it takes the LDS of a whole CU (Smem<D, true>)
+// and forms most Hessian tiles beside the first two panel streams (SmallPlan, vsmpc_p3.hpp).  Same arguments, same
+// arithmetic per tile and same workgroup barriers as solve_kernel<D, STAMPS, 1>: bit-identical outputs.  A name of its own:
+// the resource tests of the shipped kernels match on theirs.  Registers: the 256 per lane of the shipped kernel -- with 512
+// (__launch_bounds__(256, 1)) the allocator moved the tiles through 80 AGPRs and the launch took 33.2-33.5 us against
+// 32.4-32.8 (profiles/small_batch_bench_alternating.txt).
+template <class D, bool STAMPS>
+__global__ __launch_bounds__(D::BLOCK, D::WG_PER_CU) void solve_kernel_small(DevCfg cfg, const double* __restrict__ in, int batch,
+                                                         double* xout_, double* fmout_, int* status_out_,
+                                                         int* iters_out_, double* dbgM_, double* dbgL_,
+                                                         unsigned long long* stamps_) {
+    constexpr bool TUNED = false;
+    constexpr bool SMALL = true;
+    constexpr int FORM = 1;
+    const double* const tun = nullptr;
 #include "vsmpc_solve_body.inc"
 }
 
@@ -253,6 +274,8 @@ __global__ __launch_bounds__(D::BLOCK, D::WG_PER_CU) void solve_kernel_tuned(Dev
 //                                          (vsmpc_dispatch.hip) only see declared (vsmpc_launch.hpp)
 //   -DVS_TU_HORIZON=N,NS,HC -DVS_TU_STAMPS=2 -DVS_TU_FORM=0|1   the per-instance-tunables kind (solve_kernel_tuned) of that
 //                                          horizon and condensing form, as launch_solve_tuned_dims
+//   -DVS_TU_HORIZON=N,NS,HC -DVS_TU_STAMPS=3   the small-batch kind (solve_kernel_small, production and diagnostic) of that
+//                                          horizon, as launch_solve_small_dims
 // ------------------------------------------------------------------------------------------------
 template <class D, bool STAMPS, int FORM>
 static hipError_t launch_solve_f(const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm,
@@ -278,6 +301,28 @@ hipError_t launch_solve_dims(int form, const DevCfg& cfg, const double* d_in, in
         }
     }
     return launch_solve_f<D, STAMPS, 0>(cfg, d_in, batch, d_x, d_fm, d_status, d_iters, dbgM, dbgL, stamps, stream);
+}
+
+template <int N, int NS, int HC>
+hipError_t launch_solve_small_dims(const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm, int* d_status,
+                                   int* d_iters, unsigned long long* stamps, hipStream_t stream) {
+    using D = Dims<N, NS, HC>;
+    if constexpr (!has_small_kind<D>()) {
+        return hipErrorInvalidValue;   // (launch_solve asks for the kind only where variant_has_small says the horizon has it)
+    } else {
+        static std::atomic<bool> attr_set[2][MAX_DEVICES];
+        constexpr size_t lds = Smem<D, true>::bytes_struct;
+        static_assert(lds <= 160 * 1024, "the small-batch kind takes the LDS of one CU");
+        auto go = [&](auto stc) {
+            constexpr bool ST = decltype(stc)::value;
+            const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(&solve_kernel_small<D, ST>), attr_set[ST], lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((solve_kernel_small<D, ST>), dim3(batch), dim3(D::BLOCK), lds, stream, cfg, d_in, batch, d_x, d_fm,
+                               d_status, d_iters, static_cast<double*>(nullptr), static_cast<double*>(nullptr), stamps);
+            return hipGetLastError();
+        };
+        return stamps != nullptr ? go(std::true_type{}) : go(std::false_type{});
+    }
 }
 
 template <int N, int NS, int HC, int FORM>
@@ -306,7 +351,12 @@ hipError_t launch_solve_tuned_dims(const DevCfg& cfg, const double* d_in, const 
     template hipError_t launch_solve_tuned_dims<N, NS, HC, F>(const DevCfg&, const double*, const double*, int, double*, \
                                                               double*, int*, int*, hipStream_t);
 #define VS_TU_APPLY(M, ...) M(__VA_ARGS__)
-#if VS_TU_STAMPS == 2
+#define VS_INSTANTIATE_SMALL(N, NS, HC)                                                                              \
+    template hipError_t launch_solve_small_dims<N, NS, HC>(const DevCfg&, const double*, int, double*, double*, int*, int*, \
+                                                           unsigned long long*, hipStream_t);
+#if VS_TU_STAMPS == 3
+VS_TU_APPLY(VS_INSTANTIATE_SMALL, VS_TU_HORIZON)
+#elif VS_TU_STAMPS == 2
 VS_TU_APPLY(VS_INSTANTIATE_TUNED, VS_TU_HORIZON, VS_TU_FORM)
 #elif VS_TU_STAMPS
 VS_TU_APPLY(VS_INSTANTIATE_SOLVE, VS_TU_HORIZON, true)

@@ -70,6 +70,16 @@ template <int N, int NS, int HC, bool STAMPS>
 hipError_t launch_solve_dims(int form, const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm,
                              int* d_status, int* d_iters, double* dbgM, double* dbgL, unsigned long long* stamps,
                              hipStream_t stream);
+// the small-batch kind (solve_kernel_small; one unit of vsmpc_kernels.hip per horizon): structured form, no dumps; stamps !=
+// nullptr picks its diagnostic instantiation
+bool variant_has_small(int variant);
+hipError_t launch_solve_small(int variant, const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm,
+                              int* d_status, int* d_iters, unsigned long long* stamps, hipStream_t stream);
+template <int N, int NS, int HC>
+hipError_t launch_solve_small_dims(const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm, int* d_status,
+                                   int* d_iters, unsigned long long* stamps, hipStream_t stream);
+size_t variant_small_lds_bytes(int variant);   // its dynamic LDS (<= 160 KB: one workgroup per CU), 0 without the kind
+int initial_small_batch_mode();                // VSMPC_SMALL_BATCH: what a new handle starts with
 // the per-instance-tunables kind (solve_kernel_tuned; one unit of vsmpc_kernels.hip per horizon and condensing form, FORM
 // 1 = structured): d_tun [batch][VSMPC_TUNE_SIZE], rows of vsmpc_pack_tunables, 16-byte aligned
 hipError_t launch_solve_tuned(int variant, int form, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,

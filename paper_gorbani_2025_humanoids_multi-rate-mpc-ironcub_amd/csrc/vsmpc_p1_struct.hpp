@@ -41,9 +41,9 @@ VS_DEV double uniform_f64(double x) {
     return __hiloint2double(hi, lo);
 }
 
-template <class D, int KIND>
+template <class D, int KIND, bool SMALL = false>
 VS_DEV void p1s_chain(const DevCfg& cfg, int half, int lane, double* __restrict__ sm) {
-    using S = Smem<D>;
+    using S = Smem<D, SMALL>;
     constexpr int N = D::N, HC = D::HC, NV = D::NV;
     const double* sA = sm + S::oA;
     const double* sCfg = sm + S::oCfg;
@@ -286,9 +286,9 @@ VS_DEV void p1s_chain(const DevCfg& cfg, int half, int lane, double* __restrict_
 
 // sAc[c][i - 1][q] = sum over the halves of A_mom,half[:, q]^T W_c(i): the throttle x throttle tiles read it as a matrix-core
 // operand.  All wavefronts, between the chains and the entries: one (c, i) pair and its four q per thread and round.
-template <class D>
+template <class D, bool SMALL = false>
 VS_DEV void p1s_contract(double* __restrict__ sm, int tid) {
-    using S = Smem<D>;
+    using S = Smem<D, SMALL>;
     constexpr int NI = (D::NV + 1) * (D::N - 1);
     constexpr int ROUNDS = (NI + D::BLOCK - 1) / D::BLOCK;
     const double* sA = sm + S::oA;
@@ -338,9 +338,19 @@ VS_DEV void p1s_contract(double* __restrict__ sm, int tid) {
 // afterwards: with the loads of a tile right in front of its instructions every tile pays LDS round trips; the
 // accumulators are not live yet, so there are registers for the raw operands of a group of tiles at once (the loads are
 // pinned in front of the arithmetic).
-template <class D, int TPW, int W, bool PIPE = false>
+// PLAN says which slots this call forms: slot(a), a < count, in the order they are formed (groups of G), and forms(q).  The
+// shipped kernels form every slot at once (AllSlots); the small-batch kind forms a wavefront's tiles in three instalments
+// (SmallPlan in vsmpc_p3.hpp) from the arrays its carve-up keeps intact (Smem<D, true>).  A slot outside the plan is left alone.
+template <class D, int TPW, int W, bool PIPE>
+struct AllSlots {
+    static constexpr bool SMALL = false;
+    static constexpr int count = TPW;
+    static constexpr int slot(int a) { return a; }
+    static constexpr bool forms(int q) { return TileTab<D, PIPE>{}.forms(q * D::NWAVES + W, W); }
+};
+template <class D, int TPW, int W, bool PIPE = false, class PLAN = AllSlots<D, TPW, W, PIPE>>
 VS_DEV void p1s_entries(d4 (&acc)[TPW], const double* __restrict__ sm, int lane) {
-    using S = Smem<D>;
+    using S = Smem<D, PLAN::SMALL>;
     constexpr int PVT = D::PVT, N = D::N, HC = D::HC, NV = D::NV;
     static_assert(D::NU % 16 == 0, "joint rows are tile aligned");
     const double* sBj = sm + S::oBj;
@@ -372,16 +382,18 @@ VS_DEV void p1s_entries(d4 (&acc)[TPW], const double* __restrict__ sm, int lane)
     // tiles in groups of G (the raw operands of a group are all requested before its arithmetic starts)
     // 18 G + 12 G operand registers (doubles) beside the 18 of Lq; long horizons keep finished tiles in registers meanwhile
     constexpr int G = 3;
-    constexpr int NGRP = (TPW + G - 1) / G;
+    constexpr int NSLOT = PLAN::count;
+    constexpr int NGRP = (NSLOT + G - 1) / G;
     static_for<0, NGRP>([&](auto gcst) __attribute__((always_inline)) {
     constexpr int q0 = decltype(gcst)::value * G;
-    constexpr int q1 = q0 + G < TPW ? q0 + G : TPW;
+    constexpr int q1 = q0 + G < NSLOT ? q0 + G : NSLOT;
     double raw[G][NJC][3];
     static_for<q0, q1>([&](auto qcst) __attribute__((always_inline)) {
         constexpr TileTab<D, PIPE> tab{};
-        constexpr int q = decltype(qcst)::value;
+        constexpr int qi = decltype(qcst)::value;   // position in the plan; q: the slot
+        constexpr int q = PLAN::slot(qi);
         constexpr int t = q * D::NWAVES + W;
-        if constexpr (tab.forms(t, W)) {
+        if constexpr (PLAN::forms(q)) {
             constexpr int ti = tab.ti[t], tj = tab.tj[t];
             if constexpr (ti < PVT) {
                 // H^(br, bc), br = blk0(ti) + g (this lane's k block), bc = the block of column j of tile column tj; stored
@@ -398,7 +410,7 @@ VS_DEV void p1s_entries(d4 (&acc)[TPW], const double* __restrict__ sm, int lane)
                 for (int ks = 0; ks < NJC; ++ks) {
                     const double* Hk = Hp + (ks / 3) * D::NJPAIR * 9 + sa * (ks % 3);
 #pragma unroll
-                    for (int d = 0; d < 3; ++d) raw[q - q0][ks][d] = Hk[d * st];
+                    for (int d = 0; d < 3; ++d) raw[qi - q0][ks][d] = Hk[d * st];
                 }
             } else if constexpr (tj < PVT) {
                 constexpr int b0c = (16 * tj) / NJC;
@@ -407,7 +419,7 @@ VS_DEV void p1s_entries(d4 (&acc)[TPW], const double* __restrict__ sm, int lane)
                 const int bcc = b0c + g, bc = bcc < HC ? bcc : HC - 1;
 #pragma unroll
                 for (int ks = 0; ks < NJC; ++ks)
-                    raw[q - q0][ks][0] = sRb[(((ks / 3) * (NV + 1) + crc) * HC + bc) * 3 + (ks % 3)];
+                    raw[qi - q0][ks][0] = sRb[(((ks / 3) * (NV + 1) + crc) * HC + bc) * 3 + (ks % 3)];
             }
         }
     });
@@ -415,11 +427,12 @@ VS_DEV void p1s_entries(d4 (&acc)[TPW], const double* __restrict__ sm, int lane)
     double opa[G][NJC], opb[G][NJC];
     static_for<q0, q1>([&](auto qcst) __attribute__((always_inline)) {
         constexpr TileTab<D, PIPE> tab{};
-        constexpr int q = decltype(qcst)::value;
+        constexpr int qi = decltype(qcst)::value;
+        constexpr int q = PLAN::slot(qi);
         constexpr int t = q * D::NWAVES + W;
 #pragma unroll
-        for (int ks = 0; ks < NJC; ++ks) { opa[q - q0][ks] = 0.0; opb[q - q0][ks] = 0.0; }
-        if constexpr (tab.forms(t, W)) {
+        for (int ks = 0; ks < NJC; ++ks) { opa[qi - q0][ks] = 0.0; opb[qi - q0][ks] = 0.0; }
+        if constexpr (PLAN::forms(q)) {
             constexpr int ti = tab.ti[t], tj = tab.tj[t];
             // rows / columns of the dummy unknowns exist in the last joint tile row / column only (compile time)
             constexpr bool DUMMY_ROWS = 16 * ti + 16 > D::NUY, DUMMY_COLS = 16 * tj + 16 > D::NUY;
@@ -428,18 +441,18 @@ VS_DEV void p1s_entries(d4 (&acc)[TPW], const double* __restrict__ sm, int lane)
 #pragma unroll
                 for (int ks = 0; ks < NJC; ++ks) {
                     const int h3 = 3 * (ks / 3);
-                    const double hl = fma(raw[q - q0][ks][2], Lq[tj % 3][h3 + 2],
-                                          fma(raw[q - q0][ks][1], Lq[tj % 3][h3 + 1], raw[q - q0][ks][0] * Lq[tj % 3][h3]));
-                    opa[q - q0][ks] = (!DUMMY_ROWS || okm) ? LqM[ti % 3][ks] : 0.0;   // A: row j of tile row ti sits in k block g
-                    opb[q - q0][ks] = (!DUMMY_COLS || okn) ? hl : 0.0;
+                    const double hl = fma(raw[qi - q0][ks][2], Lq[tj % 3][h3 + 2],
+                                          fma(raw[qi - q0][ks][1], Lq[tj % 3][h3 + 1], raw[qi - q0][ks][0] * Lq[tj % 3][h3]));
+                    opa[qi - q0][ks] = (!DUMMY_ROWS || okm) ? LqM[ti % 3][ks] : 0.0;   // A: row j of tile row ti sits in k block g
+                    opb[qi - q0][ks] = (!DUMMY_COLS || okn) ? hl : 0.0;
                 }
             } else if constexpr (tj < PVT) {
                 const bool okr = 16 * (ti - PVT) + j <= NV;
                 const bool okn = 16 * tj + j < D::NUY;
 #pragma unroll
                 for (int ks = 0; ks < NJC; ++ks) {
-                    opa[q - q0][ks] = okr ? raw[q - q0][ks][0] : 0.0;
-                    opb[q - q0][ks] = (!DUMMY_COLS || okn) ? LqM[tj % 3][ks] : 0.0;
+                    opa[qi - q0][ks] = okr ? raw[qi - q0][ks][0] : 0.0;
+                    opb[qi - q0][ks] = (!DUMMY_COLS || okn) ? LqM[tj % 3][ks] : 0.0;
                 }
             }
         }
@@ -447,16 +460,17 @@ VS_DEV void p1s_entries(d4 (&acc)[TPW], const double* __restrict__ sm, int lane)
     __builtin_amdgcn_sched_barrier(0);
     static_for<q0, q1>([&](auto qcst) __attribute__((always_inline)) {
         constexpr TileTab<D, PIPE> tab{};
-        constexpr int q = decltype(qcst)::value;
+        constexpr int qi = decltype(qcst)::value;
+        constexpr int q = PLAN::slot(qi);
         constexpr int t = q * D::NWAVES + W;
         d4 c = d4{0.0, 0.0, 0.0, 0.0}, c2 = d4{0.0, 0.0, 0.0, 0.0};
-        if constexpr (tab.forms(t, W)) {
+        if constexpr (PLAN::forms(q)) {
             constexpr int ti = tab.ti[t], tj = tab.tj[t];
             if constexpr (tj < PVT) {
 #pragma unroll
                 for (int ks = 0; ks < NJC; ks += 2) {   // two accumulators (a dependent FP64 matrix instruction issues every ~95 cycles)
-                    c = __builtin_amdgcn_mfma_f64_16x16x4f64(opa[q - q0][ks], opb[q - q0][ks], c, 0, 0, 0);
-                    c2 = __builtin_amdgcn_mfma_f64_16x16x4f64(opa[q - q0][ks + 1], opb[q - q0][ks + 1], c2, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f64_16x16x4f64(opa[qi - q0][ks], opb[qi - q0][ks], c, 0, 0, 0);
+                    c2 = __builtin_amdgcn_mfma_f64_16x16x4f64(opa[qi - q0][ks + 1], opb[qi - q0][ks + 1], c2, 0, 0, 0);
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) c[r] += c2[r];
@@ -469,11 +483,11 @@ VS_DEV void p1s_entries(d4 (&acc)[TPW], const double* __restrict__ sm, int lane)
     // throttle x throttle tiles: all operand pairs of a tile are requested before its chain starts.  The k-steps start at
     // the first stage any column of the tile can see (tau_i = 0 up to a column's first stage); a row that does not store
     // an earlier stage (Smem::ac_first) meets only such columns in the lower triangle and reads a zero there.
-    static_for<0, TPW>([&](auto qcst) __attribute__((always_inline)) {
+    static_for<0, NSLOT>([&](auto qcst) __attribute__((always_inline)) {
         constexpr TileTab<D, PIPE> tab{};
-        constexpr int q = decltype(qcst)::value;
+        constexpr int q = PLAN::slot(decltype(qcst)::value);
         constexpr int t = q * D::NWAVES + W;
-        if constexpr (tab.forms(t, W)) {
+        if constexpr (PLAN::forms(q)) {
             constexpr int ti = tab.ti[t], tj = tab.tj[t];
             if constexpr (ti >= PVT && tj >= PVT) {
                 constexpr int K0 = tile_first_stage<D>(tj);   // first k-step (stage i' = i - 1)

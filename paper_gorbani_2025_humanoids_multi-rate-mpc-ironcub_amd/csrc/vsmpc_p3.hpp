@@ -1,6 +1,7 @@
 // P2 + P3 of the tuned solve kernels: the input-cost terms and the blocked Cholesky factorisation (panel streams, tile
 // inverses, work lists, the pipelined and the plain schedule).
 #pragma once
+#include "vsmpc_p1_struct.hpp"
 #include "vsmpc_smem.hpp"
 
 namespace vsmpc {
@@ -390,26 +391,21 @@ constexpr int pipe_inverse_wave(int p) {
     return (n3 <= n1 && n3 <= n2) ? 3 : (n2 <= n1 ? 2 : 1);
 }
 
-template <class D, int TPW, int W, bool DEBUG, bool PIPE = false>
-VS_DEV void cholesky_wave(const double* __restrict__ sCfg, d4 (&acc)[TPW], double* __restrict__ sM, double* __restrict__ sInvD,
-                          const double* __restrict__ sGy, const double* __restrict__ sVprev, int* __restrict__ sFlags,
-                          double* __restrict__ sXinv, double* __restrict__ sW, double* __restrict__ dbgL, int lane,
-                          int crow, int lrow, double* sZ_) {
+// P2 for the slots of PLAN (see p1s_entries): the input-cost terms are added to the entries in registers.
+template <class D, int TPW, int W, bool PIPE, class PLAN>
+VS_DEV void p2_terms(const double* __restrict__ sCfg, d4 (&acc)[TPW], const double* __restrict__ sGy,
+                     const double* __restrict__ sVprev, int lane) {
     constexpr TileTab<D, PIPE> tab{};
-    constexpr WaveLists<D, TPW, W, PIPE> wl{};
-    using S = Smem<D>;
     constexpr int PVT = D::PVT;
-    constexpr int GL = D::NZ & 15;  // local row of the gradient row (row NZ) in the last tile row
-    if constexpr (D::WG_PER_CU == 1) pin_tiles_agpr<TPW>(acc);
     // ---- P2: the input-cost terms, by kind of tile (compile time).  A joint diagonal tile gets the joint weights on its
     // diagonal, a tile of throttle rows x joint columns only the regularisation term of the gradient row, and only the
     // throttle x throttle tiles go through the general (branchy) input_cost_term.  (Through v13 every element of every
     // such tile went through it: 23k instructions of control flow at the 2x horizon, whose saved execution masks were what
     // pushed scalar registers into vector lanes and accumulator tiles into scratch.)
-    static_for<0, TPW>([&](auto qcst) __attribute__((always_inline)) {
-        constexpr int q = decltype(qcst)::value;
+    static_for<0, PLAN::count>([&](auto qcst) __attribute__((always_inline)) {
+        constexpr int q = PLAN::slot(decltype(qcst)::value);
         constexpr int t = q * D::NWAVES + W;
-        if constexpr (tab.forms(t, W)) {
+        if constexpr (PLAN::forms(q)) {
             constexpr int ti = tab.ti[t], tj = tab.tj[t];
             if constexpr (ti == tj && 16 * ti + 16 <= D::NU) {
                 // unit weights on the reduced joint unknowns (U^T W U / 2 = |y|^2 / 2 + |n|^2 / 2, costsVSMPC.cpp:375-381,
@@ -431,12 +427,111 @@ VS_DEV void cholesky_wave(const double* __restrict__ sCfg, d4 (&acc)[TPW], doubl
             }
         }
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// The small-batch kind (solve_kernel_small): when a wavefront forms which of its tiles.  Nothing of P1s lies under the ring
+// there (Smem<D, true>), so only what the first streams need is formed in front of them:
+//   instalment 0  in front of stream 0: tile column 0, dealt over all four wavefronts -- wavefronts 1..3 form the column-0
+//                 tiles they will later hold (in the slots the factors come back to), wavefront 0 takes two of wavefront 1's
+//                 (wavefront 1 holds one more than the others) -- each adds its P2 term and stores the tile into ring slot 0
+//   instalment 1  wavefronts 1..3 beside stream 0 (which wavefront 0 runs alone, in two row slots): tile column 1, which the
+//                 update between streams 0 and 1 needs, and the next tiles in slot order up to SMALL_BESIDE0 per wavefront
+//   instalment 2  wavefronts 1..3 beside stream 1, in front of rest-update(0), the first update that touches them: the rest
+// Per tile the order of operations is the shipped one: entries, P2 term, panel updates 0, 1, ...  No barrier moves.
+// ------------------------------------------------------------------------------------------------
+constexpr int SMALL_BESIDE0 = 4;
+template <class D>
+constexpr bool small_wave0_forms(int ti) {   // column-0 tiles wavefront 0 forms in place of their holder, wavefront 1
+    return ti % (D::NWAVES - 1) == 0 && ti / (D::NWAVES - 1) < (D::NT + 1) / 4;
+}
+template <class D, int TPW, int W>
+constexpr int small_instalment(int q) {      // -1: this wavefront never forms slot q
+    constexpr TileTab<D, true> tab{};
+    const int t = q * D::NWAVES + W;
+    if (!tab.ok(t)) return -1;
+    if (W == 0) return small_wave0_forms<D>(tab.ti[t]) ? 0 : -1;
+    if (tab.tj[t] == 0) return (W == 1 && small_wave0_forms<D>(tab.ti[t])) ? -1 : 0;
+    int n = 0;
+    for (int b = 0; b < q; ++b) n += (tab.ok(b * D::NWAVES + W) && tab.tj[b * D::NWAVES + W] > 0) ? 1 : 0;
+    return (tab.tj[t] == 1 || n < SMALL_BESIDE0) ? 1 : 2;
+}
+template <class D, int TPW, int W, int INST>
+struct SmallPlan {
+    static constexpr bool SMALL = true;
+    static constexpr int count_() {
+        int n = 0;
+        for (int q = 0; q < TPW; ++q) n += small_instalment<D, TPW, W>(q) == INST ? 1 : 0;
+        return n;
+    }
+    static constexpr int count = count_();
+    static constexpr int slot(int a) {
+        for (int q = 0; q < TPW; ++q)
+            if (small_instalment<D, TPW, W>(q) == INST && a-- == 0) return q;
+        return 0;
+    }
+    static constexpr bool forms(int) { return true; }
+};
+// every tile is formed exactly once: column 0 by the four wavefronts together, the others by their holders
+template <class D, int TPW>
+constexpr bool small_plan_complete() {
+    constexpr TileTab<D, true> tab{};
+    int col0[D::NT] = {};
+    for (int q = 0; q < TPW; ++q) {
+        const int i0 = small_instalment<D, TPW, 0>(q);
+        if (i0 >= 0) col0[tab.ti[q * D::NWAVES]] += 1;
+        const int inst[3] = {small_instalment<D, TPW, 1>(q), small_instalment<D, TPW, 2>(q), small_instalment<D, TPW, 3>(q)};
+        for (int w = 1; w < D::NWAVES; ++w) {
+            const int t = q * D::NWAVES + w;
+            if (!tab.ok(t)) continue;
+            if (tab.tj[t] == 0) col0[tab.ti[t]] += inst[w - 1] == 0 ? 1 : 0;
+            else if (inst[w - 1] < 1) return false;
+        }
+    }
+    for (int i = 0; i < D::NT; ++i)
+        if (col0[i] != 1) return false;
+    return true;
+}
+// one instalment of wavefront W: entries, P2 term, and (instalment 0) the tile into the first panel column
+template <class D, int TPW, int W, int INST>
+VS_DEV void small_form(const double* __restrict__ sCfg, d4 (&acc)[TPW], double* __restrict__ sM, const double* __restrict__ sGy,
+                       const double* __restrict__ sVprev, int lane, int crow) {
+    using PLAN = SmallPlan<D, TPW, W, INST>;
+    static_assert(small_plan_complete<D, TPW>(), "every tile is formed exactly once");
+    if constexpr (PLAN::count > 0) {
+        p1s_entries<D, TPW, W, true, PLAN>(acc, sM - Smem<D>::oM, lane);
+        p2_terms<D, TPW, W, true, PLAN>(sCfg, acc, sGy, sVprev, lane);
+        if constexpr (INST == 0) {
+            constexpr TileTab<D, true> tab{};
+            static_for<0, PLAN::count>([&](auto acst) __attribute__((always_inline)) {
+                constexpr int q = PLAN::slot(decltype(acst)::value);
+                double* T = sM + tile_off_c<D>(tab.ti[q * D::NWAVES + W], 0) + crow;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) T[4 * r * 17] = acc[q][r];
+            });
+        }
+    }
+}
+
+template <class D, int TPW, int W, bool DEBUG, bool PIPE = false, bool SMALL = false>
+VS_DEV void cholesky_wave(const double* __restrict__ sCfg, d4 (&acc)[TPW], double* __restrict__ sM, double* __restrict__ sInvD,
+                          const double* __restrict__ sGy, const double* __restrict__ sVprev, int* __restrict__ sFlags,
+                          double* __restrict__ sXinv, double* __restrict__ sW, double* __restrict__ dbgL, int lane,
+                          int crow, int lrow, double* sZ_) {
+    constexpr TileTab<D, PIPE> tab{};
+    constexpr WaveLists<D, TPW, W, PIPE> wl{};
+    using S = Smem<D>;
+    constexpr int PVT = D::PVT;
+    constexpr int GL = D::NZ & 15;  // local row of the gradient row (row NZ) in the last tile row
+    if constexpr (D::WG_PER_CU == 1) pin_tiles_agpr<TPW>(acc);
+    // ---- P2 (the small-batch kind adds the terms where it forms the tiles: small_form)
+    if constexpr (!SMALL) p2_terms<D, TPW, W, PIPE, AllSlots<D, TPW, W, PIPE>>(sCfg, acc, sGy, sVprev, lane);
     if constexpr (D::WG_PER_CU == 1) pin_tiles_agpr<TPW>(acc);
     // ---- P3: tile column 0 goes to LDS; every later column is stored by the update that completes it
 #pragma unroll
     for (int q = 0; q < TPW; ++q) {
         const int t = q * D::NWAVES + W;
-        if (tab.forms(t, W) && tab.tj[t] == 0) {
+        if (!SMALL && tab.forms(t, W) && tab.tj[t] == 0) {
             double* T = sM + tile_off_c<D>(tab.ti[t], 0) + crow;
 #pragma unroll
             for (int r = 0; r < 4; ++r) T[4 * r * 17] = acc[q][r];
@@ -483,6 +578,16 @@ VS_DEV void cholesky_wave(const double* __restrict__ sCfg, d4 (&acc)[TPW], doubl
                 } else {                                              // any other horizon: the C++ stream
                     if (W == 0 && panel_factor<D, NPIV_LAST>(sM, sInvD, p, lane) && lane == 0) sFlags[0] = 1;
                 }
+            } else if constexpr (p == 0 && SMALL) {
+                // small-batch kind: wavefront 0 takes panel 0 alone, in nshare0 row slots; the others form tiles meanwhile.
+                // (Measured against wavefront 1 sharing the stream as in the shipped kernel and forming its column-1 tiles behind
+                // its share: 32.4-32.8 us per 256-launch against 33.1-33.3, profiles/small_batch_bench_alternating.txt.)
+                static_assert(!SMALL || nshare0 <= 3, "row slots of one stream");
+                if constexpr (W == 0) {
+                    if (panel_dpp<D, nshare0>(sM, sInvD, p, lane, 0, diag, scratch) && lane == 0) sFlags[0] = 1;
+                } else {
+                    small_form<D, TPW, W, 1>(sCfg, acc, sM, sGy, sVprev, lane, crow);
+                }
             } else if constexpr (p == 0) {
                 if (W < nshare0) {
                     const int bad = panel_dpp<D, 1>(sM, sInvD, p, lane, W, diag, scratch);
@@ -520,6 +625,7 @@ VS_DEV void cholesky_wave(const double* __restrict__ sCfg, d4 (&acc)[TPW], doubl
             };
             if constexpr (p == 0) park_next_diag();
             if constexpr (p >= 1 && W >= 1) {
+                if constexpr (SMALL && p == 1) small_form<D, TPW, W, 2>(sCfg, acc, sM, sGy, sVprev, lane, crow);
                 // the finished tiles of column p - 1 come back into the registers that held them (the factor P5 reads; the
                 // gradient row -> right-hand side of the back-substitution).  Here, beside the stream, not between two streams:
                 // their ring slot stays intact until the barrier that ends this stream.

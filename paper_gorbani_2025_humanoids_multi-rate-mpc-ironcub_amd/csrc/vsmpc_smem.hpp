@@ -43,7 +43,10 @@ VS_DEV int fresh_lane() {
 //           back-substitution, the state trajectory and the stage forcing terms; the corner stays where it is
 // Paper horizon: 71 KB in total, so two workgroups fit one CU.
 // ------------------------------------------------------------------------------------------------
-template <class D>
+// SMALL: the carve-up of the small-batch kind (solve_kernel_small, one workgroup per CU, up to 160 KB): the arrays of P1a /
+// P1s lie BEHIND everything P3..P6 use instead of under the X region and the ring, so that a wavefront can still form tile
+// entries from them while the panel streams run.  Every other offset is the shipped one.
+template <class D, bool SMALL = false>
 struct Smem {
     // the dual box QP and the chain-free first pass need the throttle block to span exactly two tile rows
     static constexpr bool DUALQP = D::NT - 2 == D::PVT && D::NU % 16 == 0 && D::NV >= 20 && D::NV <= 32;
@@ -95,7 +98,9 @@ struct Smem {
     // P1a: jet thrust trajectories [NJROW][N] and the affine column's momentum forcing [2][N][3], at the head of the X
     // region (the X tiles are not written before P3)
     static constexpr int NJROW = D::NV + NTH + 1;
-    static constexpr int oJetT = oXinv;
+    // (small-batch kind: behind the ring, the corner, the parked diagonal tile and the scratch of P4..P6)
+    static constexpr int oP1Small = ((oR + D::L_TILES * D::TS + D::TS > endScratch ? oR + D::L_TILES * D::TS + D::TS : endScratch) + 3) & ~3;
+    static constexpr int oJetT = SMALL ? oP1Small : oXinv;
     static constexpr int oGA = oJetT + NJROW * D::N;
     // P1s (structured condensing, Dims::STRUCT_P1): behind them, across the rest of the X region and R
     //   sH [2][NJPAIR][3][3]      block sums of H(i, i') over (row block, column block) pairs of the joint blocks
@@ -139,8 +144,18 @@ struct Smem {
     static constexpr size_t bytes = size_t(total) * sizeof(double);
     static constexpr size_t bytes_struct = size_t(total_struct) * sizeof(double);
     static_assert(bytes <= 160 * 1024 && bytes_struct <= 160 * 1024, "LDS budget of one CU");
-    static_assert(D::WG_PER_CU < 2 || (bytes <= 80 * 1024 && bytes_struct <= 80 * 1024), "two workgroups per CU");
+    static_assert(SMALL || D::WG_PER_CU < 2 || (bytes <= 80 * 1024 && bytes_struct <= 80 * 1024), "two workgroups per CU");
+    // small-batch kind: nothing of P1a / P1s (jet trajectories, sGA, sH, sRb, sW3, sAc, reference window, zeros) overlaps the
+    // X region, the ring, the corner, the parked next diagonal tile or the scratch of P4..P6
+    static_assert(!SMALL || (D::STRUCT_P1 && !D::STRUCT_LONG), "the small-batch kind exists for short structured horizons");
+    static_assert(!SMALL || (oJetT >= oNextDiag + D::TS && oJetT >= endScratch && oJetT >= oXinv + NXT * D::TS && endP1s <= total_struct),
+                  "small-batch kind: the arrays of P1 stay apart from everything P3..P6 write");
 };
+
+// Horizons with the small-batch kind of the solve kernel: those whose shipped kernel is the pipelined structured form at two
+// workgroups per CU (when the batch does not exceed the CUs the second workgroup slot of a CU is empty anyway)
+template <class D>
+constexpr bool has_small_kind() { return D::STRUCT_P1 && !D::STRUCT_LONG && D::WG_PER_CU == 2; }
 
 // tile (i, j), j <= i, of the factor in LDS: panel columns left of the throttle corner live in a ring of two
 // (even columns at tile 0, odd ones at tile RING_A), the corner is dense behind the ring

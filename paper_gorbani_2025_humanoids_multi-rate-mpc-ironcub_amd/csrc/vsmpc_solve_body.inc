@@ -1,7 +1,8 @@
 // Body of the solve kernels (vsmpc_kernels.hip), P0 to P6, included inside solve_kernel (TUNED = false) and
 // solve_kernel_tuned (TUNED = true): each kernel has the template parameters D and FORM, declares `constexpr bool STAMPS`
 // and `constexpr bool TUNED`, and has the arguments cfg, in, batch and (tuned kind) tun before it; the trailing arguments
-// are read through late_args().  A textual body (not an inlined device function) keeps solve_kernel's code object
+// are read through late_args().  `constexpr bool SMALL` selects the small-batch kind (solve_kernel_small: structured form only,
+// its own LDS carve-up and tile-forming schedule, see SmallPlan in vsmpc_p3.hpp).  A textual body (not an inlined device function) keeps solve_kernel's code object
 // instruction for instruction what it was before solve_kernel_tuned existed (an inlined function did not: tools/isa_diff.py).
     // (the trailing kernel parameters are read through late_args(), see SolveArgs)
 #define VS_STAMP(i)                                                                         \
@@ -26,7 +27,8 @@
             t_mark = t_now;                                                \
         }                                                                  \
     } while (0)
-    using S = Smem<D>;
+    using S = Smem<D, SMALL>;   // (SMALL moves the arrays of P1a / P1s only)
+    static_assert(!SMALL || (FORM == 1 && !TUNED), "the small-batch kind is the structured form of the shared kind");
     constexpr bool FUSED_DISPATCH = FORM == 1;   // entries + P2 + P3 behind one wave dispatch (see P1)
     // the structured form runs P3 pipelined: wavefront 0 factors the panels, wavefronts 1..3 hold all tiles (TileTab, cholesky_wave)
     constexpr bool PIPE = FORM == 1;
@@ -140,8 +142,10 @@
     // brings P1 under the 256 registers a wavefront gets when two workgroups share a CU.   (systemDynamicsVSMPC.cpp:384-429)
     constexpr int NJROW = D::NV + NTH + 1, ZROW = D::NV + NTH;  // + an all-zero row for the joint and padding columns
     double* sJetT = sXinv;                    // [NJROW][N]; the X tiles are not written before P3
+    if constexpr (SMALL) sJetT = smem + S::oJetT;   // (the small-batch kind keeps it apart from them)
+    static_assert(SMALL || S::oJetT == S::oXinv, "the jet trajectories lie at the head of the X region");
     double* sGA = sJetT + NJROW * D::N;       // [2][N][3]: A_mom T_k of the affine column, per half
-    static_assert(D::NV + NTH <= 64 && NJROW * D::N + 6 * D::N <= S::NXT * D::TS, "jet trajectories fit the X region");
+    static_assert(D::NV + NTH <= 64 && (SMALL || NJROW * D::N + 6 * D::N <= S::NXT * D::TS), "jet trajectories fit the X region");
     // Runs in the wavefront whose lanes 0..3 linearised the jets (p0_linearize), straight behind that, while the other
     // wavefronts finish their pieces of P0: LDS operations of one wavefront execute in order, no barrier needed.
     if (wave == 1) {
@@ -223,17 +227,17 @@
         static_assert(D::STRUCT_P1, "structured condensing is instantiated for horizons with Dims::STRUCT_P1");
         VS_TIC();
         if (wave < 2) {
-            p1s_chain<D, 0>(cfg, wave, lane, smem);
+            p1s_chain<D, 0, SMALL>(cfg, wave, lane, smem);
             if (wave == 0) p0_joint_reduction<D, QR_P0_STEPS, NJC>(smem, lane);   // (second half; writes Bj and sQR, which nobody touches
                                                                         // before the barrier below)
         } else {
-            p1s_chain<D, 1>(cfg, wave - 2, lane, smem);
+            p1s_chain<D, 1, SMALL>(cfg, wave - 2, lane, smem);
         }
         VS_TOC(0);
         __syncthreads();
         VS_TOC(1);
         if constexpr (!D::STRUCT_LONG) {
-            p1s_contract<D>(smem, tid);
+            p1s_contract<D, SMALL>(smem, tid);
             __syncthreads();
         }
         VS_TOC(3);
@@ -245,12 +249,24 @@
             // stamps of the P1 / P2 / P3 boundaries sit inside the branch.)
             auto tail = [&](auto wcst) __attribute__((always_inline)) {
                 constexpr int W = decltype(wcst)::value;
-                p1s_entries<D, TPW, W, PIPE>(acc, smem, lane);
+                if constexpr (SMALL) {
+                    // only tile column 0, dealt over the four wavefronts, P2 term and hand-over to LDS included; the other
+                    // tiles are formed beside the first two panel streams (cholesky_wave).  Stamps 2 and 3 therefore both
+                    // mark "column 0 is in the ring": the rest of the entries and of P2 lies between stamps 3 and 4.
+                    static_for<0, TPW>([&](auto qcst) __attribute__((always_inline)) {
+                        constexpr int q = decltype(qcst)::value;
+                        if constexpr (small_instalment<D, TPW, W>(q) < 0) acc[q] = d4{0.0, 0.0, 0.0, 0.0};
+                    });
+                    const int ln0 = fresh_lane();
+                    small_form<D, TPW, W, 0>(sCfg, acc, Lb, smem + S::oQR + S::QR_GY, sVprev, ln0, (ln0 >> 4) * 17 + (ln0 & 15));
+                } else {
+                    p1s_entries<D, TPW, W, PIPE>(acc, smem, lane);
+                }
                 VS_TOC(2);
-                __syncthreads();   // the LDS arrays of P1s lie under the ring P3 is about to fill
+                __syncthreads();   // the LDS arrays of P1s lie under the ring P3 is about to fill (not in the small-batch kind)
                 VS_STAMP(2);
                 double* dbgLw = nullptr;
-                if constexpr (STAMPS) {
+                if constexpr (STAMPS && !SMALL) {   // (a dump needs all tiles at one point: the launcher asks the shipped kernel)
                     constexpr TileTab<D, PIPE> tab{};
                     double* dbgM = late_args()->dbgM;
                     double* dbgL = late_args()->dbgL;
@@ -281,7 +297,7 @@
                 VS_STAMP(3);
                 if constexpr (D::WG_PER_CU == 1) pin_tiles_agpr<TPW>(acc);
                 const int ln = fresh_lane();
-                cholesky_wave<D, TPW, W, STAMPS, PIPE>(sCfg, acc, Lb, sInvD, smem + S::oQR + S::QR_GY, sVprev, sFlags, sXinv, sW, dbgLw, ln,
+                cholesky_wave<D, TPW, W, STAMPS, PIPE, SMALL>(sCfg, acc, Lb, sInvD, smem + S::oQR + S::QR_GY, sVprev, sFlags, sXinv, sW, dbgLw, ln,
                                                       (ln >> 4) * 17 + (ln & 15), (ln & 15) * 17 + (ln >> 4), sZ);
                 if constexpr (STAMPS) {
                     if (dbgLw != nullptr) {  // debug/parity only: the factor; diagonal tiles were written while they were panels

@@ -100,6 +100,24 @@ class BatchedVSMPC:
             raise ValueError(f"kernel form {form}: {self.lib.vsmpc_strerror(prev).decode()}")
         return prev
 
+    SMALL_BATCH_MODES = {"auto": 0, "never": 1, "always": 2}
+
+    def set_small_batch_kernel(self, mode) -> int:
+        """vsmpc_set_small_batch_kernel (include/vsmpc.h): which kernel serves batches that do not exceed the device's
+        CUs -- "auto" (0) the small-batch kind there, "never" (1), "always" (2) where the horizon has the kind; returns
+        the previous setting (0..2)."""
+        prev = self.lib.vsmpc_set_small_batch_kernel(self._h, int(self.SMALL_BATCH_MODES.get(mode, mode)))
+        if prev < 0:
+            raise ValueError(f"small-batch kernel mode {mode}: {self.lib.vsmpc_strerror(prev).decode()}")
+        return prev
+
+    def uses_small_batch_kernel(self, batch: int) -> bool:
+        """vsmpc_small_batch_kernel_for: does a solve of `batch` instances run on the small-batch kind of the kernel?"""
+        r = self.lib.vsmpc_small_batch_kernel_for(self._h, int(batch))
+        if r < 0:
+            raise ValueError(f"batch {batch}: {self.lib.vsmpc_strerror(r).decode()}")
+        return bool(r)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self.lib.vsmpc_destroy(self._h)
