@@ -151,6 +151,8 @@ int vsmpc_create(const vsmpc_config* cfg, int device, int max_batch, vsmpc_handl
 #define VSMPC_CREATE_CERTIFY 0x20u      /* device staging of vsmpc_certify_batch: max_batch x (nCon + VSMPC_CERT_SIZE) doubles
                                            for y and the certificate, max_batch x nVar for x, max_batch x VSMPC_TUNE_SIZE
                                            for the rows.  Bit 0x10 is reserved (refused like every unknown bit) */
+#define VSMPC_CREATE_ADJOINT 0x40u      /* what vsmpc_adjoint_batch needs (below): the runtime-sized kernel's workspace where the
+                                           handle has none, and the staging of the host-pointer entry */
 int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned flags, vsmpc_handle** out);
 void vsmpc_destroy(vsmpc_handle* h);
 
@@ -237,6 +239,62 @@ int vsmpc_sensitivity_batch(vsmpc_handle* h, const double* in, int batch, double
 int vsmpc_sensitivity_batch_device(vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_first_move,
                                    int* d_status, int* d_iters, double* d_dx_dx0, double* d_dfm_dx0, int* d_active,
                                    int* d_sens_flags, void* stream);
+
+/*
+ * Adjoint of the solve: the gradient of a scalar loss L on the plan with respect to the measured state X0 and to the
+ * tunables (the weights and the throttle box), from the cotangents xbar = dL/dx ([batch][nVar], reference variable order) and,
+ * optionally, fmbar = dL/d first_move ([batch][24]; NULL = none).  The QP is solved exactly, so the gradient is one more
+ * linear solve with the factor the solver holds: with K the KKT matrix of the final active set, K [a; b] = [xbar; 0] gives
+ * dL/dX0 = b on the initial-state rows, dL/d throttle limit = the sum of b over the throttles on that limit, and
+ * dL/dw = -a' (dH/dw x + dg/dw) for every weight ("Adjoint"; executable model: tests/adjoint_model.py).  O(N)
+ * recursions on 26-vectors and one right-hand side through the factor: no Jacobian is formed.
+ * Needs a handle created with VSMPC_CREATE_ADJOINT (both entries; otherwise VSMPC_ERR_UNSUPPORTED_CONFIG, and
+ * vsmpc_strerror names the flag).  It solves with adjoint_kernel_rt / adjoint_kernel_rt_tuned, the runtime-sized kernel with
+ * five more phases behind the solve, on tuned handles too: a tuned handle gets no fast path here, as for the sensitivities.
+ * tunables: rows of vsmpc_pack_tunables, one per instance, or NULL = the handle's configuration for every instance (bit for
+ * bit what rows packed from the handle's configuration give).  Per instance:
+ *   x, first_move, status, iters   what vsmpc_solve_batch[_tuned] returns (bit for bit on a runtime handle, to rounding on a
+ *                                  tuned one, with the same iterations)
+ *   grad_x0[26]                    dL/dX0 (X0 = in[VSMPC_IN_X0 .. +26]; the other record fields are held fixed)
+ *   grad_cfg[VSMPC_GRAD_SIZE]      dL/d(field) in the order of the vsmpc_config fields (VSMPC_GRAD_* below): with respect to
+ *                                  the values a caller writes -- weights, not their square roots; throttle limits in percent,
+ *                                  not warped.  Entry 31 is 0.
+ *   active[NV]                     final throttle states, as vsmpc_sensitivity_batch returns them
+ *   adj_flags                      VSMPC_ADJ_DEGENERATE: a non-pinned throttle is weakly or nearly active, by the rule and the
+ *                                  tolerances of VSMPC_SENS_DEGENERATE: the gradient is still written, that of the final active
+ *                                  set's affine piece, i.e. one-sided;
+ *                                  VSMPC_ADJ_UNSOLVED: status is not Solved, both gradients are zero
+ * A non-finite entry of xbar or fmbar makes that instance's gradients NaN (and no other instance's).  Every sum has an order
+ * fixed by the sizes alone: repeated and permuted batches are bit-identical.  in, xbar and status are required; every other
+ * output, tunables and fmbar may be NULL.  batch 0: VSMPC_OK, nothing touched; batch > vsmpc_max_batch(h):
+ * VSMPC_ERR_BATCH_TOO_LARGE.
+ */
+#define VSMPC_GRAD_W_COM_POS 0
+#define VSMPC_GRAD_W_COM_POS_ERR 3
+#define VSMPC_GRAD_W_LIN_MOM 6
+#define VSMPC_GRAD_W_RPY 9
+#define VSMPC_GRAD_W_RPY_ERR 12
+#define VSMPC_GRAD_W_ANG_MOM 15
+#define VSMPC_GRAD_W_DELTA_JOINT 18
+#define VSMPC_GRAD_W_THROTTLE 26
+#define VSMPC_GRAD_W_INITIAL_THROTTLE 27
+#define VSMPC_GRAD_W_REG_JOINT_POS 28
+#define VSMPC_GRAD_THROTTLE_MIN 29
+#define VSMPC_GRAD_THROTTLE_MAX 30
+#define VSMPC_GRAD_SIZE 32
+#define VSMPC_ADJ_DEGENERATE 0x1
+#define VSMPC_ADJ_UNSOLVED 0x2
+/* Host buffers; returns after the results are in them.  Batches beyond 256 instances run in chunks in stream order. */
+int vsmpc_adjoint_batch(vsmpc_handle* h, const double* in, const double* tunables, const double* xbar, const double* fmbar,
+                        int batch, double* x, double* first_move, int* status, int* iters, double* grad_x0, double* grad_cfg,
+                        int* active, int* adj_flags, void* stream);
+/* Same, all pointers are DEVICE pointers (d_tunables 16-byte aligned) and the call only enqueues work on `stream`.  Launches
+ * of one handle share its workspace: they must be ordered (one stream at a time), also against the handle's solves on a
+ * runtime handle. */
+int vsmpc_adjoint_batch_device(vsmpc_handle* h, const double* d_in, const double* d_tunables, const double* d_xbar,
+                               const double* d_fmbar, int batch, double* d_x, double* d_first_move, int* d_status,
+                               int* d_iters, double* d_grad_x0, double* d_grad_cfg, int* d_active, int* d_adj_flags,
+                               void* stream);
 
 /*
  * Duals and a KKT certificate of a GIVEN primal, for every instance of a batch.  The QP is the reference-ordered dense one

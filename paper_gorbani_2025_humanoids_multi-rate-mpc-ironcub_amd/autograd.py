@@ -1,0 +1,97 @@
+"""The MPC solve as a differentiable torch operation: a loss on the plan backpropagates to the measured state X0 and to the
+gains (the weights and the throttle box) through vsmpc_adjoint_batch_device -- one more linear solve per instance with the
+factor the solver holds, no Jacobian ("Adjoint").
+
+    mpc = BatchedVSMPC(cfg, max_batch=B, adjoint=True)
+    x, first_move, status = plan(mpc, records, x0, gains)        # records [B, n_in], x0 [B, 26], gains [B, GRAD_SIZE]
+    loss(x, first_move).backward()                               # x0.grad, gains.grad
+
+All numerics run in libvsmpc.so (HIP); there is no CPU path.
+"""
+from __future__ import annotations
+
+import dataclasses
+
+import numpy as np
+import torch
+
+from . import layout as L
+from .solver import BatchedVSMPC, pack_tunables
+
+
+def gains_of(cfg: L.MPCConfig) -> np.ndarray:
+    """the tunable fields of `cfg` as one row of field values in L.GRAD_* order (entry 31 is 0)"""
+    row = np.zeros(L.GRAD_SIZE)
+    for name, off, n in L.GRAD_FIELDS:
+        row[off:off + n] = getattr(cfg, name)
+    return row
+
+
+def configs_of(cfg: L.MPCConfig, gains: np.ndarray) -> list:
+    """one MPCConfig per row of `gains` ([B, GRAD_SIZE] field values, L.GRAD_* order): `cfg` with its tunable fields replaced"""
+    out = []
+    for row in np.asarray(gains, dtype=np.float64):
+        kw = {name: (float(row[off]) if n == 1 else tuple(float(v) for v in row[off:off + n])) for name, off, n in L.GRAD_FIELDS}
+        out.append(dataclasses.replace(cfg, **kw))
+    return out
+
+
+class PlanFunction(torch.autograd.Function):
+    """forward(mpc, records, x0, gains, info) -> (x [B, n_var], first_move [B, 24], status [B] int32)
+
+    Forward: `x0` [B, 26] is written into the X0 columns of a copy of `records` [B, n_in] (CUDA, float64) and the batch is
+    solved with the handle's device solve entry: the tuned kernel where the handle has one, and the per-instance-tunables
+    kind when `gains` [B, L.GRAD_SIZE] is given.  `gains` holds field values in L.GRAD_* order (weights and throttle limits
+    in percent, as an MPCConfig holds them); packing them into the kernels' rows goes through the HOST
+    (vsmpc_pack_tunables validates the values), which synchronises the stream once per forward.
+    Backward: one vsmpc_adjoint_batch_device call with the incoming cotangents of x and first_move; it returns the gradients
+    of x0 and of gains.  Every other record field is non-differentiable -- the linearisation depends on them, and that
+    derivative is not computed -- so `records` must not require grad.  Instances whose status is not Solved contribute
+    zero gradient; `info` (a dict, or None) receives "flags" (L.ADJ_*) and "active" of the backward call as CUDA tensors, so
+    that a caller can mask unsolved or degenerate instances.  Calls on one handle must be ordered on one stream."""
+
+    @staticmethod
+    def forward(ctx, mpc: BatchedVSMPC, records, x0, gains, info):
+        if records.requires_grad:
+            raise ValueError("records must not require grad: only X0 (passed as x0) and the gains are differentiable")
+        assert records.is_cuda and records.dtype == torch.float64 and records.shape[1] == mpc.n_in
+        B = records.shape[0]
+        assert tuple(x0.shape) == (B, L.N_STATES) and x0.dtype == torch.float64
+        d_in = records.detach().clone().contiguous()
+        d_in[:, L.IN_X0:L.IN_X0 + L.N_STATES] = x0.detach()
+        d_tun = None
+        if gains is not None:
+            assert tuple(gains.shape) == (B, L.GRAD_SIZE) and gains.dtype == torch.float64
+            rows = pack_tunables(mpc, configs_of(mpc.cfg, gains.detach().cpu().numpy()))
+            d_tun = torch.from_numpy(rows).to(records.device)
+        x = torch.empty((B, mpc.n_var), dtype=torch.float64, device=records.device)
+        fm = torch.empty((B, L.FM_SIZE), dtype=torch.float64, device=records.device)
+        status = torch.empty(B, dtype=torch.int32, device=records.device)
+        if d_tun is None:
+            mpc.solve_device(d_in, x, fm, status, None)
+        else:
+            mpc.solve_device_tuned(d_in, d_tun, x, fm, status, None)
+        ctx.mpc, ctx.d_in, ctx.d_tun, ctx.info = mpc, d_in, d_tun, info
+        ctx.mark_non_differentiable(status)
+        return x, fm, status
+
+    @staticmethod
+    def backward(ctx, gx, gfm, _gstatus):
+        mpc, d_in = ctx.mpc, ctx.d_in
+        B, dev = d_in.shape[0], d_in.device
+        xbar = torch.zeros((B, mpc.n_var), dtype=torch.float64, device=dev) if gx is None else gx.contiguous()
+        fmbar = None if gfm is None else gfm.contiguous()
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        g0 = torch.empty((B, L.N_STATES), dtype=torch.float64, device=dev)
+        gc = torch.empty((B, L.GRAD_SIZE), dtype=torch.float64, device=dev)
+        active = torch.empty((B, mpc.n_v), dtype=torch.int32, device=dev)
+        flags = torch.empty(B, dtype=torch.int32, device=dev)
+        mpc.solve_adjoint_device(d_in, ctx.d_tun, xbar, fmbar, None, None, status, None, g0, gc, active, flags)
+        if ctx.info is not None:
+            ctx.info["flags"], ctx.info["active"] = flags, active
+        return None, None, (g0 if ctx.needs_input_grad[2] else None), (gc if ctx.needs_input_grad[3] else None), None
+
+
+def plan(mpc: BatchedVSMPC, records, x0, gains=None, info: dict | None = None):
+    """(x, first_move, status) of the batch, differentiable with respect to `x0` and `gains` (PlanFunction)"""
+    return PlanFunction.apply(mpc, records, x0, gains, info)

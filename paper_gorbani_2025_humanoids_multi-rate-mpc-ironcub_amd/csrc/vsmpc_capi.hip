@@ -120,7 +120,8 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     if (cfg == nullptr || out == nullptr || max_batch <= 0) return invalid_arg();
     *out = nullptr;
     const unsigned kernel_flags = VSMPC_CREATE_RUNTIME_FALLBACK | VSMPC_CREATE_RUNTIME_ONLY;
-    if ((flags & ~(kernel_flags | VSMPC_CREATE_SENSITIVITY | VSMPC_CREATE_TUNABLES | VSMPC_CREATE_CERTIFY)) != 0u)
+    if ((flags & ~(kernel_flags | VSMPC_CREATE_SENSITIVITY | VSMPC_CREATE_TUNABLES | VSMPC_CREATE_CERTIFY |
+                   VSMPC_CREATE_ADJOINT)) != 0u)
         return invalid_arg();
     if (!config_valid(*cfg)) return invalid_arg();
     const int variant = (flags & VSMPC_CREATE_RUNTIME_ONLY)
@@ -133,6 +134,9 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     const bool sens = (flags & VSMPC_CREATE_SENSITIVITY) != 0u;
     const RtDims rts = runtime_dims(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon, true);
     if (sens && runtime_lds_bytes(rts) > RT_MAX_LDS) return unsupported();     // (not for a valid config)
+    const bool adjoint = (flags & VSMPC_CREATE_ADJOINT) != 0u;
+    const RtDims rta = runtime_dims(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon, false, true);
+    if (adjoint && runtime_tuned_lds_bytes(rta) > RT_MAX_LDS) return unsupported();   // (not for a valid config)
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return invalid_arg();
@@ -149,6 +153,8 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     h->rts = rts;
     h->tunables = (flags & VSMPC_CREATE_TUNABLES) != 0u ? 1 : 0;
     h->certify = (flags & VSMPC_CREATE_CERTIFY) != 0u ? 1 : 0;
+    h->adjoint = adjoint ? 1 : 0;
+    h->rta = rta;
     h->form = runtime ? 0 : initial_kernel_form();
     for (int i = 0; i < VSMPC_N_JOINTS; ++i) h->kin.sel[i] = 3 + i;   // the shipped robot: joints 3..10
     h->kin.constant_lambda = 0;
@@ -192,6 +198,15 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     need(h->d_cy, B * h->n_con, h->certify);
     need(h->d_ccert, B * VSMPC_CERT_SIZE, h->certify);
     need(h->d_ctun, B * VSMPC_TUNE_SIZE, h->certify);
+    const size_t CA = std::min(B, size_t(ADJ_CHUNK));
+    need(h->d_aws, B * size_t(rta.ws_doubles), adjoint && !runtime);
+    need(h->d_axbar, CA * h->n_var, adjoint);
+    need(h->d_afmbar, CA * VSMPC_FM_SIZE, adjoint);
+    need(h->d_atun, CA * VSMPC_TUNE_SIZE, adjoint);
+    need(h->d_agx0, CA * NX, adjoint);
+    need(h->d_agcfg, CA * VSMPC_GRAD_SIZE, adjoint);
+    need(h->d_aact, CA * rta.nv, adjoint);
+    need(h->d_aflags, CA, adjoint);
     for (int i = 0; i < PIPE_STREAMS && e == hipSuccess; ++i) {
         e = hipStreamCreateWithFlags(h->pipe[i].put(), hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(h->pipe_done[i].put(), hipEventDisableTiming);

@@ -215,6 +215,67 @@ int vsmpc_sensitivity_batch(vsmpc_handle* h, const double* in, int batch, double
     return VSMPC_OK;
 }
 
+// Adjoint of the solve (include/vsmpc.h): adjoint_kernel_rt, or adjoint_kernel_rt_tuned with rows of tunables, on the
+// workspace of the runtime handle or the one VSMPC_CREATE_ADJOINT allocated
+static double* adjoint_workspace(const vsmpc_handle* h) { return h->runtime ? h->d_ws.get() : h->d_aws.get(); }
+static const char* const ADJOINT_NEEDS_FLAG =
+    "vsmpc_adjoint_batch needs a handle created with VSMPC_CREATE_ADJOINT (vsmpc_create_ex)";
+
+int vsmpc_adjoint_batch_device(vsmpc_handle* h, const double* d_in, const double* d_tunables, const double* d_xbar,
+                               const double* d_fmbar, int batch, double* d_x, double* d_first_move, int* d_status,
+                               int* d_iters, double* d_grad_x0, double* d_grad_cfg, int* d_active, int* d_adj_flags,
+                               void* stream) {
+    if (h == nullptr || d_in == nullptr || d_xbar == nullptr || d_status == nullptr || batch < 0) return invalid_arg();
+    if ((reinterpret_cast<size_t>(d_tunables) & 15) != 0) return invalid_arg();   // the kernel loads 16 bytes per lane
+    if (!h->adjoint) return unsupported(ADJOINT_NEEDS_FLAG);
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    if (batch == 0) return VSMPC_OK;
+    ON_DEVICE(h->device);
+    HIP_TRY(launch_adjoint_runtime(h->rta, h->dev, d_in, d_tunables, batch, adjoint_workspace(h), d_x, d_first_move, d_status,
+                                   d_iters, d_xbar, d_fmbar, d_grad_x0, d_grad_cfg, d_active, d_adj_flags,
+                                   static_cast<hipStream_t>(stream)));
+    return VSMPC_OK;
+}
+
+int vsmpc_adjoint_batch(vsmpc_handle* h, const double* in, const double* tunables, const double* xbar, const double* fmbar,
+                        int batch, double* x, double* first_move, int* status, int* iters, double* grad_x0, double* grad_cfg,
+                        int* active, int* adj_flags, void* stream) {
+    if (h == nullptr || in == nullptr || xbar == nullptr || status == nullptr || batch < 0) return invalid_arg();
+    if (!h->adjoint) return unsupported(ADJOINT_NEEDS_FLAG);
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    if (batch == 0) return VSMPC_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ON_DEVICE(h->device);
+    const size_t NV = size_t(h->rta.nv), FM = VSMPC_FM_SIZE, T = VSMPC_TUNE_SIZE, G = VSMPC_GRAD_SIZE;
+    // chunks of ADJ_CHUNK instances in stream order: the staging of one chunk is read back before the next overwrites it
+    hipError_t err = hipSuccess;
+    auto ok = [&](hipError_t e) { if (e != hipSuccess && err == hipSuccess) err = e; return err == hipSuccess; };
+    for (int first = 0; first < batch && err == hipSuccess; first += ADJ_CHUNK) {
+        const int n = std::min(ADJ_CHUNK, batch - first);
+        const size_t o = size_t(first), N = size_t(n);
+        if (!ok(upload_rows(h->d_in, in, o, N, h->n_in, s))) break;
+        if (!ok(hipMemcpyAsync(h->d_axbar, xbar + o * h->n_var, N * h->n_var * sizeof(double), hipMemcpyHostToDevice, s))) break;
+        if (fmbar && !ok(hipMemcpyAsync(h->d_afmbar, fmbar + o * FM, N * FM * sizeof(double), hipMemcpyHostToDevice, s))) break;
+        if (tunables && !ok(hipMemcpyAsync(h->d_atun, tunables + o * T, N * T * sizeof(double), hipMemcpyHostToDevice, s))) break;
+        if (!ok(launch_adjoint_runtime(h->rta, h->dev, h->d_in + o * h->n_in, tunables ? h->d_atun.get() : nullptr, n,
+                                       adjoint_workspace(h) + o * size_t(h->rta.ws_doubles), x ? h->d_x + o * h->n_var : nullptr,
+                                       first_move ? h->d_fm + o * FM : nullptr, h->d_status + o,
+                                       iters ? h->d_iters + o : nullptr, h->d_axbar, fmbar ? h->d_afmbar.get() : nullptr,
+                                       grad_x0 ? h->d_agx0.get() : nullptr, grad_cfg ? h->d_agcfg.get() : nullptr,
+                                       active ? h->d_aact.get() : nullptr, adj_flags ? h->d_aflags.get() : nullptr, s)))
+            break;
+        ok(download_results(h, o, N, x, first_move, status, iters, s));
+        if (grad_x0) ok(hipMemcpyAsync(grad_x0 + o * NX, h->d_agx0, N * NX * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (grad_cfg) ok(hipMemcpyAsync(grad_cfg + o * G, h->d_agcfg, N * G * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (active) ok(hipMemcpyAsync(active + o * NV, h->d_aact, N * NV * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (adj_flags) ok(hipMemcpyAsync(adj_flags + o, h->d_aflags, N * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    const hipError_t e = hipStreamSynchronize(s);   // nothing returns while copies into the caller's buffers are queued
+    if (err == hipSuccess) err = e;
+    if (err != hipSuccess) return hip_fail(err, "vsmpc_adjoint_batch");
+    return VSMPC_OK;
+}
+
 // Duals and KKT certificate of given primals: certify_kernel restates the oracle's solve_exact (the duals, OSQP's sign:
 // y > 0 upper-active, y < 0 lower-active) and its kkt_certificate on the QP of assemble_dense (module cited in include/vsmpc.h)
 int vsmpc_certify_batch_device(vsmpc_handle* h, const double* d_in, const double* d_x, const double* d_tunables, int batch,

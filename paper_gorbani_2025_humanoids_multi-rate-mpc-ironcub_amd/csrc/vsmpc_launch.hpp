@@ -99,9 +99,12 @@ struct RtDims {
     int lds_doubles;      // dynamic LDS of one workgroup (doubles)
 };
 constexpr size_t RT_MAX_LDS = 160 * 1024;
-// sensitivity: the sizes of sens_kernel_rt (NP = NZ + 1 + 26: the parameter columns of d/dX0)
-RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon, bool sensitivity = false);
+// sensitivity: the sizes of sens_kernel_rt (NP = NZ + 1 + 26: the parameter columns of d/dX0); adjoint: those of
+// adjoint_kernel_rt[_tuned] (the solve kernel's, with room in LDS for a_X and the costates at horizons with few unknowns)
+RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon, bool sensitivity = false, bool adjoint = false);
 size_t runtime_lds_bytes(const RtDims& d);
+// the same with the staged row of the per-instance-tunables kinds behind it (solve_kernel_rt_tuned, adjoint_kernel_rt_tuned)
+size_t runtime_tuned_lds_bytes(const RtDims& d);
 const char* runtime_kernel_name();
 // d_ws: workspace of the launch's first instance (instance b of the launch uses d_ws + b * d.ws_doubles)
 hipError_t launch_solve_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws, double* d_x,
@@ -115,6 +118,14 @@ hipError_t launch_solve_runtime_tuned(const RtDims& d, const DevCfg& cfg, const 
 hipError_t launch_sensitivity_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws,
                                       double* d_x, double* d_fm, int* d_status, int* d_iters, double* d_dx, double* d_dfm,
                                       int* d_active, int* d_flags, hipStream_t stream);
+// adjoint_kernel_rt (d_tun == nullptr: the handle's configuration) or adjoint_kernel_rt_tuned (rows of per-instance tunables,
+// 16-byte aligned): the solve outputs plus, for the cotangents d_xbar [batch][nVar] and d_fmbar [batch][24] (or nullptr),
+// dL/dX0 [batch][26], dL/dcfg [batch][VSMPC_GRAD_SIZE], active [batch][NV] and the VSMPC_ADJ_* flags [batch] (each may be
+// nullptr); d from runtime_dims(.., false, true), d_ws as for the solve
+hipError_t launch_adjoint_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
+                                  double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters, const double* d_xbar,
+                                  const double* d_fmbar, double* d_gx0, double* d_gcfg, int* d_active, int* d_flags,
+                                  hipStream_t stream);
 // linearize_kernel_rt (vsmpc_linearize_batch, on every handle): p0_linearize alone
 hipError_t launch_linearize_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,
                                     double* Bt, double* c, hipStream_t stream);

@@ -33,7 +33,7 @@
 // (solve_kernel_rt, sens_kernel_rt), or RtTunCfg, the instance's row of tunables staged in LDS (solve_kernel_rt_tuned,
 // vsmpc_solve_batch_tuned).
 //
-// sens_kernel_rt (vsmpc_sensitivity_batch) is rt_solve<SENS = true>: the same phases and four more.  X0 enters the QP only
+// sens_kernel_rt (vsmpc_sensitivity_batch) is rt_solve<RT_SENS>: the same phases and four more.  X0 enters the QP only
 // through the initial-state rows, so the solution's Jacobian with respect to X0 is that of the final active set's affine
 // piece ("Sensitivities"; executable model: tests/sensitivity_model.py):
 //   P1  rt_condense<true>: 26 parameter columns after the affine one (NP = NZ + 27 rows): column NZ + 1 + i starts from
@@ -45,6 +45,21 @@
 //   P5  rt_sens_joints: L_jj^T du = -(L_vj^T dv + l~)
 //   P6  rt_sens_states: dX_0 = I, dX_{k+1} = dX_k + dt_k (A dX_k + Bj dU + Bt dV); rt_sens_write: the other outputs
 // The 26 right-hand sides of P4 / P5 are solved in place in the parameter rows of the workspace, which then hold dz/dX0.
+//
+// adjoint_kernel_rt / adjoint_kernel_rt_tuned (vsmpc_adjoint_batch) are rt_solve<RT_ADJOINT>: P0 .. P6 and rt_write_solution
+// exactly as in solve_kernel_rt, then, on a Solved exit, five phases that turn a cotangent xbar = dL/dx (and fmbar = dL/d
+// first_move, folded into xbar) into dL/dX0 and dL/d(weights, throttle box) with one more solve against the factor the
+// solver holds ("Adjoint"; executable model: tests/adjoint_model.py condensed_adjoint).  With K [a; b] = [xbar; 0]
+// the KKT system of the final active set:
+//   rt_adj_rhs           r = Z^T xbar by the costate form: lambda_N = xbar_XN, lambda_k = xbar_Xk + (I + dt_k A)^T lambda_{k+1},
+//                        r_U[j] = xbar_U[j] + sum_{jb(k) = j} dt_k Bj^T lambda_{k+1}, r_V likewise with Bt
+//   rt_adj_solve         w = L_jj^-1 r_U, t = r_V - L_vj w, S_FF dv_F = t_F (dv = 0 on bound and pinned throttles),
+//                        L_jj^T du = w - L_vj^T dv: a_U = du, a_V = dv
+//   rt_adj_states        a_X0 = 0, a_X{k+1} = a_Xk + dt_k (A a_Xk + Bj a_U[jb(k)] + Bt a_V[tb(k)])
+//   rt_adj_costates      b_{N-1} = Q a_XN - xbar_XN, b_{i-1} = Q a_Xi - xbar_Xi + (I + dt_i A)^T b_i,
+//                        b_init = xbar_X0 - (I + dt_0 A)^T b_0, b_t = xbar_Vt - (H a)_Vt - sum_{tb(i) = t} dt_i Bt^T b_i
+//   rt_adj_reduce_write  dL/dX0 = b_init, dL/dvmin|vmax = sum of b_t over the lower | upper active non-pinned throttles,
+//                        dL/dw = -a^T (dH/dw x + dg/dw) for every weight: 31 sums in a fixed order
 #include <atomic>
 #include <cstddef>
 
@@ -59,6 +74,8 @@ namespace {
 constexpr int RT_BLOCK = 256;
 constexpr int RT_CPT = 2;    // columns per thread: NP <= 8 * 40 + 4 * 39 + 1 = 477 (+ 26 parameter columns: 503) < 512
 constexpr int RT_NPAR = NX;  // parameter columns of sens_kernel_rt: one per entry of X0
+constexpr int RT_NWAVES = RT_BLOCK / 64;
+enum RtMode { RT_SOLVE, RT_SENS, RT_ADJOINT };   // the instantiations of rt_solve
 enum { F_STATUS = 0, F_ITERS, F_NF, F_BEST, F_PATIENCE };   // LDS flag slots
 
 VS_DEV size_t tri(int i) { return size_t(i) * size_t(i + 1) / 2; }
@@ -97,7 +114,7 @@ VS_DEV RtSmem rt_smem(const RtDims& d, double* base) {
     s.state = reinterpret_cast<int*>(p); p += (d.nv + 1) / 2 + 1;
     s.idx = reinterpret_cast<int*>(p);   p += (d.nv + 1) / 2 + 1;
     s.flags = reinterpret_cast<int*>(p); p += 4;   // F_* slots
-    s.big = p;   // max(18 NP, NV (NV + 1) / 2), and 2 x 26 x 26 with SENS
+    s.big = p;   // max(18 NP, NV (NV + 1) / 2), and 2 x 26 x 26 with SENS, 26 (2 N + 2) with the adjoint
     return s;
 }
 
@@ -697,10 +714,326 @@ VS_DEV void rt_sens_write(const RtCtx& c, const RtBox box, bool factored, bool s
     }
 }
 
-// The solve of one instance: the phases in order.  cfg is a DevCfg or an RtTunCfg; `sens` is looked at with SENS only.
-template <bool SENS, class Cfg>
+// ---- the adjoint entry (rt_solve<RT_ADJOINT>): inputs and outputs, per batch; every output may be null
+struct RtAdjIO {
+    const double* xbar = nullptr;    // [nVar] per instance: dL/dx, reference variable order
+    const double* fmbar = nullptr;   // [24] per instance or null: dL/d first_move
+    double* gx0 = nullptr;           // [26]: dL/dX0
+    double* gcfg = nullptr;          // [VSMPC_GRAD_SIZE]: dL/d(weights, throttle limits in percent), VSMPC_GRAD_* order
+    int* active = nullptr;           // [NV]
+    int* flags = nullptr;            // VSMPC_ADJ_*
+};
+
+// The cotangent of one instance with the first-move cotangent folded in (read from global memory where it is used): joint
+// increments onto U_0, v0 and throttle percent (through d throttle / d v at the solution) onto V_0, thrust and thrust rate
+// onto rows 12..19 of X_1.
+struct RtAdjIn {
+    const double* xb;    // this instance's xbar
+    const double* fm;    // this instance's fmbar or null
+    const double* zv;    // the throttles of the solution (LDS)
+    int nxs, nu;
+    VS_DEV double x(int node, int r) const {
+        double v = xb[node * NX + r];
+        if (fm != nullptr && node == 1 && r >= 12 && r < 20) v += fm[VSMPC_FM_THRUST + r - 12];
+        return v;
+    }
+    VS_DEV double u(int e) const {
+        double v = xb[nxs + e];
+        if (fm != nullptr && e < NJ) v += fm[VSMPC_FM_DQ + e];
+        return v;
+    }
+    VS_DEV double v(int e) const {
+        double v = xb[nxs + nu + e];
+        if (fm != nullptr && e < NTH) v += fm[VSMPC_FM_V0 + e] + Jet::dthrottle_dv(zv[e]) * fm[VSMPC_FM_THROTTLE + e];
+        return v;
+    }
+};
+VS_DEV RtAdjIn rt_adj_in(const RtCtx& c, const RtAdjIO& io) {
+    return RtAdjIn{io.xbar + size_t(c.inst) * c.d.nvar,
+                   io.fmbar != nullptr ? io.fmbar + size_t(c.inst) * VSMPC_FM_SIZE : nullptr, c.zv(), c.d.nxs, c.d.nu};
+}
+
+VS_DEV double rt_wave_sum(double v) {   // butterfly: every lane ends with the same sum, formed in the same order
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// ---- adjoint 1: right-hand side r = Z^T xbar in s.col[0 .. NZ), joints then throttles
+// Reads xbar / fmbar (global), the linearisation, s.dt and zv.  Leaves r in s.col (free since P5).  Uses s.red for lambda_k |
+// lambda_{k+1} and the wavefronts' non-finite flags.  Returns whether xbar or fmbar holds a non-finite entry (the same value in every thread).
+VS_DEV bool rt_adj_rhs(const RtCtx& c, const RtAdjIn& a) {
+    const RtSmem s = c.lds();
+    const RtDims& d = c.d;
+    const int tid = c.tid, N = d.n, NU = d.nu, NZ = d.nz;
+    double* r = s.col;
+    double* lam = s.red;   // lambda_k at lam + (k & 1) * NX
+    int bad = 0;
+    for (int e = tid; e < d.nvar; e += RT_BLOCK) bad |= isfinite(a.xb[e]) ? 0 : 1;
+    if (a.fm != nullptr && tid < VSMPC_FM_SIZE) bad |= isfinite(a.fm[tid]) ? 0 : 1;
+    for (int e = tid; e < NZ; e += RT_BLOCK) r[e] = e < NU ? a.u(e) : a.v(e - NU);
+    if (tid < NX) lam[(N & 1) * NX + tid] = a.x(N, tid);
+    const bool wave_bad = __any(bad) != 0;   // the flag of the wavefront, then of the workgroup through s.red behind lambda
+    if ((tid & 63) == 0) lam[2 * NX + (tid >> 6)] = wave_bad ? 1.0 : 0.0;
+    __syncthreads();
+    const bool nonfinite = fmax(fmax(lam[2 * NX], lam[2 * NX + 1]), fmax(lam[2 * NX + 2], lam[2 * NX + 3])) != 0.0;
+    for (int k = N - 1; k >= 0; --k) {
+        const double* cur = lam + ((k + 1) & 1) * NX;   // lambda_{k+1}
+        double* nxt = lam + (k & 1) * NX;
+        const double dt = s.dt[k];
+        if (tid < NX) {
+            if (k > 0) {
+                double acc = 0.0;
+                for (int q = 0; q < NX; ++q) acc = fma(s.sA[q * NX + tid], cur[q], acc);
+                nxt[tid] = a.x(k, tid) + fma(dt, acc, cur[tid]);
+            }
+        } else if (tid >= 64 && tid < 64 + NJ) {
+            const int j = tid - 64;
+            double acc = 0.0;
+            for (int q = 0; q < NX; ++q) acc = fma(s.sBj[q * NJ + j], cur[q], acc);
+            double* e = r + NJ * joint_block(d, k) + j;
+            *e = fma(dt, acc, *e);
+        } else if (tid >= 128 && tid < 128 + NTH) {
+            const int t = tid - 128;
+            double acc = 0.0;
+            for (int q = 0; q < NX; ++q) acc = fma(s.sBt[q * NTH + t], cur[q], acc);
+            double* e = r + NU + NTH * throttle_block(d, k) + t;
+            *e = fma(dt, acc, *e);
+        }
+        __syncthreads();
+    }
+    return nonfinite;
+}
+
+// ---- adjoint 2: [C_jj C_jF; C_Fj C_FF] [du; dv_F] = [r_U; r_F] with the factors of P3 and of the box QP's last iteration
+// Reads r in s.col, L (joint columns of M, all rows), the factor of S_FF in K = s.big with its free list s.idx / F_NF.
+// Leaves a_z = [du | dv] in s.col[0 .. NZ), dv = 0 on bound and pinned throttles.  Uses s.vec0, s.vec1.  K is dead afterwards.
+VS_DEV void rt_adj_solve(const RtCtx& c) {
+    const RtSmem s = c.lds();
+    const int tid = c.tid, NU = c.d.nu, NV = c.d.nv, NZ = c.d.nz;
+    const double* M = c.M;
+    double* r = s.col;
+    // forward through the joint columns, over the throttle rows too: r_V becomes t = r_V - L_vj w.  Entry j keeps w_j L_jj
+    // (the division is repeated where w_j is read), so that no thread writes what another one reads in the same step.
+    for (int j = 0; j < NU; ++j) {
+        const double wj = r[j] / M[tri(j) + j];
+        for (int i = j + 1 + tid; i < NZ; i += RT_BLOCK) r[i] = fma(-M[tri(i) + j], wj, r[i]);
+        __syncthreads();
+    }
+    // S_FF dv_F = t_F
+    const int nf = s.flags[F_NF];
+    const double* K = s.big;
+    double* rhs = s.vec0;
+    double* y = s.vec1;
+    for (int a = tid; a < nf; a += RT_BLOCK) rhs[a] = r[NU + s.idx[a]];
+    __syncthreads();
+    for (int p = tid; p < NV; p += RT_BLOCK) r[NU + p] = 0.0;
+    for (int j = 0; j < nf; ++j) {
+        const double yj = rhs[j] / K[tri(j) + j];
+        for (int i = j + 1 + tid; i < nf; i += RT_BLOCK) rhs[i] = fma(-K[tri(i) + j], yj, rhs[i]);
+        if (tid == 0) y[j] = yj;
+        __syncthreads();
+    }
+    for (int j = nf - 1; j >= 0; --j) {
+        const double vj = y[j] / K[tri(j) + j];
+        for (int i = tid; i < j; i += RT_BLOCK) y[i] = fma(-K[tri(j) + i], vj, y[i]);
+        __syncthreads();
+        if (tid == 0) r[NU + s.idx[j]] = vj;
+    }
+    __syncthreads();
+    // L_jj^T du = w - L_vj^T dv
+    for (int j = tid; j < NU; j += RT_BLOCK) {
+        double acc = r[j] / M[tri(j) + j];
+        for (int p = 0; p < NV; ++p) acc = fma(-M[tri(NU + p) + j], r[NU + p], acc);
+        r[j] = acc;
+    }
+    __syncthreads();
+    for (int j = NU - 1; j >= 0; --j) {
+        const double uj = r[j] / M[tri(j) + j];
+        for (int i = tid; i < j; i += RT_BLOCK) r[i] = fma(-M[tri(j) + i], uj, r[i]);
+        __syncthreads();
+        if (tid == 0) r[j] = uj;
+    }
+    __syncthreads();
+}
+
+// the adjoint's carve-up of s.big (the factor of S_FF is dead): a_X [N + 1][26] | b_0 .. b_{N-1}, b_init [N + 1][26]
+VS_DEV double* rt_adj_ax(const RtCtx& c) { return c.lds().big; }
+VS_DEV double* rt_adj_b(const RtCtx& c) { return c.lds().big + NX * (c.d.n + 1); }
+
+// ---- adjoint 3: state part of a: a_X0 = 0, a_X{k+1} = a_Xk + dt_k (A a_Xk + Bj a_U[jb(k)] + Bt a_V[tb(k)])
+// Reads a_z in s.col, the linearisation, s.dt.  Leaves a_X in s.big.
+VS_DEV void rt_adj_states(const RtCtx& c) {
+    const RtSmem s = c.lds();
+    const RtDims& d = c.d;
+    const int tid = c.tid;
+    double* aX = rt_adj_ax(c);
+    if (tid < NX) aX[tid] = 0.0;
+    __syncthreads();
+    for (int k = 0; k < d.n; ++k) {
+        if (tid < NX) {
+            const int r = tid;
+            const double* U = s.col + NJ * joint_block(d, k);
+            const double* V = s.col + d.nu + NTH * throttle_block(d, k);
+            double a = 0.0;
+            for (int q = 0; q < NJ; ++q) a = fma(s.sBj[r * NJ + q], U[q], a);
+            for (int q = 0; q < NTH; ++q) a = fma(s.sBt[r * NTH + q], V[q], a);
+            for (int q = 0; q < NX; ++q) a = fma(s.sA[r * NX + q], aX[k * NX + q], a);
+            aX[(k + 1) * NX + r] = fma(s.dt[k], a, aX[k * NX + r]);
+        }
+        __syncthreads();
+    }
+}
+
+// diagonal of Q on state row r from the square-root weights (0 on thrust and thrust rate)
+template <class Cfg>
+VS_DEV double rt_q_diag(const Cfg& cfg, int r) {
+    const double q = cfg.sq[r < 12 ? r : (r >= 20 ? r - 8 : 0)];
+    return (r >= 12 && r < 20) ? 0.0 : q * q;
+}
+
+// ---- adjoint 4: costates b (the multipliers of K [a; b] = [xbar; 0]): certify_kernel's recursion with Q a_Xi - xbar_Xi
+// Reads a_X, a_z, xbar, the linearisation, s.dt, cfg.sq, cfg.w_thr, cfg.w_init.  Leaves b_i and b_init in s.big behind a_X
+// and the throttle rows' b_t (every throttle; only the active ones mean anything) in s.vec0.
+template <class Cfg>
+VS_DEV void rt_adj_costates(const RtCtx& c, const Cfg& cfg, const RtAdjIn& a) {
+    const RtSmem s = c.lds();
+    const RtDims& d = c.d;
+    const int tid = c.tid, N = d.n, NV = d.nv;
+    const double* aX = rt_adj_ax(c);
+    double* b = rt_adj_b(c);
+    const double qd = tid < NX ? rt_q_diag(cfg, tid) : 0.0;
+    if (tid < NX) b[(N - 1) * NX + tid] = qd * aX[N * NX + tid] - a.x(N, tid);
+    __syncthreads();
+    for (int i = N - 1; i >= 0; --i) {
+        if (tid < NX) {
+            const double* bi = b + i * NX;
+            double acc = 0.0;
+            for (int q = 0; q < NX; ++q) acc = fma(s.sA[q * NX + tid], bi[q], acc);
+            const double prop = fma(s.dt[i], acc, bi[tid]);                       // ((I + dt_i A)^T b_i)
+            if (i > 0) b[(i - 1) * NX + tid] = (qd * aX[i * NX + tid] - a.x(i, tid)) + prop;
+            else b[N * NX + tid] = a.x(0, tid) - prop;                            // b_init
+        }
+        __syncthreads();
+    }
+    const double* aV = s.col + d.nu;
+    const double w_thr = cfg.w_thr, w_init = cfg.w_init;
+    for (int f = tid; f < NV; f += RT_BLOCK) {
+        const int t = f >> 2, k = f & 3;
+        double sum = 0.0;
+        for (int i = 0; i < N; ++i) {
+            if (throttle_block(d, i) != t) continue;
+            const double* bi = b + i * NX;
+            double acc = 0.0;
+            for (int q = 0; q < NX; ++q) acc = fma(s.sBt[q * NTH + k], bi[q], acc);
+            sum = fma(s.dt[i], acc, sum);
+        }
+        const double v = aV[f];
+        const double vm = aV[t > 0 ? f - NTH : f], vp = aV[t < d.nvb - 1 ? f + NTH : f];   // neighbours (or v: difference 0)
+        const double hx = fma(w_thr, (v - vm) + (v - vp), t == 0 ? w_init * v : 0.0);
+        s.vec0[f] = (a.v(f) - hx) - sum;
+    }
+    __syncthreads();
+}
+
+// ---- adjoint 5: the 31 contractions and the outputs
+// Reads a_X, b (s.big), a_z (s.col), b_t (s.vec0), the solution (s.x, s.z), s.in (reference window, q_err), s.vprev,
+// s.state, the reduced gradients (row NZ of M, s.vec2) for the degeneracy flag.  Every sum: per-lane partial over the items
+// e = tid, tid + 256, .., a butterfly inside the wavefront, the four partials in wavefront order through s.red -- an order
+// the sizes alone fix.  Writes dL/dX0, dL/dcfg (all zero unless adj_ok, all NaN with a non-finite cotangent; entry 31 is 0),
+// the active set and the VSMPC_ADJ_* flags, whose degeneracy rule is rt_sens_write's.
+template <class Cfg>
+VS_DEV void rt_adj_reduce_write(const RtCtx& c, const Cfg& cfg, const RtBox box, bool factored, bool adj_ok, bool nonfinite,
+                                const RtAdjIO& out) {
+    const RtDims& d = c.d;
+    const RtSmem s = c.lds();
+    const int tid = c.tid, inst = c.inst, N = d.n, NU = d.nu, NV = d.nv;
+    const bool hold = box.hold;
+    const double vmin = box.vmin, vmax = box.vmax;
+    if (adj_ok) {
+        const double* aX = rt_adj_ax(c);
+        const double* aU = s.col;
+        const double* aV = s.col + NU;
+        const double* U = s.z;
+        const double* V = s.z + NU;
+        for (int g = 0; g < VSMPC_GRAD_THROTTLE_MAX + 1; ++g) {
+            double acc = 0.0;
+            if (g < VSMPC_GRAD_W_DELTA_JOINT) {
+                // state weights in the order of the vsmpc_config fields: w_com_pos, w_com_pos_err, w_lin_mom, w_rpy,
+                // w_rpy_err, w_ang_mom -> state rows 0, 20, 3, 6, 23, 9
+                const int f = g / 3, r = (f == 0 ? 0 : f == 1 ? 20 : f == 2 ? 3 : f == 3 ? 6 : f == 4 ? 23 : 9) + g % 3;
+                for (int e = tid; e < N; e += RT_BLOCK) {
+                    const int i = e + 1;
+                    const int col = (i - 1) < d.ns ? 0 : (i - 1) - d.ns;
+                    const double ref = r < 12 ? s.in[VSMPC_IN_XREF + col * 12 + r] : 0.0;
+                    acc = fma(-aX[i * NX + r], s.x[i * NX + r] - ref, acc);
+                }
+            } else if (g < VSMPC_GRAD_W_THROTTLE) {
+                const int j = g - VSMPC_GRAD_W_DELTA_JOINT;
+                for (int e = tid; e < d.hc; e += RT_BLOCK) acc = fma(-aU[e * NJ + j], U[e * NJ + j], acc);
+            } else if (g == VSMPC_GRAD_W_THROTTLE) {
+                for (int e = tid; e < NV - NTH; e += RT_BLOCK) acc = fma(-(aV[e] - aV[e + NTH]), V[e] - V[e + NTH], acc);
+            } else if (g == VSMPC_GRAD_W_INITIAL_THROTTLE) {
+                for (int e = tid; e < NTH; e += RT_BLOCK) acc = fma(-aV[e], V[e] - s.vprev[e], acc);
+            } else if (g == VSMPC_GRAD_W_REG_JOINT_POS) {
+                for (int e = tid; e < NU; e += RT_BLOCK) acc = fma(-aU[e], U[e] + s.in[VSMPC_IN_QERR + (e & 7)], acc);
+            } else {
+                const int want = g == VSMPC_GRAD_THROTTLE_MIN ? -1 : 1;
+                for (int e = tid; e < NV; e += RT_BLOCK)
+                    if (s.state[e] == want && !(hold && e < NTH)) acc += s.vec0[e];
+            }
+            acc = rt_wave_sum(acc);
+            if ((tid & 63) == 0) s.red[g * RT_NWAVES + (tid >> 6)] = acc;
+        }
+    }
+    __syncthreads();
+    if (out.gcfg != nullptr && tid < VSMPC_GRAD_SIZE) {
+        double v = 0.0;
+        if (adj_ok && tid <= VSMPC_GRAD_THROTTLE_MAX) {
+            const double* p = s.red + tid * RT_NWAVES;
+            v = ((p[0] + p[1]) + p[2]) + p[3];
+            // percent, not warped throttle: d v_of_throttle / du at the limit = sqrt(1 + 4 c12 v) / sigma_U
+            if (tid == VSMPC_GRAD_THROTTLE_MIN) v *= sqrt(1.0 + 4.0 * Jet::c12 * vmin) * Jet::isgU;
+            if (tid == VSMPC_GRAD_THROTTLE_MAX) v *= sqrt(1.0 + 4.0 * Jet::c12 * vmax) * Jet::isgU;
+            if (nonfinite) v = __builtin_nan("");
+        }
+        out.gcfg[size_t(inst) * VSMPC_GRAD_SIZE + tid] = v;
+    }
+    if (out.gx0 != nullptr && tid >= 64 && tid < 64 + NX) {
+        const int q = tid - 64;
+        double v = adj_ok ? rt_adj_b(c)[N * NX + q] : 0.0;
+        if (adj_ok && nonfinite) v = __builtin_nan("");
+        out.gx0[size_t(inst) * NX + q] = v;
+    }
+    if (out.active != nullptr)
+        for (int p = tid; p < NV; p += RT_BLOCK)
+            out.active[size_t(inst) * NV + p] = !factored ? 0 : ((hold && p < NTH) ? 2 : s.state[p]);
+    if (tid == 0 && out.flags != nullptr) {
+        int fl = VSMPC_ADJ_UNSOLVED;
+        if (adj_ok) {   // weakly or nearly active non-pinned throttles: the gradient is one-sided there
+            fl = 0;
+            const double* sS = c.sS();
+            const double* zv = c.zv();
+            double smax = 0.0;
+            for (int p = 0; p < NV; ++p) smax = fmax(smax, fabs(sS[p]));
+            const double gt = VSMPC_SENS_GRAD_TOL * (1.0 + smax);
+            for (int p = 0; p < NV; ++p) {
+                if (hold && p < NTH) continue;
+                const int st = s.state[p];
+                const double v = zv[p], bt = VSMPC_SENS_BOUND_TOL * (1.0 + fabs(v));
+                if ((st != 0 && fabs(s.vec2[p]) <= gt) || (st == 0 && (v - vmin <= bt || vmax - v <= bt)))
+                    fl |= VSMPC_ADJ_DEGENERATE;
+            }
+        }
+        out.flags[inst] = fl;
+    }
+}
+
+// The solve of one instance: the phases in order.  cfg is a DevCfg or an RtTunCfg; `sens` is looked at with RT_SENS only,
+// `adj` with RT_ADJOINT only.
+template <RtMode MODE, class Cfg>
 VS_DEV void rt_solve(const Cfg& cfg, const RtDims& d, const double* in, double* ws, double* xout, double* fmout,
-                     int* status_out, int* iters_out, const RtSensOut& sens = {}) {
+                     int* status_out, int* iters_out, const RtSensOut& sens = {}, const RtAdjIO& adj = {}) {
+    constexpr bool SENS = MODE == RT_SENS;
     const int inst = blockIdx.x;
     const RtCtx c{d, ws + size_t(inst) * size_t(d.ws_doubles), int(threadIdx.x), inst};
     const RtSmem s = c.lds();
@@ -726,6 +1059,18 @@ VS_DEV void rt_solve(const Cfg& cfg, const RtDims& d, const double* in, double* 
     }
     rt_write_solution(c, bad, xout, fmout, status_out, iters_out);
     if constexpr (SENS) rt_sens_write(c, box, factored, sens_ok, sens);
+    if constexpr (MODE == RT_ADJOINT) {
+        const bool adj_ok = !bad && s.flags[F_STATUS] == VSMPC_STATUS_SOLVED;   // (the same value in every thread)
+        bool nonfinite = false;
+        if (adj_ok) {
+            const RtAdjIn a = rt_adj_in(c, adj);
+            nonfinite = rt_adj_rhs(c, a);
+            rt_adj_solve(c);
+            rt_adj_states(c);
+            rt_adj_costates(c, cfg, a);
+        }
+        rt_adj_reduce_write(c, cfg, box, factored, adj_ok, nonfinite, adj);
+    }
 }
 
 }  // namespace
@@ -734,7 +1079,7 @@ __global__ __launch_bounds__(RT_BLOCK) void solve_kernel_rt(DevCfg cfg, RtDims d
                                                             double* __restrict__ ws, double* __restrict__ xout,
                                                             double* __restrict__ fmout, int* __restrict__ status_out,
                                                             int* __restrict__ iters_out) {
-    rt_solve<false>(cfg, d, in, ws, xout, fmout, status_out, iters_out);
+    rt_solve<RT_SOLVE>(cfg, d, in, ws, xout, fmout, status_out, iters_out);
 }
 
 // solve_kernel_rt + the 26 parameter columns and the outputs dx_dx0 [nVar][26], dfm_dx0 [24][26], active [NV] and the
@@ -745,7 +1090,7 @@ __global__ __launch_bounds__(RT_BLOCK) void sens_kernel_rt(DevCfg cfg, RtDims d,
                                                            int* __restrict__ iters_out, double* __restrict__ dxout,
                                                            double* __restrict__ dfmout, int* __restrict__ active_out,
                                                            int* __restrict__ flags_out) {
-    rt_solve<true>(cfg, d, in, ws, xout, fmout, status_out, iters_out, RtSensOut{dxout, dfmout, active_out, flags_out});
+    rt_solve<RT_SENS>(cfg, d, in, ws, xout, fmout, status_out, iters_out, RtSensOut{dxout, dfmout, active_out, flags_out});
 }
 
 // solve_kernel_rt with per-instance tunables (vsmpc_solve_batch_tuned on a runtime handle): the instance's row of `tun`
@@ -759,32 +1104,61 @@ struct RtTunCfg {   // LDS image: the row (CFG_* order), then what the phases re
 static_assert(offsetof(RtTunCfg, wj) == CFG_WJ * sizeof(double) && offsetof(RtTunCfg, vmax) == CFG_VMAX * sizeof(double) &&
               offsetof(RtTunCfg, dt) == CFG_SIZE * sizeof(double) && CFG_SIZE == VSMPC_TUNE_SIZE && sizeof(RtTunCfg) % 8 == 0,
               "a row of tunables is the head of RtTunCfg");
+// Stages the instance's row of `tun` and what the phases read of the handle's DevCfg behind rt_solve's carve-up (the launcher
+// adds sizeof(RtTunCfg)); ends with a barrier.
+VS_DEV RtTunCfg& rt_stage_tunables(const DevCfg& hcfg, const RtDims& d, const double* __restrict__ tun) {
+    extern __shared__ __attribute__((aligned(16))) double smem_tuned[];
+    double* const sTun = smem_tuned + d.lds_doubles;
+    RtTunCfg& tcfg = *reinterpret_cast<RtTunCfg*>(sTun);
+    const int t = threadIdx.x;
+    double2 v = make_double2(0.0, 0.0);
+    if (t < CFG_SIZE / 2) {
+        v = reinterpret_cast<const double2*>(tun + size_t(blockIdx.x) * CFG_SIZE)[t];
+        sTun[2 * t] = v.x;
+        sTun[2 * t + 1] = v.y;
+    }
+    if (t >= 64 && t < 64 + MAX_STAGES) tcfg.dt[t - 64] = hcfg.dt[t - 64];
+    if (t == 128) { tcfg.use_jet = hcfg.use_jet; tcfg.max_as_iter = hcfg.max_as_iter; }
+    // a non-finite tunable ends like a non-finite record: the first square-root weight is made NaN, so that the first pivot
+    // fails and the status is Numerical (the pad entry of the row is not looked at)
+    const bool fin = isfinite(v.x) && (isfinite(v.y) || t == CFG_SIZE / 2 - 1);
+    __syncthreads();
+    if (!fin) tcfg.sq[0] = __builtin_nan("");
+    __syncthreads();
+    return tcfg;
+}
 __global__ __launch_bounds__(RT_BLOCK) void solve_kernel_rt_tuned(DevCfg hcfg, RtDims d, const double* __restrict__ in,
                                                                   double* __restrict__ ws, double* __restrict__ xout,
                                                                   double* __restrict__ fmout, int* __restrict__ status_out,
                                                                   int* __restrict__ iters_out,
                                                                   const double* __restrict__ tun) {
-    extern __shared__ __attribute__((aligned(16))) double smem_tuned[];
-    double* const sTun = smem_tuned + d.lds_doubles;   // behind rt_solve's carve-up (the launcher adds sizeof(RtTunCfg))
-    RtTunCfg& tcfg = *reinterpret_cast<RtTunCfg*>(sTun);
-    {
-        const int t = threadIdx.x;
-        double2 v = make_double2(0.0, 0.0);
-        if (t < CFG_SIZE / 2) {
-            v = reinterpret_cast<const double2*>(tun + size_t(blockIdx.x) * CFG_SIZE)[t];
-            sTun[2 * t] = v.x;
-            sTun[2 * t + 1] = v.y;
-        }
-        if (t >= 64 && t < 64 + MAX_STAGES) tcfg.dt[t - 64] = hcfg.dt[t - 64];
-        if (t == 128) { tcfg.use_jet = hcfg.use_jet; tcfg.max_as_iter = hcfg.max_as_iter; }
-        // a non-finite tunable ends like a non-finite record: the first square-root weight is made NaN, so that the first pivot
-        // fails and the status is Numerical (the pad entry of the row is not looked at)
-        const bool fin = isfinite(v.x) && (isfinite(v.y) || t == CFG_SIZE / 2 - 1);
-        __syncthreads();
-        if (!fin) tcfg.sq[0] = __builtin_nan("");
-        __syncthreads();
-    }
-    rt_solve<false>(tcfg, d, in, ws, xout, fmout, status_out, iters_out);
+    const RtTunCfg& tcfg = rt_stage_tunables(hcfg, d, tun);
+    rt_solve<RT_SOLVE>(tcfg, d, in, ws, xout, fmout, status_out, iters_out);
+}
+
+// solve_kernel_rt + the adjoint phases: xbar [batch][nVar] and fmbar [batch][24] (or null) in, dL/dX0 [batch][26],
+// dL/dcfg [batch][VSMPC_GRAD_SIZE], active [batch][NV] and the VSMPC_ADJ_* flags out (each may be null)
+__global__ __launch_bounds__(RT_BLOCK) void adjoint_kernel_rt(DevCfg cfg, RtDims d, const double* __restrict__ in,
+                                                              double* __restrict__ ws, double* __restrict__ xout,
+                                                              double* __restrict__ fmout, int* __restrict__ status_out,
+                                                              int* __restrict__ iters_out, const double* __restrict__ xbar,
+                                                              const double* __restrict__ fmbar, double* __restrict__ gx0,
+                                                              double* __restrict__ gcfg, int* __restrict__ active_out,
+                                                              int* __restrict__ flags_out) {
+    rt_solve<RT_ADJOINT>(cfg, d, in, ws, xout, fmout, status_out, iters_out, RtSensOut{},
+                         RtAdjIO{xbar, fmbar, gx0, gcfg, active_out, flags_out});
+}
+// the same with per-instance tunables, staged as in solve_kernel_rt_tuned
+__global__ __launch_bounds__(RT_BLOCK) void adjoint_kernel_rt_tuned(DevCfg hcfg, RtDims d, const double* __restrict__ in,
+                                                                    double* __restrict__ ws, double* __restrict__ xout,
+                                                                    double* __restrict__ fmout, int* __restrict__ status_out,
+                                                                    int* __restrict__ iters_out, const double* __restrict__ xbar,
+                                                                    const double* __restrict__ fmbar, double* __restrict__ gx0,
+                                                                    double* __restrict__ gcfg, int* __restrict__ active_out,
+                                                                    int* __restrict__ flags_out, const double* __restrict__ tun) {
+    const RtTunCfg& tcfg = rt_stage_tunables(hcfg, d, tun);
+    rt_solve<RT_ADJOINT>(tcfg, d, in, ws, xout, fmout, status_out, iters_out, RtSensOut{},
+                         RtAdjIO{xbar, fmbar, gx0, gcfg, active_out, flags_out});
 }
 
 __global__ __launch_bounds__(256) void linearize_kernel_rt(DevCfg cfg, int n_in, const double* __restrict__ in,
@@ -807,7 +1181,7 @@ __global__ __launch_bounds__(256) void linearize_kernel_rt(DevCfg cfg, int n_in,
     for (int i = tid; i < NX; i += 256) c[size_t(b) * NX + i] = sC[i];
 }
 
-RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon, bool sensitivity) {
+RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon, bool sensitivity, bool adjoint) {
     RtDims d{};
     d.n = n_iter;
     d.ns = n_iter_small;
@@ -825,12 +1199,16 @@ RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon, bool sens
     const int fixed = ((d.nin + 1) & ~1) + LIN_DOUBLES + 4 + MAX_STAGES + NWROWS + 2 + NX * (d.n + 1) + ((d.nz + 1) & ~1) +
                       ((d.np + 1) & ~1) + RT_BLOCK + 3 * ((d.nv + 1) & ~1) + 2 * ((d.nv + 1) / 2 + 1) + 4;
     const int ybuf = NWROWS * d.np, kbuf = d.nv * (d.nv + 1) / 2, dxbuf = sensitivity ? 2 * NX * RT_NPAR : 0;
+    const int adjbuf = adjoint ? 2 * NX * (d.n + 1) : 0;   // a_X | b after the box QP's factor is dead (rt_adj_ax, rt_adj_b)
     const int big = ybuf > kbuf ? ybuf : kbuf;
-    d.lds_doubles = fixed + (big > dxbuf ? big : dxbuf);
+    const int big2 = big > dxbuf ? big : dxbuf;
+    d.lds_doubles = fixed + (big2 > adjbuf ? big2 : adjbuf);
     return d;
 }
 
 size_t runtime_lds_bytes(const RtDims& d) { return size_t(d.lds_doubles) * sizeof(double); }
+
+size_t runtime_tuned_lds_bytes(const RtDims& d) { return runtime_lds_bytes(d) + sizeof(RtTunCfg); }
 
 // every horizon launches under the largest dynamic LDS, allowed once per kernel and device
 static hipError_t rt_allow_lds(const void* kernel, std::atomic<bool> (&attr_set)[MAX_DEVICES], const RtDims& d) {
@@ -852,7 +1230,7 @@ hipError_t launch_solve_runtime_tuned(const RtDims& d, const DevCfg& cfg, const 
                                       double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters,
                                       hipStream_t stream) {
     static std::atomic<bool> attr_set[MAX_DEVICES];
-    const size_t lds = runtime_lds_bytes(d) + sizeof(RtTunCfg);            // the staged row lies behind the body's carve-up
+    const size_t lds = runtime_tuned_lds_bytes(d);                          // the staged row lies behind the body's carve-up
     if (lds > RT_MAX_LDS) return hipErrorInvalidValue;                      // (the largest valid horizon needs 129 KB)
     const hipError_t e = rt_allow_lds(reinterpret_cast<const void*>(&solve_kernel_rt_tuned), attr_set, d);
     if (e != hipSuccess) return e;
@@ -870,6 +1248,29 @@ hipError_t launch_sensitivity_runtime(const RtDims& d, const DevCfg& cfg, const 
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(sens_kernel_rt, dim3(batch), dim3(RT_BLOCK), runtime_lds_bytes(d), stream, cfg, d, d_in, d_ws, d_x,
                        d_fm, d_status, d_iters, d_dx, d_dfm, d_active, d_flags);
+    return hipGetLastError();
+}
+
+hipError_t launch_adjoint_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
+                                  double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters, const double* d_xbar,
+                                  const double* d_fmbar, double* d_gx0, double* d_gcfg, int* d_active, int* d_flags,
+                                  hipStream_t stream) {
+    static std::atomic<bool> attr_set[MAX_DEVICES], attr_set_tuned[MAX_DEVICES];
+    static_assert(VSMPC_GRAD_SIZE * RT_NWAVES <= RT_BLOCK && 2 * NX + RT_NWAVES <= RT_BLOCK, "s.red holds the partial sums and lambda");
+    if (d.np != d.nz + 1) return hipErrorInvalidValue;                                    // runtime_dims(.., false, true)
+    const size_t lds = d_tun != nullptr ? runtime_tuned_lds_bytes(d) : runtime_lds_bytes(d);
+    if (lds > RT_MAX_LDS) return hipErrorInvalidValue;
+    if (d_tun != nullptr) {
+        const hipError_t e = rt_allow_lds(reinterpret_cast<const void*>(&adjoint_kernel_rt_tuned), attr_set_tuned, d);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(adjoint_kernel_rt_tuned, dim3(batch), dim3(RT_BLOCK), lds, stream, cfg, d, d_in, d_ws, d_x, d_fm,
+                           d_status, d_iters, d_xbar, d_fmbar, d_gx0, d_gcfg, d_active, d_flags, d_tun);
+        return hipGetLastError();
+    }
+    const hipError_t e = rt_allow_lds(reinterpret_cast<const void*>(&adjoint_kernel_rt), attr_set, d);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(adjoint_kernel_rt, dim3(batch), dim3(RT_BLOCK), lds, stream, cfg, d, d_in, d_ws, d_x, d_fm, d_status,
+                       d_iters, d_xbar, d_fmbar, d_gx0, d_gcfg, d_active, d_flags);
     return hipGetLastError();
 }
 

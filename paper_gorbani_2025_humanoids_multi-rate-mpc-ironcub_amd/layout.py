@@ -83,6 +83,21 @@ CERT_STATIONARITY, CERT_STAT_SCALE, CERT_PRIMAL, CERT_COMPLEMENTARITY, CERT_OBJE
 CERT_SIZE = 8
 CERTIFY_KERNEL_NAME = "certify_kernel"
 
+# adjoint of the solve (vsmpc_adjoint_batch, VSMPC_GRAD_* / VSMPC_ADJ_* in include/vsmpc.h): a row of dL/dcfg follows the
+# order of the vsmpc_config fields
+CREATE_ADJOINT = 0x40
+GRAD_W_COM_POS, GRAD_W_COM_POS_ERR, GRAD_W_LIN_MOM, GRAD_W_RPY, GRAD_W_RPY_ERR, GRAD_W_ANG_MOM = 0, 3, 6, 9, 12, 15
+GRAD_W_DELTA_JOINT, GRAD_W_THROTTLE, GRAD_W_INITIAL_THROTTLE, GRAD_W_REG_JOINT_POS = 18, 26, 27, 28
+GRAD_THROTTLE_MIN, GRAD_THROTTLE_MAX = 29, 30
+GRAD_SIZE = 32
+# (config field, offset, length) of every entry of a gradient row
+GRAD_FIELDS = (("w_com_pos", 0, 3), ("w_com_pos_err", 3, 3), ("w_lin_mom", 6, 3), ("w_rpy", 9, 3), ("w_rpy_err", 12, 3),
+               ("w_ang_mom", 15, 3), ("w_delta_joint", 18, 8), ("w_throttle", 26, 1), ("w_initial_throttle", 27, 1),
+               ("w_reg_joint_pos", 28, 1), ("throttle_min", 29, 1), ("throttle_max", 30, 1))
+ADJ_DEGENERATE = 0x1
+ADJ_UNSOLVED = 0x2
+ADJOINT_KERNEL_NAMES = ("adjoint_kernel_rt", "adjoint_kernel_rt_tuned")
+
 # closed-loop rollout: plant state / parameter layouts (VSMPC_PS_* / VSMPC_PP_* in include/vsmpc.h)
 PS_P, PS_HLIN, PS_RPY, PS_HANG, PS_T, PS_TD, PS_Q, PS_U, PS_TDES, PS_TDDES = 0, 3, 6, 9, 12, 16, 20, 28, 32, 36
 PS_TNN, PS_EST, PS_EKFP = 40, 44, 52     # jet plant option (LSTM thrust, EKF estimates (T, Tdot) x 4, covariances 2x2 x 4)
