@@ -36,25 +36,10 @@ namespace vsmpc {
 namespace {
 
 constexpr int CB = 256;
-// diagonal of Q on state row r (costsVSMPC.cpp:78-93): the squared square-root weight of the weighted rows, 0 on T, Tdot
-VS_DEV double q_diag(const double* __restrict__ sCfg, int r) {
-    const double s = sCfg[CFG_SQ + (r < 12 ? r : (r >= 20 ? r - 8 : 0))];   // loaded unconditionally, selected afterwards
-    return (r >= 12 && r < 20) ? 0.0 : s * s;
-}
-
 // running maximum that remembers a non-finite candidate (fmax drops a NaN)
 VS_DEV void take_max(double& m, double v, double& bad) {
     m = fmax(m, v);
     bad = isfinite(v) ? bad : 1.0;
-}
-
-VS_DEV double wave_max(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-VS_DEV double wave_sum(double v) {   // butterfly: every lane ends with the same sum, formed in the same order
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 struct CertSmem {
@@ -148,7 +133,7 @@ __global__ __launch_bounds__(CB) void certify_kernel(DevCfg cfg, RtDims d, const
         double acol[NX];   // column q of A: row q of A^T
 #pragma unroll
         for (int r = 0; r < NX; ++r) acol[r] = sA[r * NX + q];
-        const double qd = q_diag(s.cfg, q);
+        const double qd = q_diag(s.cfg + CFG_SQ, q);
         const int qx = q < 12 ? q : 11;           // reference rows 0..11 only: loaded unconditionally, selected afterwards
         double yv;
         {
@@ -210,7 +195,7 @@ __global__ __launch_bounds__(CB) void certify_kernel(DevCfg cfg, RtDims d, const
             take_max(m_prim, fabs(fma(s.dt[i], acc, xi[r]) - xn), bad);
             const int col = i < d.ns ? 0 : i - d.ns;                              // node i + 1 reads column (i + 1) - 1 - nS
             const double xrl = s.in[VSMPC_IN_XREF + col * 12 + (r < 12 ? r : 11)];
-            const double qd = q_diag(s.cfg, r), gq = qd * (r < 12 ? xrl : 0.0);   // g = -Q xr
+            const double qd = q_diag(s.cfg + CFG_SQ, r), gq = qd * (r < 12 ? xrl : 0.0);   // g = -Q xr
             const double hx = qd * xn;
             take_max(m_scale, fmax(fabs(hx), fabs(gq)), bad);
             obj += xn * fma(0.5, hx, -gq);

@@ -1,5 +1,6 @@
 // What the runtime-sized kernels (vsmpc_runtime.hip, vsmpc_certify.hip) both state about the problem's structure: the
-// move-blocking maps by RtDims, the size of p0_linearize's block, and which entries of A the linearisation can fill.
+// move-blocking maps by RtDims, the size of p0_linearize's block, which entries of A the linearisation can fill, the
+// diagonal of Q and the wavefront reductions.
 #pragma once
 #include "vsmpc_launch.hpp"
 
@@ -45,5 +46,22 @@ constexpr bool a_sparsity_statements_agree() {
     return true;
 }
 static_assert(a_sparsity_statements_agree(), "a_nz and a_row_ranges describe the same 26 x 26 pattern");
+
+// diagonal of Q on state row r (costsVSMPC.cpp:78-93) from the 18 square-root weights `sq` (a row of tunables' CFG_SQ part,
+// or the sq of a DevCfg): the squared weight of the weighted rows, 0 on T, Tdot
+VS_DEV double q_diag(const double* __restrict__ sq, int r) {
+    const double s = sq[r < 12 ? r : (r >= 20 ? r - 8 : 0)];   // loaded unconditionally, selected afterwards
+    return (r >= 12 && r < 20) ? 0.0 : s * s;
+}
+
+// wavefront reductions by butterfly: every lane ends with the same value, formed in the same order
+VS_DEV double wave_max(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+VS_DEV double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 
 }  // namespace vsmpc

@@ -6,7 +6,7 @@ tunable configuration fields -- two ways, for tests/test_adjoint_model.py and te
                      rows (dynamics, initial state) and the active throttle rows.  Then dL/dX0 = b on the initial-state rows,
                      dL/d(throttle limit) = the sum of b over the non-pinned throttles on that limit, and
                      dL/dw = -a^T (dH/dw x + dg/dw) for every weight w
-  condensed_adjoint  numpy mirror of adjoint_kernel_rt (csrc/vsmpc_runtime.hip: rt_adj_rhs, rt_adj_solve, rt_adj_states,
+  condensed_adjoint  numpy mirror of adjoint_kernel_rt (csrc/vsmpc_rt_adjoint.hpp: rt_adj_rhs, rt_adj_solve, rt_adj_states,
                      rt_adj_costates, rt_adj_reduce_write) on runtime_model.condense / _chol_partial / box_qp: the
                      right-hand side Z^T xbar by a costate recursion, one right-hand side through the joint factor and the
                      factor of S_FF, a forward recursion for the state part of a, certify's costate recursion for b

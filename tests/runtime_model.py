@@ -1,4 +1,4 @@
-"""Executable numpy model of the runtime-sized solve kernel (csrc/vsmpc_runtime.hip), step for step:
+"""Executable numpy model of the runtime-sized solve kernel (csrc/vsmpc_rt_core.hpp, driver in csrc/vsmpc_runtime.hip), step for step:
 
   P1  sensitivity recursion of every condensed column (joints 8 per block, throttles in the reference order, then the
       affine column), Y_k = sqrt(Q) (X_k - xref_k) on the 18 weighted rows, C = sum_k Y_k^T Y_k

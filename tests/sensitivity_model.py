@@ -4,7 +4,7 @@ tests/test_sensitivity_model.py and tests/test_gpu_sensitivity.py:
   kkt_jacobian        the oracle's dense reference-ordered QP (vsmpc_ref.assemble_dense / solve_exact) with its final active
                       set: [H Ae^T; Ae 0] [J; dy] = [0; E], Ae = the equality rows (dynamics, initial state) and the active
                       throttle rows, E = I_26 on the initial-state rows
-  condensed_jacobian  numpy mirror of sens_kernel_rt (csrc/vsmpc_runtime_body.inc), the way tests/runtime_model.py mirrors
+  condensed_jacobian  numpy mirror of sens_kernel_rt (csrc/vsmpc_rt_sens.hpp), the way tests/runtime_model.py mirrors
                       solve_kernel_rt: condensing with 26 parameter columns (X_0 = e_i, no input, no c, no reference), the
                       joint-column Cholesky, the box QP, then S_FF dv_F = -F~_F, L_jj^T du = -(L_vj^T dv + l~) and
                       dX_{k+1} = dX_k + dt_k (A dX_k + Bj dU + Bt dV)
