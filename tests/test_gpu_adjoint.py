@@ -1,6 +1,7 @@
 """The adjoint of the solve on the GPU (vsmpc_adjoint_batch, adjoint_kernel_rt[_tuned]): gradients against
 tests/adjoint_model.py (the numpy mirror and the dense-KKT route), grad_x0 against the shipped sensitivity entry, the solve
-outputs against solve(), per-instance tunables, determinism, the contracts of the entry points, and PlanFunction."""
+outputs against solve(), per-instance tunables, determinism, the contracts of the entry points, and PlanFunction.
+Records away from the synthetic workloads and the box QP's tabled active sets: tests/test_gpu_adjoint_records.py."""
 import dataclasses
 from ctypes import c_void_p
 from importlib import import_module

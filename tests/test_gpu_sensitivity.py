@@ -1,6 +1,7 @@
 """Sensitivities of the solution to X0 on the GPU (vsmpc_sensitivity_batch, sens_kernel_rt): Jacobians against
 tests/sensitivity_model.py, the solve outputs against solve(), affine exactness on the production path, the degeneracy
-flag, and the contracts of the entry points."""
+flag, and the contracts of the entry points.
+Records away from the synthetic workloads and the box QP's tabled active sets: tests/test_gpu_sensitivity_records.py."""
 import dataclasses
 from ctypes import c_void_p
 
