@@ -80,15 +80,16 @@ def _units():
         # short-horizon kernels (<= 256 registers, two workgroups per CU) gain 2-3 % with max-ilp -- 36.6 -> 35.7 us per 256-launch,
         # 327 -> 317 us per 4096 -- the long-horizon kernel (512 registers, tiles in AGPRs) loses 2.6 % (1,593 -> 1,634 us).
         sched = SCHED_MAX_ILP if n <= 24 else []
-        for st in (0, 1):
-            units.append((f"kernels_{n}_{ns}_{hc}_{'diag' if st else 'prod'}", SOLVE,
-                          [f"-DVS_TU_HORIZON={n},{ns},{hc}", f"-DVS_TU_STAMPS={st}"] + sched))
+        for name, kind in (("prod", "PRODUCTION"), ("diag", "DIAGNOSTIC")):
+            units.append((f"kernels_{n}_{ns}_{hc}_{name}", SOLVE,
+                          [f"-DVS_TU_HORIZON={n},{ns},{hc}", f"-DVS_TU_KIND=VS_KIND_{kind}"] + sched))
         for form in (0, 1):     # the per-instance-tunables kind: one unit per condensing form (1 = structured)
             units.append((f"kernels_{n}_{ns}_{hc}_tuned_{'struct' if form else 'syrk'}", SOLVE,
-                          [f"-DVS_TU_HORIZON={n},{ns},{hc}", "-DVS_TU_STAMPS=2", f"-DVS_TU_FORM={form}"] + sched))
+                          [f"-DVS_TU_HORIZON={n},{ns},{hc}", "-DVS_TU_KIND=VS_KIND_TUNED", f"-DVS_TU_FORM={form}"] + sched))
         # the small-batch kind (solve_kernel_small, production + diagnostic; a horizon without it gets a launcher that
         # refuses and that the dispatcher never calls).  Scheduler strategy: see SMALL_SCHED
-        units.append((f"kernels_{n}_{ns}_{hc}_small", SOLVE, [f"-DVS_TU_HORIZON={n},{ns},{hc}", "-DVS_TU_STAMPS=3"] + SMALL_SCHED))
+        units.append((f"kernels_{n}_{ns}_{hc}_small", SOLVE,
+                      [f"-DVS_TU_HORIZON={n},{ns},{hc}", "-DVS_TU_KIND=VS_KIND_SMALL"] + SMALL_SCHED))
     for src in SOURCES:
         if src != SOLVE:
             units.append((os.path.splitext(src)[0], src, []))
@@ -104,12 +105,30 @@ def _extra_flags():
     return os.environ.get("VSMPC_HIPCC_FLAGS", "").split()
 
 
+def _unit_options(unit):
+    """what hipcc is given for one unit of _units() besides the paths: what the code in its object depends on"""
+    return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c"] + _extra_flags() + unit[2]
+
+
+def _stamp(unit):
+    """(path, text now) of the unit's .flags stamp, written beside its object when it has compiled.  Neither the place of
+    the tree nor the compiler's is in the text: a tree that was copied with its library stays built."""
+    return os.path.join(OBJ_DIR, unit[0] + ".o.flags"), " ".join(_unit_options(unit) + [unit[1]])
+
+
+def _stamped(unit) -> bool:
+    path, text = _stamp(unit)
+    return os.path.exists(path) and open(path).read() == text
+
+
 def needs_build() -> bool:
+    """True when the library is missing, older than a source, or was built with other flags than a build would use now
+    (VSMPC_HIPCC_FLAGS: a measurement build must not pass for the production library, nor the reverse)"""
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in deps) or not all(_stamped(u) for u in _units())
 
 
 def build_library(force: bool = False, verbose: bool = False, jobs: int | None = None) -> str:
@@ -121,18 +140,15 @@ def build_library(force: bool = False, verbose: bool = False, jobs: int | None =
         return LIB_PATH
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
-    base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c"] + _extra_flags()
-    if verbose:
-        base.insert(1, "-Rpass-analysis=kernel-resource-usage")
     todo, objs = [], []
-    for name, src, flags in _units():
-        obj = os.path.join(OBJ_DIR, name + ".o")
-        stamp = obj + ".flags"
-        cmd = base + flags + [os.path.join(CSRC, src), "-o", obj]
+    for unit in _units():
+        obj = os.path.join(OBJ_DIR, unit[0] + ".o")
+        stamp, flagtext = _stamp(unit)
+        cmd = ([hipcc] + (["-Rpass-analysis=kernel-resource-usage"] if verbose else []) + _unit_options(unit)
+               + [os.path.join(CSRC, unit[1]), "-o", obj])
         objs.append(obj)
-        flagtext = " ".join(cmd)
-        fresh = (not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == flagtext
-                 and all(os.path.getmtime(d) <= os.path.getmtime(obj) for d in _deps(src)))
+        fresh = (not force and os.path.exists(obj) and _stamped(unit)
+                 and all(os.path.getmtime(d) <= os.path.getmtime(obj) for d in _deps(unit[1])))
         if not fresh:
             todo.append((cmd, stamp, flagtext))
 

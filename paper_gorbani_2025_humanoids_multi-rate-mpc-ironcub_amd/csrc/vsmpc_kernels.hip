@@ -60,11 +60,12 @@
 #include "vsmpc_p4.hpp"
 #include "vsmpc_p5.hpp"
 
-#if !defined(VS_TU_HORIZON) || !defined(VS_TU_STAMPS)
-#error "one unit per horizon and kind: -DVS_TU_HORIZON=N,NS,HC -DVS_TU_STAMPS=0|1, =2 -DVS_TU_FORM=0|1, or =3 (build.py)"
-#endif
-#if VS_TU_STAMPS == 2 && !defined(VS_TU_FORM)
-#error "a unit of the tuned kind holds one condensing form: -DVS_TU_FORM=0|1"
+#define VS_KIND_PRODUCTION 1   // the kinds of unit (see the launchers below); another name is 0: refused at the end of the file
+#define VS_KIND_DIAGNOSTIC 2
+#define VS_KIND_TUNED 3
+#define VS_KIND_SMALL 4
+#if !defined(VS_TU_HORIZON) || !defined(VS_TU_KIND) || (VS_TU_KIND == VS_KIND_TUNED && !defined(VS_TU_FORM))
+#error "one unit per horizon and kind: -DVS_TU_HORIZON=N,NS,HC -DVS_TU_KIND=VS_KIND_..., tuned kind: -DVS_TU_FORM=0|1 (build.py)"
 #endif
 
 namespace vsmpc {
@@ -221,8 +222,8 @@ VS_DEV const SolveArgs* late_args() {
 // forms agree to rounding (different summation order), which tests/test_gpu_parity.py checks on the device.
 // TUNED = true is the per-instance-tunables kind (vsmpc_solve_batch_tuned): `tun` holds one row of VSMPC_TUNE_SIZE doubles
 // per instance, in sCfg order (vsmpc_pack_tunables), which P0 loads beside the record and writes to sCfg where the shared
-// kind copies the kernel argument.  Nothing after P0 differs.  The body (vsmpc_solve_body.inc) is included under two kernel
-// entries so that the shared kind keeps its name, its arguments and its code.
+// kind copies the kernel argument.  Nothing after P0 differs.  The body (vsmpc_solve_body.inc; its head says what an includer
+// declares) is included under the three kernel entries below so that the shared kind keeps its name, arguments and code.
 template <class D, bool STAMPS, int FORM = 0>
 __global__ __launch_bounds__(D::BLOCK, D::WG_PER_CU) void solve_kernel(DevCfg cfg, const double* __restrict__ in, int batch,
                                                          double* xout_, double* fmout_, int* status_out_,
@@ -268,26 +269,29 @@ __global__ __launch_bounds__(D::BLOCK, D::WG_PER_CU) void solve_kernel_small(Dev
 // ------------------------------------------------------------------------------------------------
 // launchers of ONE horizon.  The kernels are straight-line template instantiations over Dims<nIter, nIterSmall,
 // controlHorizon>, ~10 instantiations of a 30 k-instruction kernel per horizon, so build.py compiles this file once per
-// horizon of csrc/vsmpc_horizons.def and kind, in parallel:
-//   -DVS_TU_HORIZON=N,NS,HC -DVS_TU_STAMPS=0|1   the production (0) or diagnostic (1) solve kernels of that horizon, as
-//                                          explicit instantiations of launch_solve_dims, which the dispatchers
-//                                          (vsmpc_dispatch.hip) only see declared (vsmpc_launch.hpp)
-//   -DVS_TU_HORIZON=N,NS,HC -DVS_TU_STAMPS=2 -DVS_TU_FORM=0|1   the per-instance-tunables kind (solve_kernel_tuned) of that
-//                                          horizon and condensing form, as launch_solve_tuned_dims
-//   -DVS_TU_HORIZON=N,NS,HC -DVS_TU_STAMPS=3   the small-batch kind (solve_kernel_small, production and diagnostic) of that
-//                                          horizon, as launch_solve_small_dims
+// horizon of csrc/vsmpc_horizons.def (-DVS_TU_HORIZON=N,NS,HC) and kind (-DVS_TU_KIND=), in parallel:
+//   VS_KIND_PRODUCTION, VS_KIND_DIAGNOSTIC   the solve kernels of that horizon, as explicit instantiations of launch_solve_dims,
+//                    which the dispatchers (vsmpc_dispatch.hip) only see declared (vsmpc_launch.hpp)
+//   VS_KIND_TUNED    solve_kernel_tuned of that horizon and condensing form (-DVS_TU_FORM=0|1), as launch_solve_tuned_dims
+//   VS_KIND_SMALL    solve_kernel_small (production and diagnostic) of that horizon, as launch_solve_small_dims
 // ------------------------------------------------------------------------------------------------
-template <class D, bool STAMPS, int FORM>
-static hipError_t launch_solve_f(const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm,
-                                 int* d_status, int* d_iters, double* dbgM, double* dbgL,
-                                 unsigned long long* stamps, hipStream_t stream) {
-    static std::atomic<bool> attr_set[MAX_DEVICES];   // (allow_dynamic_lds, vsmpc_launch.hpp)
-    constexpr size_t lds = FORM == 1 ? Smem<D>::bytes_struct : Smem<D>::bytes;
-    const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(&solve_kernel<D, STAMPS, FORM>), attr_set, lds);
+// One launch, one workgroup per instance: `lds` bytes of dynamic LDS, allowed once per kernel and device (attr_set is the
+// kernel's own, one per instantiation; allow_dynamic_lds, vsmpc_launch.hpp)
+template <auto Kernel, class D, class... Args>
+static hipError_t solve_launch(size_t lds, int batch, hipStream_t stream, Args... args) {
+    static std::atomic<bool> attr_set[MAX_DEVICES];
+    const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(Kernel), attr_set, lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((solve_kernel<D, STAMPS, FORM>), dim3(batch), dim3(D::BLOCK), lds, stream,
-                       cfg, d_in, batch, d_x, d_fm, d_status, d_iters, dbgM, dbgL, stamps);
+    hipLaunchKernelGGL(Kernel, dim3(batch), dim3(D::BLOCK), lds, stream, args...);
     return hipGetLastError();
+}
+
+template <class D, bool STAMPS, int FORM>
+static hipError_t launch_solve_f(const DevCfg& cfg, const double* d_in, int batch, double* d_x, double* d_fm, int* d_status,
+                                 int* d_iters, double* dbgM, double* dbgL, unsigned long long* stamps, hipStream_t stream) {
+    constexpr size_t lds = FORM == 1 ? Smem<D>::bytes_struct : Smem<D>::bytes;
+    return solve_launch<solve_kernel<D, STAMPS, FORM>, D>(lds, batch, stream, cfg, d_in, batch, d_x, d_fm, d_status, d_iters, dbgM,
+                                                          dbgL, stamps);
 }
 
 template <int N, int NS, int HC, bool STAMPS>
@@ -296,9 +300,7 @@ hipError_t launch_solve_dims(int form, const DevCfg& cfg, const double* d_in, in
                              hipStream_t stream) {
     using D = Dims<N, NS, HC>;
     if constexpr (D::STRUCT_P1) {
-        if (form != 2) {
-            return launch_solve_f<D, STAMPS, 1>(cfg, d_in, batch, d_x, d_fm, d_status, d_iters, dbgM, dbgL, stamps, stream);
-        }
+        if (form != 2) return launch_solve_f<D, STAMPS, 1>(cfg, d_in, batch, d_x, d_fm, d_status, d_iters, dbgM, dbgL, stamps, stream);
     }
     return launch_solve_f<D, STAMPS, 0>(cfg, d_in, batch, d_x, d_fm, d_status, d_iters, dbgM, dbgL, stamps, stream);
 }
@@ -310,18 +312,14 @@ hipError_t launch_solve_small_dims(const DevCfg& cfg, const double* d_in, int ba
     if constexpr (!has_small_kind<D>()) {
         return hipErrorInvalidValue;   // (launch_solve asks for the kind only where variant_has_small says the horizon has it)
     } else {
-        static std::atomic<bool> attr_set[2][MAX_DEVICES];
         constexpr size_t lds = Smem<D, true>::bytes_struct;
         static_assert(lds <= 160 * 1024, "the small-batch kind takes the LDS of one CU");
-        auto go = [&](auto stc) {
-            constexpr bool ST = decltype(stc)::value;
-            const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(&solve_kernel_small<D, ST>), attr_set[ST], lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((solve_kernel_small<D, ST>), dim3(batch), dim3(D::BLOCK), lds, stream, cfg, d_in, batch, d_x, d_fm,
-                               d_status, d_iters, static_cast<double*>(nullptr), static_cast<double*>(nullptr), stamps);
-            return hipGetLastError();
-        };
-        return stamps != nullptr ? go(std::true_type{}) : go(std::false_type{});
+        double* const no_dump = nullptr;
+        if (stamps != nullptr)
+            return solve_launch<solve_kernel_small<D, true>, D>(lds, batch, stream, cfg, d_in, batch, d_x, d_fm, d_status, d_iters,
+                                                                no_dump, no_dump, stamps);
+        return solve_launch<solve_kernel_small<D, false>, D>(lds, batch, stream, cfg, d_in, batch, d_x, d_fm, d_status, d_iters,
+                                                             no_dump, no_dump, stamps);
     }
 }
 
@@ -332,15 +330,12 @@ hipError_t launch_solve_tuned_dims(const DevCfg& cfg, const double* d_in, const 
     if constexpr (FORM == 1 && !D::STRUCT_P1) {
         return hipErrorInvalidValue;   // (launch_solve_tuned asks for the structured form only where the horizon has it)
     } else {
-        static std::atomic<bool> attr_set[MAX_DEVICES];
         constexpr size_t lds = FORM == 1 ? Smem<D>::bytes_struct : Smem<D>::bytes;
         static_assert(D::WG_PER_CU < 2 || lds <= 80 * 1024, "the tuned kind keeps two workgroups per CU");
-        const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(&solve_kernel_tuned<D, FORM>), attr_set, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((solve_kernel_tuned<D, FORM>), dim3(batch), dim3(D::BLOCK), lds, stream, cfg, d_in, batch, d_x, d_fm,
-                           d_status, d_iters, static_cast<double*>(nullptr), static_cast<double*>(nullptr),
-                           static_cast<unsigned long long*>(nullptr), d_tun);
-        return hipGetLastError();
+        double* const no_dump = nullptr;
+        unsigned long long* const no_stamps = nullptr;
+        return solve_launch<solve_kernel_tuned<D, FORM>, D>(lds, batch, stream, cfg, d_in, batch, d_x, d_fm, d_status, d_iters,
+                                                            no_dump, no_dump, no_stamps, d_tun);
     }
 }
 
@@ -354,14 +349,16 @@ hipError_t launch_solve_tuned_dims(const DevCfg& cfg, const double* d_in, const 
 #define VS_INSTANTIATE_SMALL(N, NS, HC)                                                                              \
     template hipError_t launch_solve_small_dims<N, NS, HC>(const DevCfg&, const double*, int, double*, double*, int*, int*, \
                                                            unsigned long long*, hipStream_t);
-#if VS_TU_STAMPS == 3
+#if VS_TU_KIND == VS_KIND_SMALL
 VS_TU_APPLY(VS_INSTANTIATE_SMALL, VS_TU_HORIZON)
-#elif VS_TU_STAMPS == 2
+#elif VS_TU_KIND == VS_KIND_TUNED
 VS_TU_APPLY(VS_INSTANTIATE_TUNED, VS_TU_HORIZON, VS_TU_FORM)
-#elif VS_TU_STAMPS
+#elif VS_TU_KIND == VS_KIND_DIAGNOSTIC
 VS_TU_APPLY(VS_INSTANTIATE_SOLVE, VS_TU_HORIZON, true)
-#else
+#elif VS_TU_KIND == VS_KIND_PRODUCTION
 VS_TU_APPLY(VS_INSTANTIATE_SOLVE, VS_TU_HORIZON, false)
+#else
+#error "VS_TU_KIND is none of VS_KIND_PRODUCTION, VS_KIND_DIAGNOSTIC, VS_KIND_TUNED, VS_KIND_SMALL"
 #endif
 
 }  // namespace vsmpc

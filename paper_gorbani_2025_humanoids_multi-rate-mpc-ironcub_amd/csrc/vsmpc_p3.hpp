@@ -32,6 +32,28 @@ VS_DEV double input_cost_term(const double* __restrict__ sCfg, const double* __r
     return 0.0;
 }
 
+// Debug / parity dumps of the diagnostic instantiation, one accumulator slot each (C/D fragment: row (lane >> 4) + 4 r,
+// column lane & 15), into the instance's NP x NP matrix.  Which slots are dumped is the caller's business (TileTab).
+// The augmented condensed Hessian before factorisation: tile (ti, tj) as P1 left it + the input-cost terms P2 adds (diagonal
+// tiles and the throttle rows), lower triangle
+template <class D>
+VS_DEV void dump_hessian_tile(double* __restrict__ Mi, int ti, int tj, d4 tile, const double* __restrict__ sCfg,
+                              const double* __restrict__ sGy, const double* __restrict__ sVprev, int lane) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int gr = 16 * ti + (lane >> 4) + 4 * r, gc = 16 * tj + (lane & 15);
+        if (ti == tj || ti >= D::PVT) tile[r] += input_cost_term<D>(sCfg, sGy, sVprev, gr, gc);
+        if (gc <= gr) Mi[size_t(gr) * D::NP + gc] = tile[r];
+    }
+}
+// The factor: a tile below the diagonal of a joint column, from the registers that hold it after P3 (the diagonal tiles are
+// written while they are panels, the throttle corner from LDS)
+template <class D>
+VS_DEV void dump_factor_tile(double* __restrict__ Li, int ti, int tj, const d4& tile, int lane) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Li[size_t(16 * ti + (lane >> 4) + 4 * r) * D::NP + 16 * tj + (lane & 15)] = tile[r];
+}
+
 // ------------------------------------------------------------------------------------------------
 // P3 panel factorisation in C++ by ONE wavefront, branch-free: lane l owns panel row 16p + l (lanes 0..15 = the diagonal
 // tile).  Pivot-column entries are broadcast with v_readlane.  The only panel it still factors is the LAST one of a horizon

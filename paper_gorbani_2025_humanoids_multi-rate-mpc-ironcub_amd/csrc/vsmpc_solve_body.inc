@@ -1,11 +1,21 @@
-// Body of the solve kernels (vsmpc_kernels.hip), P0 to P6, included inside solve_kernel (TUNED = false) and
-// solve_kernel_tuned (TUNED = true): each kernel has the template parameters D and FORM, declares `constexpr bool STAMPS`
-// and `constexpr bool TUNED`, and has the arguments cfg, in, batch and (tuned kind) tun before it; the trailing arguments
-// are read through late_args().  `constexpr bool SMALL` selects the small-batch kind (solve_kernel_small: structured form only,
-// its own LDS carve-up and tile-forming schedule, see SmallPlan in vsmpc_p3.hpp).  A textual body (not an inlined device function) keeps solve_kernel's code object
-// instruction for instruction what it was before solve_kernel_tuned existed (an inlined function did not: tools/isa_diff.py).
-    // (the trailing kernel parameters are read through late_args(), see SolveArgs)
-#define VS_STAMP(i)                                                                         \
+// Body of the solve kernels, P0 to P6: the text between the braces of solve_kernel, solve_kernel_tuned and
+// solve_kernel_small (vsmpc_kernels.hip).
+//
+// The includer declares, as template parameters, constants or kernel arguments:
+//   D       Dims<nIter, nIterSmall, controlHorizon>
+//   STAMPS  bool: the diagnostic instantiation (phase stamps, t_acc, the debug dumps)
+//   FORM    int: how P1 condenses, 0 = SYRK form, 1 = structured form (PIPE below; needs D::STRUCT_P1)
+//   TUNED   bool: P0 takes the weights and limits from the instance's row of `tun` instead of `cfg`
+//   SMALL   bool: the small-batch kind (FORM 1 and !TUNED only): Smem<D, true>, tiles formed beside the first panel streams
+//   cfg, in, batch, tun   kernel arguments (tun: a null constant where !TUNED)
+// and its arguments begin as SolveArgs does: everything behind `batch` is read through late_args().
+// Macros: VS_STAMP, VS_TIC, VS_TOC, VS_REFRESH_IDS and VS_P6_TOC are defined here and undefined at the end; VS_DIAG_QP,
+// VS_DIAG_P3 and VS_DIAG_P6 (measurement builds, from the command line) are read.
+//
+// Textual on purpose: the same text inlined from a device function is not the same kernel (three signatures tried: -3
+// instructions in solve_kernel<Dims<17,7,12>, false, 0>, -6 in <.., false, 1>; tools/isa_diff.py), and which of the two is
+// faster nobody has measured.  Sharing inside the body is by lambdas, each checked the same way.
+#define VS_STAMP(i)                                                                        \
     do {                                                                                    \
         if constexpr (STAMPS) {                                                             \
             unsigned long long* st_ = late_args()->stamps;                                  \
@@ -29,8 +39,9 @@
     } while (0)
     using S = Smem<D, SMALL>;   // (SMALL moves the arrays of P1a / P1s only)
     static_assert(!SMALL || (FORM == 1 && !TUNED), "the small-batch kind is the structured form of the shared kind");
-    constexpr bool FUSED_DISPATCH = FORM == 1;   // entries + P2 + P3 behind one wave dispatch (see P1)
-    // the structured form runs P3 pipelined: wavefront 0 factors the panels, wavefronts 1..3 hold all tiles (TileTab, cholesky_wave)
+    // The structured form: its tile entries, P2 and P3 sit behind one wave dispatch (see P1); P3 runs pipelined -- wavefront 0
+    // factors the panels, wavefronts 1..3 hold all tiles (TileTab, cholesky_wave) -- so wavefront 0 runs the jets link of P6
+    // beside P5, and P6 starts at the momenta
     constexpr bool PIPE = FORM == 1;
     // steps of the joint reduction that run in P0 (wavefront 3); the rest follows a generator chain in P1.  Long horizons
     // have ~9 k cycles of slack behind the generator chains, short ones ~3 k.
@@ -241,98 +252,68 @@
             __syncthreads();
         }
         VS_TOC(3);
-        if constexpr (FUSED_DISPATCH) {
-            // the shipped structured form: ONE wave dispatch for the entries, P2 and P3 -- the accumulator tiles are born and
-            // factored inside one branch, no join in between (at a join the allocator moved the tiles of a wavefront through
-            // the vector registers, and at the 2x horizon pushed other values into scratch to make room)
-            // (The diagnostic instantiation takes the same path; its dumps -- condensed Hessian before, factor after P3 -- and the
-            // stamps of the P1 / P2 / P3 boundaries sit inside the branch.)
-            auto tail = [&](auto wcst) __attribute__((always_inline)) {
-                constexpr int W = decltype(wcst)::value;
-                if constexpr (SMALL) {
-                    // only tile column 0, dealt over the four wavefronts, P2 term and hand-over to LDS included; the other
-                    // tiles are formed beside the first two panel streams (cholesky_wave).  Stamps 2 and 3 therefore both
-                    // mark "column 0 is in the ring": the rest of the entries and of P2 lies between stamps 3 and 4.
+        // ONE wave dispatch for the entries, P2 and P3 -- the accumulator tiles are born and factored inside one branch, no join
+        // in between (at a join the allocator moved the tiles of a wavefront through the vector registers, and at the 2x
+        // horizon pushed other values into scratch to make room).  The diagnostic instantiation takes the same path; its
+        // dumps -- condensed Hessian before, factor after P3 -- and the stamps of the P1 / P2 / P3 boundaries sit inside the
+        // branch.
+        auto tail = [&](auto wcst) __attribute__((always_inline)) {
+            constexpr int W = decltype(wcst)::value;
+            if constexpr (SMALL) {
+                // only tile column 0, dealt over the four wavefronts, P2 term and hand-over to LDS included; the other
+                // tiles are formed beside the first two panel streams (cholesky_wave).  Stamps 2 and 3 therefore both
+                // mark "column 0 is in the ring": the rest of the entries and of P2 lies between stamps 3 and 4.
+                static_for<0, TPW>([&](auto qcst) __attribute__((always_inline)) {
+                    constexpr int q = decltype(qcst)::value;
+                    if constexpr (small_instalment<D, TPW, W>(q) < 0) acc[q] = d4{0.0, 0.0, 0.0, 0.0};
+                });
+                const int ln0 = fresh_lane();
+                small_form<D, TPW, W, 0>(sCfg, acc, Lb, smem + S::oQR + S::QR_GY, sVprev, ln0, (ln0 >> 4) * 17 + (ln0 & 15));
+            } else {
+                p1s_entries<D, TPW, W, PIPE>(acc, smem, lane);
+            }
+            VS_TOC(2);
+            __syncthreads();   // the LDS arrays of P1s lie under the ring P3 is about to fill (not in the small-batch kind)
+            VS_STAMP(2);
+            constexpr TileTab<D, PIPE> tab{};
+            double* dbgLw = nullptr;
+            if constexpr (STAMPS && !SMALL) {   // (a dump needs all tiles at one point: the launcher asks the shipped kernel)
+                double* dbgM = late_args()->dbgM;
+                double* dbgL = late_args()->dbgL;
+                dbgLw = dbgL != nullptr ? dbgL + size_t(inst) * D::NP * D::NP : nullptr;
+                if (dbgM != nullptr) {
+                    const int ln = fresh_lane();
                     static_for<0, TPW>([&](auto qcst) __attribute__((always_inline)) {
                         constexpr int q = decltype(qcst)::value;
-                        if constexpr (small_instalment<D, TPW, W>(q) < 0) acc[q] = d4{0.0, 0.0, 0.0, 0.0};
+                        constexpr int t = q * D::NWAVES + W;
+                        if constexpr (tab.forms(t, W))
+                            dump_hessian_tile<D>(dbgM + size_t(inst) * D::NP * D::NP, tab.ti[t], tab.tj[t], acc[q], sCfg,
+                                                 smem + S::oQR + S::QR_GY, sVprev, ln);
                     });
-                    const int ln0 = fresh_lane();
-                    small_form<D, TPW, W, 0>(sCfg, acc, Lb, smem + S::oQR + S::QR_GY, sVprev, ln0, (ln0 >> 4) * 17 + (ln0 & 15));
-                } else {
-                    p1s_entries<D, TPW, W, PIPE>(acc, smem, lane);
                 }
-                VS_TOC(2);
-                __syncthreads();   // the LDS arrays of P1s lie under the ring P3 is about to fill (not in the small-batch kind)
-                VS_STAMP(2);
-                double* dbgLw = nullptr;
-                if constexpr (STAMPS && !SMALL) {   // (a dump needs all tiles at one point: the launcher asks the shipped kernel)
-                    constexpr TileTab<D, PIPE> tab{};
-                    double* dbgM = late_args()->dbgM;
-                    double* dbgL = late_args()->dbgL;
-                    dbgLw = dbgL != nullptr ? dbgL + size_t(inst) * D::NP * D::NP : nullptr;
-                    if (dbgM != nullptr) {   // debug/parity only: the augmented condensed Hessian before factorisation, from registers
-                        const int ln = fresh_lane();
-                        static_for<0, TPW>([&](auto qcst) __attribute__((always_inline)) {
-                            constexpr int q = decltype(qcst)::value;
-                            constexpr int t = q * D::NWAVES + W;
-                            if constexpr (tab.forms(t, W)) {
-                                constexpr int ti_q = tab.ti[t], tj_q = tab.tj[t];
-                                d4 tmp = acc[q];
-                                if constexpr (ti_q == tj_q || ti_q >= D::PVT) {
-#pragma unroll
-                                    for (int r = 0; r < 4; ++r)
-                                        tmp[r] += input_cost_term<D>(sCfg, smem + S::oQR + S::QR_GY, sVprev, 16 * ti_q + (ln >> 4) + 4 * r,
-                                                                     16 * tj_q + (ln & 15));
-                                }
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    const int gr = 16 * ti_q + (ln >> 4) + 4 * r, gc = 16 * tj_q + (ln & 15);
-                                    if (gc <= gr) dbgM[size_t(inst) * D::NP * D::NP + size_t(gr) * D::NP + gc] = tmp[r];
-                                }
-                            }
-                        });
-                    }
-                }
-                VS_STAMP(3);
-                if constexpr (D::WG_PER_CU == 1) pin_tiles_agpr<TPW>(acc);
-                const int ln = fresh_lane();
-                cholesky_wave<D, TPW, W, STAMPS, PIPE, SMALL>(sCfg, acc, Lb, sInvD, smem + S::oQR + S::QR_GY, sVprev, sFlags, sXinv, sW, dbgLw, ln,
-                                                      (ln >> 4) * 17 + (ln & 15), (ln & 15) * 17 + (ln >> 4), sZ);
-                if constexpr (STAMPS) {
-                    if (dbgLw != nullptr) {  // debug/parity only: the factor; diagonal tiles were written while they were panels
-                        constexpr TileTab<D, PIPE> tab{};
-                        const int l2 = fresh_lane();
-                        static_for<0, TPW>([&](auto qcst) __attribute__((always_inline)) {
-                            constexpr int q = decltype(qcst)::value;
-                            constexpr int t = q * D::NWAVES + W;
-                            if constexpr (tab.holds(t, W)) {
-                                constexpr int ti_q = tab.ti[t], tj_q = tab.tj[t];
-                                if constexpr (tj_q < D::PVT && ti_q > tj_q) {
-#pragma unroll
-                                    for (int r = 0; r < 4; ++r)
-                                        dbgLw[size_t(16 * ti_q + (l2 >> 4) + 4 * r) * D::NP + 16 * tj_q + (l2 & 15)] = acc[q][r];
-                                }
-                            }
-                        });
-                    }
-                }
-            };
-            switch (wave) {
-                case 0: tail(std::integral_constant<int, 0>{}); break;
-                case 1: tail(std::integral_constant<int, 1>{}); break;
-                case 2: tail(std::integral_constant<int, 2>{}); break;
-                default: tail(std::integral_constant<int, 3>{}); break;
             }
-        } else {
+            VS_STAMP(3);
+            if constexpr (D::WG_PER_CU == 1) pin_tiles_agpr<TPW>(acc);
+            const int ln = fresh_lane();
+            cholesky_wave<D, TPW, W, STAMPS, PIPE, SMALL>(sCfg, acc, Lb, sInvD, smem + S::oQR + S::QR_GY, sVprev, sFlags, sXinv, sW, dbgLw, ln,
+                                                  (ln >> 4) * 17 + (ln & 15), (ln & 15) * 17 + (ln >> 4), sZ);
+            if constexpr (STAMPS) {
+                if (dbgLw != nullptr) {
+                    const int l2 = fresh_lane();
+                    static_for<0, TPW>([&](auto qcst) __attribute__((always_inline)) {
+                        constexpr int q = decltype(qcst)::value;
+                        constexpr int t = q * D::NWAVES + W;
+                        if constexpr (tab.holds(t, W) && tab.tj[t] < D::PVT && tab.ti[t] > tab.tj[t])
+                            dump_factor_tile<D>(dbgLw, tab.ti[t], tab.tj[t], acc[q], l2);
+                    });
+                }
+            }
+        };
         switch (wave) {
-            case 0: p1s_entries<D, TPW, 0, PIPE>(acc, smem, lane); break;
-            case 1: p1s_entries<D, TPW, 1, PIPE>(acc, smem, lane); break;
-            case 2: p1s_entries<D, TPW, 2, PIPE>(acc, smem, lane); break;
-            default: p1s_entries<D, TPW, 3, PIPE>(acc, smem, lane); break;
-        }
-        VS_TOC(2);
-        __syncthreads();   // the LDS arrays of P1s lie under the ring P3 is about to fill
+            case 0: tail(std::integral_constant<int, 0>{}); break;
+            case 1: tail(std::integral_constant<int, 1>{}); break;
+            case 2: tail(std::integral_constant<int, 2>{}); break;
+            default: tail(std::integral_constant<int, 3>{}); break;
         }
     } else {
 #pragma unroll
@@ -530,62 +511,61 @@
         }
         VS_TIC();
     }
-    if constexpr (!FUSED_DISPATCH) VS_STAMP(2);   // (the fused branch stamps its own P1 / P2 / P3 boundaries)
     VS_REFRESH_IDS();
     if constexpr (D::WG_PER_CU == 1) pin_tiles_agpr<TPW>(acc);   // long horizons: see pin_tiles_agpr
 
     // ---------------------------------------------------------------- P2 + P3 (wave-specialised, see cholesky_wave)
+    static_assert(D::NWAVES == 4, "wave-specialised phases are instantiated for four wavefronts");
     constexpr int PVT = D::PVT;  // first tile row that contains a throttle row
     const int crow = (lane >> 4) * 17 + (lane & 15);  // C/D fragment: row (lane>>4)+4r, column lane&15
     const int lrow = (lane & 15) * 17 + (lane >> 4);  // A/B fragment: row lane&15, k = lane>>4
-    // The debug dumps (condensed Hessian, factor) exist in the diagnostic instantiation only (STAMPS; the launcher picks it
-    // when a dump or the stamps are asked for): in the shipped kernel their code -- input_cost_term per element, a branch
-    // around every store -- cost registers at the joins for nothing.
-    double* dbgM = STAMPS ? late_args()->dbgM : nullptr;
+    // The debug dumps (condensed Hessian, factor; dump_hessian_tile, dump_factor_tile) exist in the diagnostic instantiation
+    // only (STAMPS; the launcher picks it when a dump or the stamps are asked for): in the shipped kernel their code --
+    // input_cost_term per element, a branch around every store -- cost registers at the joins for nothing.
     double* dbgL = STAMPS ? late_args()->dbgL : nullptr;
     double* dbgLi = dbgL != nullptr ? dbgL + size_t(inst) * D::NP * D::NP : nullptr;
-    if (STAMPS && !FUSED_DISPATCH && dbgM != nullptr) {  // debug/parity only: the augmented condensed Hessian before factorisation, from registers
+    VS_REFRESH_IDS();   // (crow / lrow keep the derivation above, `lane` below is this one: as shipped)
+    if constexpr (!PIPE) {   // the SYRK form's P2 + P3 (the structured form ran them inside its wave dispatch, stamps and dumps included)
+        // The dumps look the coordinates up through a copy of `wave` the compiler cannot see through.  With the plain index
+        // it based the dword loads of ti / tj of slot 0 on the byte address of valid[wave] (table + wave, offset 3 wave), and
+        // a scalar load ignores the low two bits of its base: wavefronts 1..3 dumped slot 0 at another tile's coordinates.
+        // (The table is named inside the diagnostic branches only: the shipped units carry no copy of it.)
+        int wave_c = wave;
+        if constexpr (STAMPS) asm volatile("" : "+s"(wave_c));
+        VS_STAMP(2);
+        if constexpr (STAMPS) {
+            const TileTab<D, PIPE>& tab = kTileTab<D, PIPE>;
+            double* dbgM = late_args()->dbgM;
+            if (dbgM != nullptr) {
 #pragma unroll
-        for (int q = 0; q < TPW; ++q) {
-            if (kTileTab<D, PIPE>.forms(q * D::NWAVES + wave, wave)) {
-                const int ti_q = kTileTab<D, PIPE>.ti[q * D::NWAVES + wave], tj_q = kTileTab<D, PIPE>.tj[q * D::NWAVES + wave];
-                d4 tmp = acc[q];
-                if (ti_q == tj_q || ti_q >= PVT) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        tmp[r] += input_cost_term<D>(sCfg, smem + S::oQR + S::QR_GY, sVprev, 16 * ti_q + (lane >> 4) + 4 * r,
-                                                     16 * tj_q + (lane & 15));
+                for (int q = 0; q < TPW; ++q) {
+                    const int t = q * D::NWAVES + wave, tc = q * D::NWAVES + wave_c;
+                    if (tab.forms(t, wave))
+                        dump_hessian_tile<D>(dbgM + size_t(inst) * D::NP * D::NP, tab.ti[tc], tab.tj[tc], acc[q], sCfg,
+                                             smem + S::oQR + S::QR_GY, sVprev, lane);
                 }
+            }
+        }
+        VS_STAMP(3);
+        switch (wave) {  // scalar dispatch: every wavefront runs its own straight-line copy, same barrier count
+            case 0: cholesky_wave<D, TPW, 0, STAMPS, PIPE>(sCfg, acc, Lb, sInvD, smem + S::oQR + S::QR_GY, sVprev, sFlags, sXinv, sW, dbgLi, lane, crow, lrow, sZ); break;
+            case 1: cholesky_wave<D, TPW, 1, STAMPS, PIPE>(sCfg, acc, Lb, sInvD, smem + S::oQR + S::QR_GY, sVprev, sFlags, sXinv, sW, dbgLi, lane, crow, lrow, sZ); break;
+            case 2: cholesky_wave<D, TPW, 2, STAMPS, PIPE>(sCfg, acc, Lb, sInvD, smem + S::oQR + S::QR_GY, sVprev, sFlags, sXinv, sW, dbgLi, lane, crow, lrow, sZ); break;
+            default: cholesky_wave<D, TPW, 3, STAMPS, PIPE>(sCfg, acc, Lb, sInvD, smem + S::oQR + S::QR_GY, sVprev, sFlags, sXinv, sW, dbgLi, lane, crow, lrow, sZ); break;
+        }
+        if constexpr (STAMPS) {
+            const TileTab<D, PIPE>& tab = kTileTab<D, PIPE>;
+            if (dbgLi != nullptr) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int gr = 16 * ti_q + (lane >> 4) + 4 * r, gc = 16 * tj_q + (lane & 15);
-                    if (gc <= gr) dbgM[size_t(inst) * D::NP * D::NP + size_t(gr) * D::NP + gc] = tmp[r];
+                for (int q = 0; q < TPW; ++q) {
+                    const int t = q * D::NWAVES + wave, tc = q * D::NWAVES + wave_c;
+                    if (tab.holds(t, wave) && tab.tj[tc] < PVT && tab.ti[tc] > tab.tj[tc])
+                        dump_factor_tile<D>(dbgLi, tab.ti[tc], tab.tj[tc], acc[q], lane);
                 }
             }
         }
     }
-    if constexpr (!FUSED_DISPATCH) VS_STAMP(3);
-    VS_REFRESH_IDS();
-    if constexpr (!FUSED_DISPATCH)
-    switch (wave) {  // scalar dispatch: every wavefront runs its own straight-line copy, same barrier count
-        case 0: cholesky_wave<D, TPW, 0, STAMPS, PIPE>(sCfg, acc, Lb, sInvD, smem + S::oQR + S::QR_GY, sVprev, sFlags, sXinv, sW, dbgLi, lane, crow, lrow, sZ); break;
-        case 1: cholesky_wave<D, TPW, 1, STAMPS, PIPE>(sCfg, acc, Lb, sInvD, smem + S::oQR + S::QR_GY, sVprev, sFlags, sXinv, sW, dbgLi, lane, crow, lrow, sZ); break;
-        case 2: cholesky_wave<D, TPW, 2, STAMPS, PIPE>(sCfg, acc, Lb, sInvD, smem + S::oQR + S::QR_GY, sVprev, sFlags, sXinv, sW, dbgLi, lane, crow, lrow, sZ); break;
-        default: cholesky_wave<D, TPW, 3, STAMPS, PIPE>(sCfg, acc, Lb, sInvD, smem + S::oQR + S::QR_GY, sVprev, sFlags, sXinv, sW, dbgLi, lane, crow, lrow, sZ); break;
-    }
-    static_assert(D::NWAVES == 4, "wave-specialised phases are instantiated for four wavefronts");
-    if (STAMPS && dbgLi != nullptr) {  // debug/parity only: the factor; diagonal tiles were written while they were panels
-        if constexpr (!FUSED_DISPATCH) {
-#pragma unroll
-            for (int q = 0; q < TPW; ++q) {
-                const int ti_q = kTileTab<D, PIPE>.ti[q * D::NWAVES + wave], tj_q = kTileTab<D, PIPE>.tj[q * D::NWAVES + wave];
-                if (kTileTab<D, PIPE>.holds(q * D::NWAVES + wave, wave) && tj_q < PVT && ti_q > tj_q) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        dbgLi[size_t(16 * ti_q + (lane >> 4) + 4 * r) * D::NP + 16 * tj_q + (lane & 15)] = acc[q][r];
-                }
-            }
-        }
+    if (STAMPS && dbgLi != nullptr) {
         for (int e = tid; e < (D::NP - 16 * PVT) * (D::NP - 16 * PVT); e += D::BLOCK) {  // throttle corner, from LDS
             const int gr = 16 * PVT + e / (D::NP - 16 * PVT), gc = 16 * PVT + e % (D::NP - 16 * PVT);
             if (gc <= gr) dbgLi[size_t(gr) * D::NP + gc] = Lb[lower_at<D>(gr, gc)];
@@ -612,6 +592,21 @@
     if (tid < D::NP) sZ[tid] = (hold && tid >= D::NZ - 4 && tid < D::NZ) ? sVprev[tid - (D::NZ - 4)] : 0.0;
     __syncthreads();
 
+    // behind tile row p of the sweep: its z leaves the right-hand sides of the corner columns to its left (corner columns
+    // only: the joint columns are updated from registers in P5)
+    auto corner_update = [&](int p) __attribute__((always_inline)) {
+        if (p > PV) {
+            if (tid >= 16 * PV && tid < 16 * p) {
+                const double* T = Lb + tile_off<D>(p, tid >> 4) + (tid & 15);
+                const double* zp = sZ + 16 * p;
+                double a2 = 0.0;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) a2 += T[k * 17] * zp[k];
+                sW[tid] -= a2;
+            }
+            __syncthreads();
+        }
+    };
     // one tile step of the sweep over the corner; `prescribed` = throttles already fixed in sZ
     auto sweep_tile = [&](int p, bool prescribed) {
         if (wave == 0) {
@@ -640,17 +635,7 @@
             if (lane < 16) sZ[gj] = z;
         }
         __syncthreads();
-        if (p > PV) {  // corner columns only: the joint columns are updated from registers in P5
-            if (tid >= 16 * PV && tid < 16 * p) {
-                const double* T = Lb + tile_off<D>(p, tid >> 4) + (tid & 15);
-                const double* zp = sZ + 16 * p;
-                double a2 = 0.0;
-#pragma unroll
-                for (int k = 0; k < 16; ++k) a2 += T[k * 17] * zp[k];
-                sW[tid] -= a2;
-            }
-            __syncthreads();
-        }
+        corner_update(p);
     };
 
     constexpr bool DUALQP = S::DUALQP;
@@ -728,17 +713,7 @@
                 if (lane < 16) sZ[16 * p + j] = z0 + z1;
             }
             __syncthreads();
-            if (p > PV) {
-                if (tid >= 16 * PV && tid < 16 * p) {
-                    const double* T = Lb + tile_off<D>(p, tid >> 4) + (tid & 15);
-                    const double* zp = sZ + 16 * p;
-                    double a2 = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) a2 += T[k * 17] * zp[k];
-                    sW[tid] -= a2;
-                }
-                __syncthreads();
-            }
+            corner_update(p);
         };
         if (wave == 1) tile_inverse_rows<8, 13>(L22d, inv2, x2, lane);
         sweep_tile_x(PV + 1, smem + S::oDual3T0);
@@ -773,13 +748,12 @@
 
 #ifdef VS_DIAG_QP   // measurement build: the box QP in four parts -> t_acc[0..3] (see vsmpc_p4.hpp)
     for (int i = 0; i < 4; ++i) t_acc[i] = 0;
+    unsigned long long* const qp_cycles = STAMPS ? t_acc : nullptr;
+#else
+    constexpr unsigned long long* qp_cycles = nullptr;
 #endif
     if (need_qp) {
-#ifdef VS_DIAG_QP
-        box_qp<D>(sFlags[3], hold, wave, STAMPS ? t_acc : nullptr);
-#else
-        box_qp<D>(sFlags[3], hold, wave);
-#endif
+        box_qp<D>(sFlags[3], hold, wave, qp_cycles);
         __syncthreads();
         VS_STAMP(6);
         VS_REFRESH_IDS();
@@ -825,6 +799,17 @@
     double* fmout = ka->fmout;
     int* status_out = ka->status_out;
     int* iters_out = ka->iters_out;
+    // entry l of the first-move block.  Everything in it is known once the jets' node 1 is; its throttle percentages cost a
+    // square root
+    auto write_first_move = [&](int l) __attribute__((always_inline)) {
+        double v;
+        if (l < 8) v = sU[l];                                        // delta q           (variableSamplingMPC.cpp:99)
+        else if (l < 12) v = sV[D::NV - 4 + (l - 8)];                // v0                (:100)
+        else if (l < 16) v = Jet::throttle_of_v(sV[D::NV - 4 + (l - 12)]);  // throttle % (:146-149)
+        else if (l < 20) v = sX[NX + 12 + (l - 16)];                 // thrust, node 1    (:101)
+        else v = sX[NX + 16 + (l - 20)];                             // thrust rate, node 1 (:102)
+        fmout[size_t(inst) * VSMPC_FM_SIZE + l] = v;
+    };
     // wavefront 3 has no element of the input-term pass below (pipelined schedule: 6 N of them): it starts taking the reduced joint
     // unknowns back to joint increments here -- the first three reflectors; the rest beside the first pipeline step
     double u8[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -872,10 +857,9 @@
         const int hr0m = (lane & 1) ? 9 : 3;                       // wavefront 1, lane < 2: h_lin / h_ang
         const int cg = lane / 3, cr = lane - 3 * cg;               // wavefront 2, lane < 6: (half, row)
         const int cxr = (cg ? 6 : 0) + cr, chr0 = cg ? 9 : 3, cer = (cg ? 23 : 20) + cr;
-        // (pipelined schedule: the jets ran beside P5, p5_wave0_jets; the cascade starts at the momenta)
-        constexpr bool JETS_EARLY = PIPE;
-        constexpr int JOFF = JETS_EARLY ? 0 : 1;
-        if (!JETS_EARLY && wave == 0 && lane < NTH) {
+        // (pipelined schedule: the jets ran beside P5, p5_wave0_jets; the cascade starts at the momenta, a step earlier)
+        constexpr int JOFF = PIPE ? 0 : 1;
+        if (!PIPE && wave == 0 && lane < NTH) {
             jon = sA[(12 + lane) * NX + 16 + lane]; ja = sA[(16 + lane) * NX + 12 + lane]; jb = sA[(16 + lane) * NX + 16 + lane];
             jT = sIn[VSMPC_IN_X0 + 12 + lane]; jTd = sIn[VSMPC_IN_X0 + 16 + lane];
             sX[12 + lane] = jT;
@@ -919,7 +903,7 @@
 
         static_for<0, NCH + 1 + JOFF>([&](auto scst) __attribute__((always_inline)) {
             constexpr int st = decltype(scst)::value;
-            if constexpr (!JETS_EARLY && st < NCH) {   // jets, chunk st
+            if constexpr (!PIPE && st < NCH) {   // jets, chunk st
                 if (wave == 0 && lane < NTH) {
                     constexpr int k0 = st * CHK;
                     double fa[CHK], fb[CHK], dtk[CHK];
@@ -943,18 +927,10 @@
                     }
                 }
             }
-            // pipelined schedule: wavefront 3 sends the first-move block beside the second step -- everything in it is known (the
-            // jets' node 1 since P5), and its throttle percentages cost a square root that has no business on the kernel's last stretch
+            // pipelined schedule: wavefront 3 sends the first-move block beside the second step (the jets' node 1 is known since
+            // P5), which keeps the square root off the kernel's last stretch
             if constexpr (PIPE && st == 1) {
-                if (wave == 3 && fmout != nullptr && lane < VSMPC_FM_SIZE) {
-                    double v;
-                    if (lane < 8) v = sU[lane];                                        // delta q           (variableSamplingMPC.cpp:99)
-                    else if (lane < 12) v = sV[D::NV - 4 + (lane - 8)];                // v0                (:100)
-                    else if (lane < 16) v = Jet::throttle_of_v(sV[D::NV - 4 + (lane - 12)]);  // throttle % (:146-149)
-                    else if (lane < 20) v = sX[NX + 12 + (lane - 16)];                 // thrust, node 1    (:101)
-                    else v = sX[NX + 16 + (lane - 20)];                                // thrust rate, node 1 (:102)
-                    fmout[size_t(inst) * VSMPC_FM_SIZE + lane] = v;
-                }
+                if (wave == 3 && fmout != nullptr && lane < VSMPC_FM_SIZE) write_first_move(lane);
             }
             if constexpr (st >= JOFF && st - JOFF < NCH) {   // momenta, chunk st - JOFF
                 if (wave == 1) {
@@ -1030,15 +1006,7 @@
         for (int i = tid; i < D::NXS / 2; i += D::BLOCK) xo[i] = make_double2(sX[2 * i], sX[2 * i + 1]);
         // (the joint increments and the throttles left from wavefront 3 during the cascade)
     }
-    if (!PIPE && fmout != nullptr && tid < VSMPC_FM_SIZE) {   // (pipelined schedule: sent by wavefront 3 during the cascade)
-        double v;
-        if (tid < 8) v = sU[tid];                                        // delta q           (variableSamplingMPC.cpp:99)
-        else if (tid < 12) v = sV[D::NV - 4 + (tid - 8)];                // v0                (:100)
-        else if (tid < 16) v = Jet::throttle_of_v(sV[D::NV - 4 + (tid - 12)]);  // throttle % (:146-149)
-        else if (tid < 20) v = sX[NX + 12 + (tid - 16)];                 // thrust, node 1    (:101)
-        else v = sX[NX + 16 + (tid - 20)];                               // thrust rate, node 1 (:102)
-        fmout[size_t(inst) * VSMPC_FM_SIZE + tid] = v;
-    }
+    if (!PIPE && fmout != nullptr && tid < VSMPC_FM_SIZE) write_first_move(tid);   // (pipelined schedule: sent during the cascade)
     if (tid == 0) {
         int st = sFlags[1];
         if (sFlags[0]) st = VSMPC_STATUS_NUMERICAL;
@@ -1062,3 +1030,4 @@
 #undef VS_REFRESH_IDS
 #undef VS_TIC
 #undef VS_TOC
+#undef VS_P6_TOC

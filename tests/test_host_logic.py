@@ -50,3 +50,36 @@ def test_config_derived_sizes(layout, ref):
     for pc, rc in ((layout.paper_config(), ref.paper_config()), (layout.horizon2x_config(), ref.horizon2x_config())):
         assert (pc.n_var, pc.n_con, pc.n_in, pc.ratio) == (rc.n_var, rc.n_con, rc.n_in, rc.ratio)
         assert pc.n_inputs == pc.n_var - 26 * (pc.n_iter + 1)
+
+
+def test_needs_build_compares_the_flags_of_every_unit(pkg, tmp_path, monkeypatch):
+    """A library built with other VSMPC_HIPCC_FLAGS (a measurement build) is not the library a plain build would make, and
+    the reverse: build.needs_build() reads the .flags stamp beside every object.  No compiler runs here: a fake library
+    newer than every source, and stamps as a plain build leaves them, in a temporary directory."""
+    import importlib
+    import os
+    import time
+    b = importlib.import_module(pkg.__name__ + ".build")
+    monkeypatch.delenv("VSMPC_HIPCC_FLAGS", raising=False)
+    monkeypatch.setattr(b, "OBJ_DIR", str(tmp_path / "build"))
+    monkeypatch.setattr(b, "LIB_PATH", str(tmp_path / "libvsmpc.so"))
+    assert b.needs_build()                                   # no library
+    os.makedirs(b.OBJ_DIR)
+    (tmp_path / "libvsmpc.so").write_bytes(b"")
+    later = time.time() + 3600.0
+    os.utime(b.LIB_PATH, (later, later))
+    assert b.needs_build()                                   # no stamps
+    units = b._units()
+    assert len(units) > 10
+    for unit in units:
+        path, text = b._stamp(unit)
+        assert os.path.dirname(path) == b.OBJ_DIR and str(tmp_path) not in text
+        with open(path, "w") as f:
+            f.write(text)
+    assert not b.needs_build()
+    monkeypatch.setenv("VSMPC_HIPCC_FLAGS", "-DVS_DIAG_QP")
+    assert b.needs_build()
+    monkeypatch.delenv("VSMPC_HIPCC_FLAGS")
+    assert not b.needs_build()
+    os.remove(b._stamp(units[-1])[0])                        # one unit's stamp missing
+    assert b.needs_build()

@@ -19,7 +19,7 @@ def main():
     asm = os.path.join(tmp, "vsmpc_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
     if not os.path.exists(asm) or os.environ.get("SPILL_REBUILD"):
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c",
-                        f"-DVS_TU_HORIZON={hz}", "-DVS_TU_STAMPS=0", "--save-temps=obj", SRC, "-o", os.path.join(tmp, "k.o")]
+                        f"-DVS_TU_HORIZON={hz}", "-DVS_TU_KIND=VS_KIND_PRODUCTION", "--save-temps=obj", SRC, "-o", os.path.join(tmp, "k.o")]
                        + os.environ.get("VSMPC_HIPCC_FLAGS", "").split(), cwd=tmp, check=True, capture_output=True)
     S = open(asm).read().split("\n")
     n, ns, hc = hz.split(",")
