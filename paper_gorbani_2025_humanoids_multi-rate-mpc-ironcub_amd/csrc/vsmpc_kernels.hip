@@ -32,7 +32,11 @@
 //   P5 back-subst  joints from the register-resident factor, tile row by tile row: z_r = X_r^T (w_r - u_r), then every
 //                  wavefront adds L_rq^T z_r of the tiles it owns to its partial sums u_q
 //                  (pipelined schedule: the panel wavefront, which holds no tile, runs the jets link of P6 beside it)
-//   P6 simulate    state trajectory, primal in the reference variable order, first-move block
+//   P6 simulate    state trajectory, primal in the reference variable order, first-move block.  Pipelined schedule: the
+//                  momenta link and the CoM / RPY link with its integrators are one stream in one wavefront, a state row per
+//                  lane, a half of the model per 16-lane row, the 3 x 3 products as DPP row_newbcast FMAs (no barrier
+//                  inside); the other wavefronts expand the joints and send the inputs and the first move meanwhile.  SYRK
+//                  form: the three links in three wavefronts, a chunk of stages apart
 //                                                            (variableSamplingMPC.cpp:93-108,138-151)
 //
 // FP64 throughout.  The un-condensed KKT system the reference hands to OSQP has condition number

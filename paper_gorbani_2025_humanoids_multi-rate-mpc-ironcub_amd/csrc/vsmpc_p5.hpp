@@ -106,8 +106,9 @@ VS_DEV void backsub_wave(const d4 (&acc)[TPW], const double* __restrict__ sW, do
 // P5, wavefront 0 of the pipelined schedule (kernel v29).  It holds no tile, so the back-substitution has nothing for it to do
 // but meet its barriers -- and the first link of P6's cascade, the jets, depends on the throttles only, which are final
 // since P4: their input terms and their whole two-state recursion (systemDynamicsVSMPC.cpp:384-429) run here, beside P5,
-// CHJ stages per barrier interval.  P6 then starts at the momenta, one pipeline step shorter.  (Wavefront 0's slot of the
-// partial sums is zeroed once; wavefront 1 stores z.)
+// CHJ stages per barrier interval.  P6 then starts at the momenta with every T_k in sX: its input-term pass forms the whole
+// forcing A_mom T_k + f_k, and the momenta and CoM / RPY links run as one stream with no barrier inside.  (Wavefront 0's slot
+// of the partial sums is zeroed once; wavefront 1 stores z.)
 // ------------------------------------------------------------------------------------------------
 template <class D>
 VS_DEV void p5_wave0_jets(double* __restrict__ smem, int lane) {

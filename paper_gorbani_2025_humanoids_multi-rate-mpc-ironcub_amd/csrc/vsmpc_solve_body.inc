@@ -787,7 +787,9 @@
     // ---------------------------------------------------------------- P6 forward simulation + outputs
     // the output pointers: requested from the kernarg segment here, a phase ahead of their use (a scalar load is a
     // ~0.5 us round trip when it misses, and nothing else in P6 wants the scalar registers)
-#ifdef VS_DIAG_P6   // measurement build: P6 in four pieces (input terms / set-up + first step / other steps / outputs) -> t_acc[0..3]
+#ifdef VS_DIAG_P6   // measurement build: P6 in four pieces -> t_acc[0..3].  Pipelined schedule: the forcing pass / the stream as
+                    // wavefront 1 ran it / that wavefront's wait at the closing barrier (what the side work of the other
+                    // wavefronts costs) / outputs.  SYRK form: input terms / set-up + first step / other steps / outputs
     for (int i = 0; i < 4; ++i) t_acc[i] = 0;
     VS_TIC();
 #define VS_P6_TOC(i) VS_TOC(i)
@@ -819,15 +821,18 @@
     // (straight-line rounds with clamped indices: the loads of all rounds are in flight together; as a loop with a per-thread
     // trip count the rounds ran one LDS round trip after the other)
     // Pipelined schedule: only the six momentum rows are read from here (the jets formed theirs beside P5, the CoM / RPY link has
-    // constant input terms and reads c itself): 6 N elements, one round.
+    // constant input terms and reads c itself), and every T_k is in sX since P5 (p5_wave0_jets), so the element goes on to the
+    // finished forcing g_k = A_mom T_k + f_k.  A seventh element per stage puts -0.0 into row 0: what the lanes of the stream
+    // below that have no forcing start their sums from.  7 N elements, one round.
     {
-        constexpr int ROWS = PIPE ? 6 : NX;
+        constexpr int ROWS = PIPE ? 7 : NX;
         constexpr int NE = ROWS * D::N, RND = (NE + D::BLOCK - 1) / D::BLOCK;
+        static_assert(!PIPE || RND == 1, "the forcing of the pipelined schedule is one round");
 #pragma unroll
         for (int rd = 0; rd < RND; ++rd) {
             const int e0 = tid + rd * D::BLOCK, ec = e0 < NE ? e0 : NE - 1;
             const int k = ec / ROWS, rr = ec - k * ROWS;
-            const int r = PIPE ? (rr < 3 ? 3 + rr : 6 + rr) : rr;   // rows 3..5, 9..11
+            const int r = PIPE ? (rr < 3 ? 3 + rr : (rr < 6 ? 6 + rr : 0)) : rr;   // rows 3..5, 9..11; 0: the -0.0
             const int e = NX * k + r;
             const int jb = joint_block_of_stage<D>(k);
             const int tb = throttle_block_of_stage<D>(k);
@@ -837,13 +842,18 @@
             for (int c = 0; c < NJC; ++c) f += sBj[r * NJ + c] * sZ[NJC * jb + c];
 #pragma unroll
             for (int c = 0; c < NTH; ++c) f += sBt[r * NTH + c] * sV[vq + c];
+            if constexpr (PIPE) {
+#pragma unroll
+                for (int c = 0; c < NTH; ++c) f = fma(sA[r * NX + 12 + c], sX[NX * k + 12 + c], f);
+                if (rr == 6) f = -0.0;
+            }
             if (e0 < NE) sF[e] = f;
         }
     }
     __syncthreads();
     VS_P6_TOC(0);
-    {
-        // The three links of the cascade (jets -> momenta -> CoM / RPY + error integrators; systemDynamicsVSMPC.cpp:
+    if constexpr (!PIPE) {
+        // SYRK form.  The three links of the cascade (jets -> momenta -> CoM / RPY + error integrators; systemDynamicsVSMPC.cpp:
         // 79-103,288-319,384-429) run in THREE wavefronts, one chunk of CHK stages apart: step s = jets of chunk s (wavefront
         // 0), momenta of chunk s - 1 (wavefront 1, after adding A_mom T_k to its forcing), CoM / RPY of chunk s - 2
         // (wavefront 2); a workgroup barrier per step hands the trajectories over through sX.  NCH + 2 steps instead of the
@@ -857,9 +867,8 @@
         const int hr0m = (lane & 1) ? 9 : 3;                       // wavefront 1, lane < 2: h_lin / h_ang
         const int cg = lane / 3, cr = lane - 3 * cg;               // wavefront 2, lane < 6: (half, row)
         const int cxr = (cg ? 6 : 0) + cr, chr0 = cg ? 9 : 3, cer = (cg ? 23 : 20) + cr;
-        // (pipelined schedule: the jets ran beside P5, p5_wave0_jets; the cascade starts at the momenta, a step earlier)
-        constexpr int JOFF = PIPE ? 0 : 1;
-        if (!PIPE && wave == 0 && lane < NTH) {
+        constexpr int JOFF = 1;   // the momenta run a step behind the jets
+        if (wave == 0 && lane < NTH) {
             jon = sA[(12 + lane) * NX + 16 + lane]; ja = sA[(16 + lane) * NX + 12 + lane]; jb = sA[(16 + lane) * NX + 16 + lane];
             jT = sIn[VSMPC_IN_X0 + 12 + lane]; jTd = sIn[VSMPC_IN_X0 + 16 + lane];
             sX[12 + lane] = jT;
@@ -885,8 +894,7 @@
         // U_i = W^(-1/2) (Q y_i + N n), one block per lane, into the (dead) partial-sum array of P5
         static_assert(D::NUO <= D::NWAVES * D::NP, "joint increments fit the partial-sum array");
         if (wave == 3 && lane < D::HC) {
-            if constexpr (PIPE) joint_expand<D, JX_SPLIT, 0>(smem + S::oQR, sZ + NJC * lane, u8);
-            else joint_expand<D>(smem + S::oQR, sZ + NJC * lane, u8);
+            joint_expand<D>(smem + S::oQR, sZ + NJC * lane, u8);
 #pragma unroll
             for (int i = 0; i < 8; ++i) sU[NJ * lane + i] = u8[i];
         }
@@ -903,7 +911,7 @@
 
         static_for<0, NCH + 1 + JOFF>([&](auto scst) __attribute__((always_inline)) {
             constexpr int st = decltype(scst)::value;
-            if constexpr (!PIPE && st < NCH) {   // jets, chunk st
+            if constexpr (st < NCH) {   // jets, chunk st
                 if (wave == 0 && lane < NTH) {
                     constexpr int k0 = st * CHK;
                     double fa[CHK], fb[CHK], dtk[CHK];
@@ -926,11 +934,6 @@
                         }
                     }
                 }
-            }
-            // pipelined schedule: wavefront 3 sends the first-move block beside the second step (the jets' node 1 is known since
-            // P5), which keeps the square root off the kernel's last stretch
-            if constexpr (PIPE && st == 1) {
-                if (wave == 3 && fmout != nullptr && lane < VSMPC_FM_SIZE) write_first_move(lane);
             }
             if constexpr (st >= JOFF && st - JOFF < NCH) {   // momenta, chunk st - JOFF
                 if (wave == 1) {
@@ -995,9 +998,117 @@
             if constexpr (st + 1 < NCH + 1 + JOFF) __syncthreads();
             if constexpr (st == 0) VS_P6_TOC(1);
         });
+    } else {
+        // Pipelined schedule (v37): the momenta link and the CoM / RPY link with its error integrators are ONE lane-parallel
+        // stream in wavefront 1, all N stages straight-line, no barrier inside.  One state row per lane, one half of the model per
+        // 16-lane row:
+        //   16-lane row 0 (linear):   lanes 0..2 h_lin (state rows 3..5),  lanes 3..5 CoM (rows 0..2) + integrators (rows 20..22)
+        //   16-lane row 1 (angular):  lanes 0..2 h_ang (rows 9..11),       lanes 3..5 RPY (rows 6..8) + integrators (rows 23..25)
+        // Both links multiply a 3 x 3 block by the same h_k, which lanes 0..2 of the row hold: v_fmac_f64 with DPP row_newbcast
+        // feeds it to the row inside the FMA, three instructions per stage for both links and both halves.  A momentum lane
+        // starts its sum from the forcing g_k, the others from the -0.0 of row 0 of sF: fma(c, h, -0.0) is c * h for every
+        // input, signed zeros included, so every operation is the one the three-wavefront cascade did, in its order.
+        // The whole wavefront runs the stream under one execution mask (the broadcasts' source lanes must be enabled): lanes
+        // without a row have zero coefficients and a zero state, and store into words of their own in the (dead) X region.
+        constexpr int JUNK = 128 + NX * (D::N + 1);   // doubles the ownerless stores can reach
+        static_assert(JUNK + 2 <= S::NXT * D::TS, "the ownerless stores of the stream stay inside the X region");
+        double* junk = sXinv;
+#ifdef VS_DIAG_P6
+        unsigned long long* p6t = reinterpret_cast<unsigned long long*>(junk + JUNK);   // the stream's start and end (wavefront 1)
+#endif
+        if (wave == 1) {
+#ifdef VS_DIAG_P6
+            if constexpr (STAMPS) { if (lane == 0) p6t[0] = __builtin_amdgcn_s_memtime(); }
+#endif
+            const int half = (lane >> 4) & 1, l = lane & 15;
+            const bool own = lane < 32 && l < 6, mom = own && l < 3, integ = own && !mom;
+            const int r3 = l < 3 ? l : (l < 6 ? l - 3 : 0);
+            const int hc0 = half ? 9 : 3;                                         // first momentum row of the half
+            const int srow = (l < 3 ? hc0 : (half ? 6 : 0)) + r3, cer = (half ? 23 : 20) + r3;
+            // unconditional loads from addresses that are valid for every lane, selected afterwards
+            double c0 = sA[srow * NX + hc0], c1 = sA[srow * NX + hc0 + 1], c2 = sA[srow * NX + hc0 + 2];
+            double cce = sC[cer], xs = sIn[VSMPC_IN_X0 + srow], ee = sIn[VSMPC_IN_X0 + cer];
+            c0 = own ? c0 : 0.0; c1 = own ? c1 : 0.0; c2 = own ? c2 : 0.0;
+            xs = own ? xs : 0.0;
+            cce = integ ? cce : 0.0;
+            ee = integ ? ee : 0.0;
+            double* xp = own ? sX + srow : junk + lane;          // + NX (k + 1): immediate offsets
+            double* ep = integ ? sX + cer : junk + 64 + lane;
+            const double* gp = sF + (mom ? srow : 0);
+            xp[0] = xs;
+            ep[0] = ee;
+            // at most ~24 stages per batch of loads: the 2x horizon keeps its register picture
+            constexpr int NSB = (D::N + 23) / 24, CHS = (D::N + NSB - 1) / NSB;
+#pragma unroll
+            for (int sb = 0; sb < NSB; ++sb) {
+                double gk[CHS], dtk[CHS];
+#pragma unroll
+                for (int u = 0; u < CHS; ++u) {
+                    const int k = (sb * CHS + u < D::N) ? sb * CHS + u : D::N - 1;
+                    gk[u] = gp[NX * k];
+                    dtk[u] = sDt[k];
+                }
+#pragma unroll
+                for (int u = 0; u < CHS; ++u) {
+                    const int k = sb * CHS + u;
+                    if (k < D::N) {
+                        // The hazard recogniser does not look inside inline assembly: `xs` was written by the previous stage's
+                        // last FMA (2 wait states before a DPP read), in front of the first stage possibly under another
+                        // execution mask (5).
+                        if (k == 0)
+                            asm volatile("s_nop 4\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:2 row_mask:0xf bank_mask:0xf" : "+v"(gk[u]) : "v"(xs), "v"(c2));
+                        else
+                            asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:2 row_mask:0xf bank_mask:0xf" : "+v"(gk[u]) : "v"(xs), "v"(c2));
+                        asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:1 row_mask:0xf bank_mask:0xf" : "+v"(gk[u]) : "v"(xs), "v"(c1));
+                        asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf" : "+v"(gk[u]) : "v"(xs), "v"(c0));
+                        ee = fma(dtk[u], xs + cce, ee);   // the integrator sees the state of node k
+                        xs = fma(dtk[u], gk[u], xs);
+                        xp[NX * (k + 1)] = xs;
+                        ep[NX * (k + 1)] = ee;
+                    }
+                }
+            }
+#ifdef VS_DIAG_P6
+            if constexpr (STAMPS) { if (lane == 0) p6t[1] = __builtin_amdgcn_s_memtime(); }
+#endif
+        }
+        // Beside it, none of which may reach the closing barrier behind the stream: wavefront 3 finishes the joint increments
+        // U_i = W^(-1/2) (Q y_i + N n), one block per lane, into the (dead) partial-sum array of P5, and sends them and the
+        // first-move entries made of them; wavefront 0 sends the throttle part of the primal, wavefront 2 the first-move
+        // entries that need no joint (the jets' node 1 is known since P5; their square roots are the long part).
+        static_assert(D::NUO <= D::NWAVES * D::NP, "joint increments fit the partial-sum array");
+        if (wave == 3) {
+            if (lane < D::HC) {
+                joint_expand<D, JX_SPLIT, 0>(smem + S::oQR, sZ + NJC * lane, u8);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) sU[NJ * lane + i] = u8[i];
+            }
+            if (xout != nullptr) {
+                double2* xo = reinterpret_cast<double2*>(xout + size_t(inst) * D::NVAR);  // 16 B per lane stores
+                for (int i = lane; i < D::NUO / 2; i += 64) xo[D::NXS / 2 + i] = make_double2(sU[2 * i], sU[2 * i + 1]);
+            }
+            if (fmout != nullptr && lane < 8) write_first_move(lane);
+        }
+        if (wave == 0 && xout != nullptr && lane < D::NV / 2) {  // reference order v_0..v_{NVB-1}
+            double2* xo = reinterpret_cast<double2*>(xout + size_t(inst) * D::NVAR);
+            const int e = 2 * lane, b = e >> 2, c = e & 3;
+            const int q = b == 0 ? D::NV - 4 + c : 4 * (b - 1) + c;
+            xo[(D::NXS + D::NUO) / 2 + lane] = make_double2(sV[q], sV[q + 1]);
+        }
+        if (wave == 2 && fmout != nullptr && lane < VSMPC_FM_SIZE - 8) write_first_move(8 + lane);
     }
     __syncthreads();
-    VS_P6_TOC(2);
+#ifdef VS_DIAG_P6
+    if constexpr (STAMPS && PIPE) {   // the stream and its wait at the closing barrier, as wavefront 1 saw them
+        const unsigned long long* p6t = reinterpret_cast<const unsigned long long*>(sXinv + 128 + NX * (D::N + 1));
+        const unsigned long long t_now = __builtin_amdgcn_s_memtime();
+        t_acc[1] = p6t[1] - p6t[0];
+        t_acc[2] = t_now - p6t[1];
+        t_mark = t_now;
+    } else {
+        VS_P6_TOC(2);
+    }
+#endif
     VS_STAMP(8);
     VS_REFRESH_IDS();
 

@@ -9,9 +9,10 @@ solve_kernel<...> that only the OLD build has (the retired PLDS parameter) is dr
 
 Compared per kernel: the instruction text (mnemonic and operands; encodings and addresses are not; branch operands are
 PC-relative and so position independent as they stand; the literal of a PC-relative address -- s_getpc_b64 followed by
-s_add_u32 -- is replaced by the data object it points into and the offset inside it, or by section and section offset
-where no object symbol covers the address: where the constant tables lie relative to the code, and behind how many
-kernel descriptors in .rodata, is layout; which table an instruction reads is not) and the resource notes of the
+s_add_u32 -- is replaced by the data object or the kernel it points into and the offset inside it -- a long branch inside
+a kernel, so that a kernel does not differ because another kernel in front of it in the same object changed size -- or by
+section and section offset where no symbol covers the address: where the constant tables lie relative to the code, and
+behind how many kernel descriptors in .rodata, is layout; which table an instruction reads is not) and the resource notes of the
 code-object metadata.
 
 NOT compared: the constant data the kernels read (the tile tables and the kernel descriptors in .rodata).  A change that
@@ -40,7 +41,7 @@ _INS = re.compile(r"^\s+(\S.*?)\s*//\s*([0-9A-Fa-f]+):")
 _GETPC = re.compile(r"^s_getpc_b64 s\[(\d+):\d+\]")
 _PCADD = re.compile(r"^(s_add_u32 s(\d+), s(\d+), )(0x[0-9a-f]+|-?\d+)$")
 _SECTION = re.compile(r"^\s*\d+\s+(\S+)\s+([0-9a-f]+)\s+([0-9a-f]+)\s")
-_OBJECT = re.compile(r"^([0-9a-f]+)\s+\S+\s+O\s+\S+\s+([0-9a-f]+)\s+(?:\.\S+\s+)?(\S+)\s*$")
+_OBJECT = re.compile(r"^([0-9a-f]+)\s+\S+\s+[OF]\s+\S+\s+([0-9a-f]+)\s+(?:\.\S+\s+)?(\S+)\s*$")
 
 
 def demangle(names):
