@@ -286,9 +286,10 @@ VS_DEV void p1s_chain(const DevCfg& cfg, int half, int lane, double* __restrict_
 
 // sAc[c][i - 1][q] = sum over the halves of A_mom,half[:, q]^T W_c(i): the throttle x throttle tiles read it as a matrix-core
 // operand.  All wavefronts, between the chains and the entries: one (c, i) pair and its four q per thread and round.
-template <class D, bool SMALL = false>
+// (The small-batch kind runs it off that path: p1s_contract_beside.)
+template <class D>
 VS_DEV void p1s_contract(double* __restrict__ sm, int tid) {
-    using S = Smem<D, SMALL>;
+    using S = Smem<D>;
     constexpr int NI = (D::NV + 1) * (D::N - 1);
     constexpr int ROUNDS = (NI + D::BLOCK - 1) / D::BLOCK;
     const double* sA = sm + S::oA;
@@ -320,6 +321,45 @@ VS_DEV void p1s_contract(double* __restrict__ sm, int tid) {
 #pragma unroll
             for (int q = 0; q < NTH; ++q) sAc[ci * 4 + q] = v[q];
         }
+    }
+}
+
+// The same contraction as the small-batch kind runs it: by wavefronts 1..3 (t = 0 .. 191) beside panel stream 0, at the head of
+// their instalment 1 (small_form) -- nothing reads sAc before instalment 2, and the barrier that closes stream 0 publishes it.
+// One round at a time (the column-0 tiles are live in registers here); every item's expression and summation order are those
+// of p1s_contract, so the values are bit for bit the same.
+template <class D>
+VS_DEV void p1s_contract_beside(double* __restrict__ sm, int t) {
+    using S = Smem<D, true>;
+    constexpr int NI = (D::NV + 1) * (D::N - 1);
+    constexpr int NTHR = (D::NWAVES - 1) * 64;
+    constexpr int ROUNDS = (NI + NTHR - 1) / NTHR;
+    const double* sA = sm + S::oA;
+    const double* sW3 = sm + S::oSW3;
+    double* sAc = sm + S::oSAc;
+    double Am[6][NTH];   // uniform addresses: LDS broadcasts
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int q = 0; q < NTH; ++q) { Am[a][q] = sA[(3 + a) * NX + 12 + q]; Am[3 + a][q] = sA[(9 + a) * NX + 12 + q]; }
+#pragma unroll
+    for (int rd = 0; rd < ROUNDS; ++rd) {
+        const int ci = t + rd * NTHR, cic = ci < NI ? ci : NI - 1;
+        double w[6];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { w[a] = sW3[cic * 3 + a]; w[3 + a] = sW3[(NI + cic) * 3 + a]; }
+        double v[NTH];
+#pragma unroll
+        for (int q = 0; q < NTH; ++q) {
+            v[q] = Am[0][q] * w[0];
+#pragma unroll
+            for (int a = 1; a < 6; ++a) v[q] = fma(Am[a][q], w[a], v[q]);
+        }
+        if (ci < NI) {
+#pragma unroll
+            for (int q = 0; q < NTH; ++q) sAc[ci * 4 + q] = v[q];
+        }
+        __builtin_amdgcn_sched_barrier(0);   // (a round's operands are dead before the next round asks for its own)
     }
 }
 

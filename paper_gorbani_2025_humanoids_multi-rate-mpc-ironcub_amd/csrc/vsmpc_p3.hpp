@@ -457,10 +457,19 @@ VS_DEV void p2_terms(const double* __restrict__ sCfg, d4 (&acc)[TPW], const doub
 //   instalment 0  in front of stream 0: tile column 0, dealt over all four wavefronts -- wavefronts 1..3 form the column-0
 //                 tiles they will later hold (in the slots the factors come back to), wavefront 0 takes two of wavefront 1's
 //                 (wavefront 1 holds one more than the others) -- each adds its P2 term and stores the tile into ring slot 0
-//   instalment 1  wavefronts 1..3 beside stream 0 (which wavefront 0 runs alone, in two row slots): tile column 1, which the
-//                 update between streams 0 and 1 needs, and the next tiles in slot order up to SMALL_BESIDE0 per wavefront
-//   instalment 2  wavefronts 1..3 beside stream 1, in front of rest-update(0), the first update that touches them: the rest
-// Per tile the order of operations is the shipped one: entries, P2 term, panel updates 0, 1, ...  No barrier moves.
+//   instalment 1  wavefronts 1..3 beside stream 0 (which wavefront 0 runs alone, in two row slots): first the contraction sAc
+//                 (p1s_contract_beside: 192 threads, three rounds -- the shipped kernels run it on all threads behind a barrier of
+//                 its own in front of the entries), then tile column 1, which the update between streams 0 and 1 needs, and
+//                 the next tiles in slot order up to SMALL_BESIDE0 per wavefront.  None of them reads sAc.
+//   instalment 2  wavefronts 1..3 beside stream 1, in front of rest-update(0), the first update that touches them: the rest,
+//                 the three throttle x throttle tiles among them (small_ac_tiles_last), which read sAc behind the barrier
+//                 that closes stream 0
+// Per tile the order of operations is the shipped one: entries, P2 term, panel updates 0, 1, ...  Two barriers of the shipped
+// kernel do not exist here, in any of the four wavefront copies: the one behind the contraction, and the first one of
+// cholesky_wave, which would follow the barrier behind instalment 0 with nothing in between.
+// SMALL_BESIDE0, measured with the contraction in instalment 1 (profiles/small_offpath_phase_cycles.txt): 3 makes instalment 2
+// and rest-update(0) outlast stream 1 (P3 +1.0 k cycles), 5 takes 0.16 k off P3 but not off the launch (30.47-30.55 us against
+// 30.21-30.43 in alternation).
 // ------------------------------------------------------------------------------------------------
 constexpr int SMALL_BESIDE0 = 4;
 template <class D>
@@ -476,6 +485,10 @@ constexpr int small_instalment(int q) {      // -1: this wavefront never forms s
     if (tab.tj[t] == 0) return (W == 1 && small_wave0_forms<D>(tab.ti[t])) ? -1 : 0;
     int n = 0;
     for (int b = 0; b < q; ++b) n += (tab.ok(b * D::NWAVES + W) && tab.tj[b * D::NWAVES + W] > 0) ? 1 : 0;
+    // a throttle x throttle tile reads sAc, which is formed at the head of instalment 1: never before instalment 2 (at the paper
+    // horizon the count puts them there anyway; shorter horizons have too few tiles for that).  None is in column 1, which
+    // has to be formed beside stream 0: has_small_kind asks for PVT >= 2
+    if (tab.ti[t] >= D::PVT && tab.tj[t] >= D::PVT) return 2;
     return (tab.tj[t] == 1 || n < SMALL_BESIDE0) ? 1 : 2;
 }
 template <class D, int TPW, int W, int INST>
@@ -514,12 +527,32 @@ constexpr bool small_plan_complete() {
         if (col0[i] != 1) return false;
     return true;
 }
+// every tile that reads sAc (throttle x throttle) is formed in instalment 2: sAc itself is formed beside stream 0, at the head
+// of instalment 1 (p1s_contract_beside), and the barrier that closes that stream is the first one behind it
+template <class D, int TPW>
+constexpr bool small_ac_tiles_last() {
+    constexpr TileTab<D, true> tab{};
+    for (int q = 0; q < TPW; ++q) {
+        const int inst[D::NWAVES] = {small_instalment<D, TPW, 0>(q), small_instalment<D, TPW, 1>(q), small_instalment<D, TPW, 2>(q),
+                                     small_instalment<D, TPW, 3>(q)};
+        for (int w = 0; w < D::NWAVES; ++w) {
+            const int t = q * D::NWAVES + w;
+            if (inst[w] >= 0 && tab.ti[t] >= D::PVT && tab.tj[t] >= D::PVT && inst[w] != 2) return false;
+        }
+    }
+    return true;
+}
 // one instalment of wavefront W: entries, P2 term, and (instalment 0) the tile into the first panel column
 template <class D, int TPW, int W, int INST>
 VS_DEV void small_form(const double* __restrict__ sCfg, d4 (&acc)[TPW], double* __restrict__ sM, const double* __restrict__ sGy,
                        const double* __restrict__ sVprev, int lane, int crow) {
     using PLAN = SmallPlan<D, TPW, W, INST>;
     static_assert(small_plan_complete<D, TPW>(), "every tile is formed exactly once");
+    static_assert(small_ac_tiles_last<D, TPW>(), "the tiles that read sAc are formed behind the barrier that publishes it");
+    if constexpr (INST == 1) {
+        static_assert(W >= 1, "wavefront 0 runs stream 0 meanwhile");
+        p1s_contract_beside<D>(sM - Smem<D>::oM, 64 * (W - 1) + lane);
+    }
     if constexpr (PLAN::count > 0) {
         p1s_entries<D, TPW, W, true, PLAN>(acc, sM - Smem<D>::oM, lane);
         p2_terms<D, TPW, W, true, PLAN>(sCfg, acc, sGy, sVprev, lane);
@@ -559,7 +592,9 @@ VS_DEV void cholesky_wave(const double* __restrict__ sCfg, d4 (&acc)[TPW], doubl
             for (int r = 0; r < 4; ++r) T[4 * r * 17] = acc[q][r];
         }
     }
-    __syncthreads();
+    // (small-batch kind: column 0 went to LDS in instalment 0, and the barrier behind that -- the caller's, straight in front
+    // of this call -- is this one)
+    if constexpr (!SMALL) __syncthreads();
 #ifdef VS_DIAG_P3
     unsigned long long p3_mark = __builtin_amdgcn_s_memtime();
     if (DEBUG && W == 0 && lane < 4) vs_diag_p3[lane] = 0;

@@ -106,7 +106,8 @@ struct Smem {
     //   sH [2][NJPAIR][3][3]      block sums of H(i, i') over (row block, column block) pairs of the joint blocks
     //   sRb[2][NV + 1][HC][3]     W_c(i) of the throttle columns and of the affine column, summed over joint blocks
     //   sW3[2][NV + 1][N - 1][3]  W_c(i), i = 1 .. N - 1, of the throttle columns and of the affine column
-    //   sAc[NV + 1][N - 1][4]     sum over the halves of A_mom[:, q]^T W_c(i) (formed by all wavefronts after the chains)
+    //   sAc[NV + 1][N - 1][4]     sum over the halves of A_mom[:, q]^T W_c(i) (formed by all wavefronts after the chains;
+    //                             small-batch kind: by wavefronts 1..3 beside panel stream 0)
     //   sRefC[NREF][12]           reference window with the integrator offsets c_e folded into the x rows
     //   sZero                     zeros: what the columns without a thrust trajectory / forcing / reference read
     static constexpr int oSH = oGA + 6 * D::N;
@@ -153,9 +154,11 @@ struct Smem {
 };
 
 // Horizons with the small-batch kind of the solve kernel: those whose shipped kernel is the pipelined structured form at two
-// workgroups per CU (when the batch does not exceed the CUs the second workgroup slot of a CU is empty anyway)
+// workgroups per CU (when the batch does not exceed the CUs the second workgroup slot of a CU is empty anyway), and whose tile
+// column 1 holds no throttle x throttle tile (PVT >= 2): column 1 is formed beside stream 0, where the contraction those
+// tiles read is still being formed
 template <class D>
-constexpr bool has_small_kind() { return D::STRUCT_P1 && !D::STRUCT_LONG && D::WG_PER_CU == 2; }
+constexpr bool has_small_kind() { return D::STRUCT_P1 && !D::STRUCT_LONG && D::WG_PER_CU == 2 && D::PVT >= 2; }
 
 // tile (i, j), j <= i, of the factor in LDS: panel columns left of the throttle corner live in a ring of two
 // (even columns at tile 0, odd ones at tile RING_A), the corner is dense behind the ring

@@ -247,8 +247,10 @@
         VS_TOC(0);
         __syncthreads();
         VS_TOC(1);
-        if constexpr (!D::STRUCT_LONG) {
-            p1s_contract<D, SMALL>(smem, tid);
+        // (the small-batch kind forms sAc beside panel stream 0, in wavefronts 1..3: nothing in front of that stream reads it,
+        // and this barrier is not on its path -- small_form, instalment 1)
+        if constexpr (!D::STRUCT_LONG && !SMALL) {
+            p1s_contract<D>(smem, tid);
             __syncthreads();
         }
         VS_TOC(3);
@@ -273,7 +275,8 @@
                 p1s_entries<D, TPW, W, PIPE>(acc, smem, lane);
             }
             VS_TOC(2);
-            __syncthreads();   // the LDS arrays of P1s lie under the ring P3 is about to fill (not in the small-batch kind)
+            __syncthreads();   // the LDS arrays of P1s lie under the ring P3 is about to fill (not in the small-batch kind, where
+                               // this is the barrier behind instalment 0 and the only one in front of stream 0)
             VS_STAMP(2);
             constexpr TileTab<D, PIPE> tab{};
             double* dbgLw = nullptr;
