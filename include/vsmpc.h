@@ -153,6 +153,10 @@ int vsmpc_create(const vsmpc_config* cfg, int device, int max_batch, vsmpc_handl
                                            for the rows.  Bit 0x10 is reserved (refused like every unknown bit) */
 #define VSMPC_CREATE_ADJOINT 0x40u      /* what vsmpc_adjoint_batch needs (below): the runtime-sized kernel's workspace where the
                                            handle has none, and the staging of the host-pointer entry */
+#define VSMPC_CREATE_ADJOINT_RECORD 0x80u   /* what vsmpc_adjoint_record_batch needs (below): everything VSMPC_CREATE_ADJOINT
+                                           allocates (the flag implies it) and the staging of grad_in and grad_model for the
+                                           chunks of the host-pointer entry, min(max_batch, 256) x (n_in +
+                                           VSMPC_GRAD_MODEL_SIZE) doubles.  No later call allocates */
 int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned flags, vsmpc_handle** out);
 void vsmpc_destroy(vsmpc_handle* h);
 
@@ -255,7 +259,7 @@ int vsmpc_sensitivity_batch_device(vsmpc_handle* h, const double* d_in, int batc
  * bit what rows packed from the handle's configuration give).  Per instance:
  *   x, first_move, status, iters   what vsmpc_solve_batch[_tuned] returns (bit for bit on a runtime handle, to rounding on a
  *                                  tuned one, with the same iterations)
- *   grad_x0[26]                    dL/dX0 (X0 = in[VSMPC_IN_X0 .. +26]; the other record fields are held fixed)
+ *   grad_x0[26]                    dL/dX0 (X0 = in[VSMPC_IN_X0 .. +26]; for the other record fields: vsmpc_adjoint_record_batch)
  *   grad_cfg[VSMPC_GRAD_SIZE]      dL/d(field) in the order of the vsmpc_config fields (VSMPC_GRAD_* below): with respect to
  *                                  the values a caller writes -- weights, not their square roots; throttle limits in percent,
  *                                  not warped.  Entry 31 is 0.
@@ -295,6 +299,48 @@ int vsmpc_adjoint_batch_device(vsmpc_handle* h, const double* d_in, const double
                                const double* d_fmbar, int batch, double* d_x, double* d_first_move, int* d_status,
                                int* d_iters, double* d_grad_x0, double* d_grad_cfg, int* d_active, int* d_adj_flags,
                                void* stream);
+
+/*
+ * Adjoint of the record: vsmpc_adjoint_batch, and beside its outputs the gradient of L with respect to EVERY entry of the
+ * input record -- the reference window, the previous throttle, the linearisation point, the posture error and the model
+ * data of the kinematics provider -- and with respect to the linearisation itself.  With nu the multipliers of the solve
+ * and K [a; b] = [xbar; 0] as above, dL/dp = -a' (dH/dp x + dg/dp + dE'/dp nu) + b' (de/dp - dE/dp x) for any parameter p of
+ * the QP min 1/2 x'Hx + g'x, E x = e of the final active set ("Adjoint of the record"; executable model:
+ * tests/adjoint_record_model.py).  nu is one more costate recursion, dL/d(A, Bj, Bt, c) a sum of rank-one terms over the
+ * stages, and the record entries follow through the transposed linearisation: no Jacobian, no second factorisation, no
+ * finite differences.
+ * Needs a handle created with VSMPC_CREATE_ADJOINT_RECORD (both entries; otherwise VSMPC_ERR_UNSUPPORTED_CONFIG, and
+ * vsmpc_strerror names the flag).  It solves with adjoint_record_kernel_rt / adjoint_record_kernel_rt_tuned: the adjoint
+ * kernel with two more phases, on tuned handles too.  Arguments and outputs of vsmpc_adjoint_batch, bit for bit, plus, per
+ * instance (each may be NULL):
+ *   grad_in[n_in]                        dL/d in[.], entry by entry in the layout of the record (VSMPC_IN_*), all other
+ *                                        entries held fixed.  grad_in[VSMPC_IN_X0 .. +26] is grad_x0.  The hold flag is a
+ *                                        switch: 0.  The entries nothing reads (in[VSMPC_IN_RPY + 2] and, where nIter > nIterSmall,
+ *                                        the last column of the window) get +0.0.  With use_jet_dynamic = 0 the entries of T0, TD0, TDES and
+ *                                        TDDES are 0 and UPREV keeps its direct part (initial-throttle cost, hold pin).
+ *   grad_model[VSMPC_GRAD_MODEL_SIZE]    dL/d(A | Bj | Bt | c), row-major blocks in the layout of vsmpc_linearize_batch at the
+ *                                        offsets VSMPC_GRAD_MODEL_*: every entry of the four, also those the linearisation
+ *                                        leaves at zero
+ * The time grid (dt, the periods) is structural: no gradient.  Not Solved: VSMPC_ADJ_UNSOLVED and every entry of both is 0;
+ * a non-finite entry of xbar or fmbar: every entry of both is NaN for that instance alone; VSMPC_ADJ_DEGENERATE as above (the
+ * gradients are those of the final active set's affine piece).  Every sum has an order fixed by the sizes alone.
+ */
+#define VSMPC_GRAD_MODEL_A 0
+#define VSMPC_GRAD_MODEL_BJ 676
+#define VSMPC_GRAD_MODEL_BT 884
+#define VSMPC_GRAD_MODEL_C 988
+#define VSMPC_GRAD_MODEL_SIZE 1014
+/* Host buffers; returns after the results are in them.  Batches beyond 256 instances run in chunks in stream order. */
+int vsmpc_adjoint_record_batch(vsmpc_handle* h, const double* in, const double* tunables, const double* xbar,
+                               const double* fmbar, int batch, double* x, double* first_move, int* status, int* iters,
+                               double* grad_x0, double* grad_cfg, int* active, int* adj_flags, double* grad_in,
+                               double* grad_model, void* stream);
+/* Same, all pointers are DEVICE pointers (d_tunables 16-byte aligned) and the call only enqueues work on `stream`; ordering
+ * as for vsmpc_adjoint_batch_device. */
+int vsmpc_adjoint_record_batch_device(vsmpc_handle* h, const double* d_in, const double* d_tunables, const double* d_xbar,
+                                      const double* d_fmbar, int batch, double* d_x, double* d_first_move, int* d_status,
+                                      int* d_iters, double* d_grad_x0, double* d_grad_cfg, int* d_active, int* d_adj_flags,
+                                      double* d_grad_in, double* d_grad_model, void* stream);
 
 /*
  * Duals and a KKT certificate of a GIVEN primal, for every instance of a batch.  The QP is the reference-ordered dense one

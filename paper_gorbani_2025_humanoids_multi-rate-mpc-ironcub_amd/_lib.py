@@ -23,7 +23,7 @@ EXPORTS = (
     "vsmpc_sensitivity_batch_device", "vsmpc_pack_tunables", "vsmpc_solve_batch_tuned", "vsmpc_solve_batch_tuned_device",
     "vsmpc_rollout_set_tunables", "vsmpc_certify_batch", "vsmpc_certify_batch_device",
     "vsmpc_set_small_batch_kernel", "vsmpc_small_batch_kernel_for", "vsmpc_small_batch_lds_bytes",
-    "vsmpc_adjoint_batch", "vsmpc_adjoint_batch_device",
+    "vsmpc_adjoint_batch", "vsmpc_adjoint_batch_device", "vsmpc_adjoint_record_batch", "vsmpc_adjoint_record_batch_device",
     # include/vsmpc_jet.h
     "vsmpc_jet_create", "vsmpc_jet_destroy", "vsmpc_jet_nn_step", "vsmpc_jet_nn_sequence", "vsmpc_jet_ekf_update",
     "vsmpc_jet_plant_run", "vsmpc_jet_plant_run_device", "vsmpc_rollout_set_jet_plant",
@@ -88,6 +88,10 @@ def load():
     lib.vsmpc_adjoint_batch.restype = c_int
     lib.vsmpc_adjoint_batch_device.argtypes = [vp, dp, dp, dp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp, vp]
     lib.vsmpc_adjoint_batch_device.restype = c_int
+    # the same, with grad_in and grad_model in front of stream
+    for fn in (lib.vsmpc_adjoint_record_batch, lib.vsmpc_adjoint_record_batch_device):
+        fn.argtypes = [vp, dp, dp, dp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp, dp, dp, vp]
+        fn.restype = c_int
     lib.vsmpc_linearize_batch.argtypes = [vp, dp, c_int, dp, dp, dp, dp, dp]
     lib.vsmpc_linearize_batch.restype = c_int
     lib.vsmpc_assemble_dense.argtypes = [vp, dp, dp, dp, dp, dp, dp]

@@ -6,6 +6,14 @@ factor the solver holds, no Jacobian ("Adjoint").
     x, first_move, status = plan(mpc, records, x0, gains)        # records [B, n_in], x0 [B, 26], gains [B, GRAD_SIZE]
     loss(x, first_move).backward()                               # x0.grad, gains.grad
 
+On a handle created with adjoint_record=True the record itself is differentiable too -- the reference window, the previous
+throttle, the linearisation point, the posture error and the model data -- through vsmpc_adjoint_record_batch_device
+(DESIGN.md, "Adjoint of the record"):
+
+    mpc = BatchedVSMPC(cfg, max_batch=B, adjoint_record=True)
+    x, first_move, status = plan(mpc, records.requires_grad_(), x0, gains)
+    loss(x, first_move).backward()                               # records.grad (zero in the X0 columns), x0.grad, gains.grad
+
 All numerics run in libvsmpc.so (HIP); there is no CPU path.
 """
 from __future__ import annotations
@@ -45,15 +53,18 @@ class PlanFunction(torch.autograd.Function):
     in percent, as an MPCConfig holds them); packing them into the kernels' rows goes through the HOST
     (vsmpc_pack_tunables validates the values), which synchronises the stream once per forward.
     Backward: one vsmpc_adjoint_batch_device call with the incoming cotangents of x and first_move; it returns the gradients
-    of x0 and of gains.  Every other record field is non-differentiable -- the linearisation depends on them, and that
-    derivative is not computed -- so `records` must not require grad.  Instances whose status is not Solved contribute
+    of x0 and of gains.  On a handle without adjoint_record every other record field is non-differentiable -- the
+    linearisation depends on them, and that entry does not compute the derivative -- so `records` must not require grad.  On
+    a handle with it the one call is vsmpc_adjoint_record_batch_device and `records` gets the gradient of every entry; since
+    `x0` overwrites the X0 columns in the forward pass, that gradient is zero there.  Instances whose status is not Solved contribute
     zero gradient; `info` (a dict, or None) receives "flags" (L.ADJ_*) and "active" of the backward call as CUDA tensors, so
     that a caller can mask unsolved or degenerate instances.  Calls on one handle must be ordered on one stream."""
 
     @staticmethod
     def forward(ctx, mpc: BatchedVSMPC, records, x0, gains, info):
-        if records.requires_grad:
-            raise ValueError("records must not require grad: only X0 (passed as x0) and the gains are differentiable")
+        if records.requires_grad and not mpc.adjoint_record:
+            raise ValueError("records must not require grad: only X0 (passed as x0) and the gains are differentiable "
+                             "(the other record entries: a handle created with adjoint_record=True)")
         assert records.is_cuda and records.dtype == torch.float64 and records.shape[1] == mpc.n_in
         B = records.shape[0]
         assert tuple(x0.shape) == (B, L.N_STATES) and x0.dtype == torch.float64
@@ -86,12 +97,20 @@ class PlanFunction(torch.autograd.Function):
         gc = torch.empty((B, L.GRAD_SIZE), dtype=torch.float64, device=dev)
         active = torch.empty((B, mpc.n_v), dtype=torch.int32, device=dev)
         flags = torch.empty(B, dtype=torch.int32, device=dev)
-        mpc.solve_adjoint_device(d_in, ctx.d_tun, xbar, fmbar, None, None, status, None, g0, gc, active, flags)
+        gin = None
+        if ctx.needs_input_grad[1]:
+            gin = torch.empty((B, mpc.n_in), dtype=torch.float64, device=dev)
+            mpc.solve_adjoint_record_device(d_in, ctx.d_tun, xbar, fmbar, None, None, status, None, g0, gc, active, flags, gin,
+                                            None)
+            gin[:, L.IN_X0:L.IN_X0 + L.N_STATES] = 0.0       # the forward pass replaced these columns by x0
+        else:
+            mpc.solve_adjoint_device(d_in, ctx.d_tun, xbar, fmbar, None, None, status, None, g0, gc, active, flags)
         if ctx.info is not None:
             ctx.info["flags"], ctx.info["active"] = flags, active
-        return None, None, (g0 if ctx.needs_input_grad[2] else None), (gc if ctx.needs_input_grad[3] else None), None
+        return None, gin, (g0 if ctx.needs_input_grad[2] else None), (gc if ctx.needs_input_grad[3] else None), None
 
 
 def plan(mpc: BatchedVSMPC, records, x0, gains=None, info: dict | None = None):
-    """(x, first_move, status) of the batch, differentiable with respect to `x0` and `gains` (PlanFunction)"""
+    """(x, first_move, status) of the batch, differentiable with respect to `x0` and `gains`, and on a handle created with
+    adjoint_record=True with respect to `records` (PlanFunction)"""
     return PlanFunction.apply(mpc, records, x0, gains, info)

@@ -121,7 +121,7 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     *out = nullptr;
     const unsigned kernel_flags = VSMPC_CREATE_RUNTIME_FALLBACK | VSMPC_CREATE_RUNTIME_ONLY;
     if ((flags & ~(kernel_flags | VSMPC_CREATE_SENSITIVITY | VSMPC_CREATE_TUNABLES | VSMPC_CREATE_CERTIFY |
-                   VSMPC_CREATE_ADJOINT)) != 0u)
+                   VSMPC_CREATE_ADJOINT | VSMPC_CREATE_ADJOINT_RECORD)) != 0u)
         return invalid_arg();
     if (!config_valid(*cfg)) return invalid_arg();
     const int variant = (flags & VSMPC_CREATE_RUNTIME_ONLY)
@@ -134,9 +134,12 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     const bool sens = (flags & VSMPC_CREATE_SENSITIVITY) != 0u;
     const RtDims rts = runtime_dims(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon, true);
     if (sens && runtime_lds_bytes(rts) > RT_MAX_LDS) return unsupported();     // (not for a valid config)
-    const bool adjoint = (flags & VSMPC_CREATE_ADJOINT) != 0u;
+    const bool adjoint_record = (flags & VSMPC_CREATE_ADJOINT_RECORD) != 0u;
+    const bool adjoint = (flags & VSMPC_CREATE_ADJOINT) != 0u || adjoint_record;
     const RtDims rta = runtime_dims(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon, false, true);
     if (adjoint && runtime_tuned_lds_bytes(rta) > RT_MAX_LDS) return unsupported();   // (not for a valid config)
+    const RtDims rtr = runtime_dims(cfg->n_iter, cfg->n_iter_small, cfg->control_horizon, false, true, true);
+    if (adjoint_record && runtime_tuned_lds_bytes(rtr) > RT_MAX_LDS) return unsupported();   // (not for a valid config)
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return invalid_arg();
@@ -155,6 +158,8 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     h->certify = (flags & VSMPC_CREATE_CERTIFY) != 0u ? 1 : 0;
     h->adjoint = adjoint ? 1 : 0;
     h->rta = rta;
+    h->adjoint_record = adjoint_record ? 1 : 0;
+    h->rtr = rtr;
     h->form = runtime ? 0 : initial_kernel_form();
     for (int i = 0; i < VSMPC_N_JOINTS; ++i) h->kin.sel[i] = 3 + i;   // the shipped robot: joints 3..10
     h->kin.constant_lambda = 0;
@@ -207,6 +212,8 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     need(h->d_agcfg, CA * VSMPC_GRAD_SIZE, adjoint);
     need(h->d_aact, CA * rta.nv, adjoint);
     need(h->d_aflags, CA, adjoint);
+    need(h->d_agin, CA * h->n_in, adjoint_record);
+    need(h->d_agmodel, CA * VSMPC_GRAD_MODEL_SIZE, adjoint_record);
     for (int i = 0; i < PIPE_STREAMS && e == hipSuccess; ++i) {
         e = hipStreamCreateWithFlags(h->pipe[i].put(), hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(h->pipe_done[i].put(), hipEventDisableTiming);

@@ -237,17 +237,17 @@ int vsmpc_adjoint_batch_device(vsmpc_handle* h, const double* d_in, const double
     return VSMPC_OK;
 }
 
-int vsmpc_adjoint_batch(vsmpc_handle* h, const double* in, const double* tunables, const double* xbar, const double* fmbar,
-                        int batch, double* x, double* first_move, int* status, int* iters, double* grad_x0, double* grad_cfg,
-                        int* active, int* adj_flags, void* stream) {
-    if (h == nullptr || in == nullptr || xbar == nullptr || status == nullptr || batch < 0) return invalid_arg();
-    if (!h->adjoint) return unsupported(ADJOINT_NEEDS_FLAG);
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
+// the host-pointer entries of the adjoint and of the record adjoint (`record`: adjoint_record_kernel_rt, which also writes
+// grad_in and grad_model): chunks of ADJ_CHUNK instances in stream order, the staging of one chunk is read back before the
+// next overwrites it
+static int adjoint_batch_host(vsmpc_handle* h, bool record, const double* in, const double* tunables, const double* xbar,
+                              const double* fmbar, int batch, double* x, double* first_move, int* status, int* iters,
+                              double* grad_x0, double* grad_cfg, int* active, int* adj_flags, double* grad_in,
+                              double* grad_model, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     ON_DEVICE(h->device);
-    const size_t NV = size_t(h->rta.nv), FM = VSMPC_FM_SIZE, T = VSMPC_TUNE_SIZE, G = VSMPC_GRAD_SIZE;
-    // chunks of ADJ_CHUNK instances in stream order: the staging of one chunk is read back before the next overwrites it
+    const RtDims& d = record ? h->rtr : h->rta;
+    const size_t NV = size_t(d.nv), FM = VSMPC_FM_SIZE, T = VSMPC_TUNE_SIZE, G = VSMPC_GRAD_SIZE, GM = VSMPC_GRAD_MODEL_SIZE;
     hipError_t err = hipSuccess;
     auto ok = [&](hipError_t e) { if (e != hipSuccess && err == hipSuccess) err = e; return err == hipSuccess; };
     for (int first = 0; first < batch && err == hipSuccess; first += ADJ_CHUNK) {
@@ -257,23 +257,81 @@ int vsmpc_adjoint_batch(vsmpc_handle* h, const double* in, const double* tunable
         if (!ok(hipMemcpyAsync(h->d_axbar, xbar + o * h->n_var, N * h->n_var * sizeof(double), hipMemcpyHostToDevice, s))) break;
         if (fmbar && !ok(hipMemcpyAsync(h->d_afmbar, fmbar + o * FM, N * FM * sizeof(double), hipMemcpyHostToDevice, s))) break;
         if (tunables && !ok(hipMemcpyAsync(h->d_atun, tunables + o * T, N * T * sizeof(double), hipMemcpyHostToDevice, s))) break;
-        if (!ok(launch_adjoint_runtime(h->rta, h->dev, h->d_in + o * h->n_in, tunables ? h->d_atun.get() : nullptr, n,
-                                       adjoint_workspace(h) + o * size_t(h->rta.ws_doubles), x ? h->d_x + o * h->n_var : nullptr,
-                                       first_move ? h->d_fm + o * FM : nullptr, h->d_status + o,
-                                       iters ? h->d_iters + o : nullptr, h->d_axbar, fmbar ? h->d_afmbar.get() : nullptr,
-                                       grad_x0 ? h->d_agx0.get() : nullptr, grad_cfg ? h->d_agcfg.get() : nullptr,
-                                       active ? h->d_aact.get() : nullptr, adj_flags ? h->d_aflags.get() : nullptr, s)))
+        const double* d_in = h->d_in + o * h->n_in;
+        const double* d_tun = tunables ? h->d_atun.get() : nullptr;
+        double* d_ws = adjoint_workspace(h) + o * size_t(d.ws_doubles);
+        double* d_x = x ? h->d_x + o * h->n_var : nullptr;
+        double* d_fm = first_move ? h->d_fm + o * FM : nullptr;
+        int* d_it = iters ? h->d_iters + o : nullptr;
+        const double* d_fmbar = fmbar ? h->d_afmbar.get() : nullptr;
+        double* d_gx0 = grad_x0 ? h->d_agx0.get() : nullptr;
+        double* d_gcfg = grad_cfg ? h->d_agcfg.get() : nullptr;
+        int* d_act = active ? h->d_aact.get() : nullptr;
+        int* d_fl = adj_flags ? h->d_aflags.get() : nullptr;
+        if (!ok(record ? launch_adjoint_record_runtime(d, h->dev, d_in, d_tun, n, d_ws, d_x, d_fm, h->d_status + o, d_it, h->d_axbar,
+                                                       d_fmbar, d_gx0, d_gcfg, d_act, d_fl, grad_in ? h->d_agin.get() : nullptr,
+                                                       grad_model ? h->d_agmodel.get() : nullptr, s)
+                       : launch_adjoint_runtime(d, h->dev, d_in, d_tun, n, d_ws, d_x, d_fm, h->d_status + o, d_it, h->d_axbar,
+                                                d_fmbar, d_gx0, d_gcfg, d_act, d_fl, s)))
             break;
         ok(download_results(h, o, N, x, first_move, status, iters, s));
         if (grad_x0) ok(hipMemcpyAsync(grad_x0 + o * NX, h->d_agx0, N * NX * sizeof(double), hipMemcpyDeviceToHost, s));
         if (grad_cfg) ok(hipMemcpyAsync(grad_cfg + o * G, h->d_agcfg, N * G * sizeof(double), hipMemcpyDeviceToHost, s));
         if (active) ok(hipMemcpyAsync(active + o * NV, h->d_aact, N * NV * sizeof(int), hipMemcpyDeviceToHost, s));
         if (adj_flags) ok(hipMemcpyAsync(adj_flags + o, h->d_aflags, N * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (record && grad_in)
+            ok(hipMemcpyAsync(grad_in + o * h->n_in, h->d_agin, N * h->n_in * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (record && grad_model)
+            ok(hipMemcpyAsync(grad_model + o * GM, h->d_agmodel, N * GM * sizeof(double), hipMemcpyDeviceToHost, s));
     }
     const hipError_t e = hipStreamSynchronize(s);   // nothing returns while copies into the caller's buffers are queued
     if (err == hipSuccess) err = e;
-    if (err != hipSuccess) return hip_fail(err, "vsmpc_adjoint_batch");
+    if (err != hipSuccess) return hip_fail(err, record ? "vsmpc_adjoint_record_batch" : "vsmpc_adjoint_batch");
     return VSMPC_OK;
+}
+
+int vsmpc_adjoint_batch(vsmpc_handle* h, const double* in, const double* tunables, const double* xbar, const double* fmbar,
+                        int batch, double* x, double* first_move, int* status, int* iters, double* grad_x0, double* grad_cfg,
+                        int* active, int* adj_flags, void* stream) {
+    if (h == nullptr || in == nullptr || xbar == nullptr || status == nullptr || batch < 0) return invalid_arg();
+    if (!h->adjoint) return unsupported(ADJOINT_NEEDS_FLAG);
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    if (batch == 0) return VSMPC_OK;
+    return adjoint_batch_host(h, false, in, tunables, xbar, fmbar, batch, x, first_move, status, iters, grad_x0, grad_cfg, active,
+                              adj_flags, nullptr, nullptr, stream);
+}
+
+// Adjoint of the record (include/vsmpc.h): adjoint_record_kernel_rt[_tuned] on the adjoint entry's workspace and staging,
+// with the staging VSMPC_CREATE_ADJOINT_RECORD allocated for the two further outputs
+static const char* const ADJOINT_RECORD_NEEDS_FLAG =
+    "vsmpc_adjoint_record_batch needs a handle created with VSMPC_CREATE_ADJOINT_RECORD (vsmpc_create_ex)";
+
+int vsmpc_adjoint_record_batch_device(vsmpc_handle* h, const double* d_in, const double* d_tunables, const double* d_xbar,
+                                      const double* d_fmbar, int batch, double* d_x, double* d_first_move, int* d_status,
+                                      int* d_iters, double* d_grad_x0, double* d_grad_cfg, int* d_active, int* d_adj_flags,
+                                      double* d_grad_in, double* d_grad_model, void* stream) {
+    if (h == nullptr || d_in == nullptr || d_xbar == nullptr || d_status == nullptr || batch < 0) return invalid_arg();
+    if ((reinterpret_cast<size_t>(d_tunables) & 15) != 0) return invalid_arg();   // the kernel loads 16 bytes per lane
+    if (!h->adjoint_record) return unsupported(ADJOINT_RECORD_NEEDS_FLAG);
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    if (batch == 0) return VSMPC_OK;
+    ON_DEVICE(h->device);
+    HIP_TRY(launch_adjoint_record_runtime(h->rtr, h->dev, d_in, d_tunables, batch, adjoint_workspace(h), d_x, d_first_move,
+                                          d_status, d_iters, d_xbar, d_fmbar, d_grad_x0, d_grad_cfg, d_active, d_adj_flags,
+                                          d_grad_in, d_grad_model, static_cast<hipStream_t>(stream)));
+    return VSMPC_OK;
+}
+
+int vsmpc_adjoint_record_batch(vsmpc_handle* h, const double* in, const double* tunables, const double* xbar,
+                               const double* fmbar, int batch, double* x, double* first_move, int* status, int* iters,
+                               double* grad_x0, double* grad_cfg, int* active, int* adj_flags, double* grad_in,
+                               double* grad_model, void* stream) {
+    if (h == nullptr || in == nullptr || xbar == nullptr || status == nullptr || batch < 0) return invalid_arg();
+    if (!h->adjoint_record) return unsupported(ADJOINT_RECORD_NEEDS_FLAG);
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    if (batch == 0) return VSMPC_OK;
+    return adjoint_batch_host(h, true, in, tunables, xbar, fmbar, batch, x, first_move, status, iters, grad_x0, grad_cfg, active,
+                              adj_flags, grad_in, grad_model, stream);
 }
 
 // Duals and KKT certificate of given primals: certify_kernel restates the oracle's solve_exact (the duals, OSQP's sign:

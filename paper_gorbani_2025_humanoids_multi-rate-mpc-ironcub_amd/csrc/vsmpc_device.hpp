@@ -130,6 +130,10 @@ struct Jet {
     static VS_HD double dg_dT(double T, double Td) { return c7 + c9 * Td + 2 * c10 * T; }
     static VS_HD double dg_dTd(double T, double Td) { return c8 + c9 * T + 2 * c11 * Td; }
     static VS_HD double v(double u) { return u + c12 * u * u; }
+    // f and g are quadratics: their second derivatives are constants (the record adjoint, vsmpc_rt_adjoint_record.hpp)
+    static constexpr double d2f_dT2 = 2 * c4, d2f_dTdTd = c3, d2f_dTd2 = 2 * c5;
+    static constexpr double d2g_dT2 = 2 * c10, d2g_dTdTd = c9, d2g_dTd2 = 2 * c11;
+    static VS_HD double dv_du(double u) { return 1.0 + 2.0 * c12 * u; }   // of v, in the standardised throttle
     // reciprocals as constants: an FP64 division costs ~40 instructions on the device
     static constexpr double isgT = 1.0 / sgT, isgU = 1.0 / sgU;
     static VS_HD double stdT(double T) { return (T - muT) * isgT; }

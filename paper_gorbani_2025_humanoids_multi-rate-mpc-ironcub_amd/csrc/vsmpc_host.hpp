@@ -105,6 +105,11 @@ struct vsmpc_handle {
     vsmpc::RtDims rta;
     vsmpc::DevBuf<double> d_aws, d_axbar, d_afmbar, d_atun, d_agx0, d_agcfg;
     vsmpc::DevBuf<int> d_aact, d_aflags;
+    // VSMPC_CREATE_ADJOINT_RECORD (implies `adjoint`): sizes of adjoint_record_kernel_rt (rta's workspace serves) and the
+    // staging of its two outputs, ADJ_CHUNK instances at a time
+    int adjoint_record;
+    vsmpc::RtDims rtr;
+    vsmpc::DevBuf<double> d_agin, d_agmodel;
     int form;       // condensing form of the solve kernel (vsmpc_set_kernel_form)
     int small_mode; // which kernel serves small batches (vsmpc_set_small_batch_kernel): 0 auto, 1 never, 2 always
     int cu_count;   // compute units of `device` (read once, at create): auto takes the small-batch kind up to this batch
@@ -180,7 +185,7 @@ constexpr int PIPE_STREAMS = VS_PIPE_STREAMS;
 static_assert(PIPE_STREAMS >= 1 && PIPE_STREAMS <= 4, "vsmpc_handle::pipe holds four streams");
 constexpr int SENS_CHUNK = 256;   // instances per chunk of vsmpc_sensitivity_batch (dx_dx0 staging: 82 MB at (40, 2, 40))
 constexpr int SENS_NPAR = VSMPC_N_STATES;
-constexpr int ADJ_CHUNK = 256;    // instances per chunk of vsmpc_adjoint_batch
+constexpr int ADJ_CHUNK = 256;    // instances per chunk of vsmpc_adjoint_batch and vsmpc_adjoint_record_batch
 
 void fill_dt(const vsmpc_config& c, double* dt);   // vsmpc_capi.hip: the dt schedule, MAX_STAGES doubles
 bool tree_valid(const vsmpc_tree& tree);            // vsmpc_capi_debug.hip: parents precede children, indices in range

@@ -100,8 +100,10 @@ struct RtDims {
 };
 constexpr size_t RT_MAX_LDS = 160 * 1024;
 // sensitivity: the sizes of sens_kernel_rt (NP = NZ + 1 + 26: the parameter columns of d/dX0); adjoint: those of
-// adjoint_kernel_rt[_tuned] (the solve kernel's, with room in LDS for a_X and the costates at horizons with few unknowns)
-RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon, bool sensitivity = false, bool adjoint = false);
+// adjoint_kernel_rt[_tuned] (the solve kernel's, with room in LDS for a_X and the costates at horizons with few unknowns);
+// adjoint_record (with adjoint): those of adjoint_record_kernel_rt[_tuned] (room for dL/d(A | Bj | Bt | c) behind them)
+RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon, bool sensitivity = false, bool adjoint = false,
+                    bool adjoint_record = false);
 size_t runtime_lds_bytes(const RtDims& d);
 // the same with the staged row of the per-instance-tunables kinds behind it (solve_kernel_rt_tuned, adjoint_kernel_rt_tuned)
 size_t runtime_tuned_lds_bytes(const RtDims& d);
@@ -126,6 +128,13 @@ hipError_t launch_adjoint_runtime(const RtDims& d, const DevCfg& cfg, const doub
                                   double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters, const double* d_xbar,
                                   const double* d_fmbar, double* d_gx0, double* d_gcfg, int* d_active, int* d_flags,
                                   hipStream_t stream);
+// adjoint_record_kernel_rt[_tuned] (vsmpc_adjoint_record_batch): launch_adjoint_runtime's arguments and outputs plus dL/d record
+// [batch][n_in] and dL/d(A | Bj | Bt | c) [batch][VSMPC_GRAD_MODEL_SIZE] (each may be nullptr); d from
+// runtime_dims(.., false, true, true)
+hipError_t launch_adjoint_record_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
+                                         double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters,
+                                         const double* d_xbar, const double* d_fmbar, double* d_gx0, double* d_gcfg,
+                                         int* d_active, int* d_flags, double* d_gin, double* d_gmodel, hipStream_t stream);
 // linearize_kernel_rt (vsmpc_linearize_batch, on every handle): p0_linearize alone
 hipError_t launch_linearize_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,
                                     double* Bt, double* c, hipStream_t stream);

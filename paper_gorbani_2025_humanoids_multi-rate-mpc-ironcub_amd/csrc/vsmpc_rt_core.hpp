@@ -41,7 +41,7 @@ constexpr int RT_BLOCK = 256;
 constexpr int RT_CPT = 2;    // columns per thread: NP <= 8 * 40 + 4 * 39 + 1 = 477 (+ 26 parameter columns: 503) < 512
 constexpr int RT_NPAR = NX;  // parameter columns of sens_kernel_rt: one per entry of X0
 constexpr int RT_NWAVES = RT_BLOCK / 64;
-enum RtMode { RT_SOLVE, RT_SENS, RT_ADJOINT };   // the instantiations of rt_solve
+enum RtMode { RT_SOLVE, RT_SENS, RT_ADJOINT, RT_ADJOINT_REC };   // the instantiations of rt_solve
 enum { F_STATUS = 0, F_ITERS, F_NF, F_BEST, F_PATIENCE };   // LDS flag slots
 
 VS_DEV size_t tri(int i) { return size_t(i) * size_t(i + 1) / 2; }
@@ -54,7 +54,8 @@ VS_DEV void tri_advance(int& i, int& j, int step) {
 
 // LDS carve-up (doubles), stated once as a walk over P: over double* in the kernels (rt_smem), and over size_t from 0 on the
 // host, where runtime_dims takes the size of the fixed part -- everything in front of `big` -- from it.  `big` is shared by
-// whoever needs it at the time; its sizes stand beside their users (rt_big_condense, rt_big_box_qp, RT_BIG_SENS, rt_big_adjoint).
+// whoever needs it at the time; its sizes stand beside their users (rt_big_condense, rt_big_box_qp, RT_BIG_SENS, rt_big_adjoint,
+// rt_big_adjoint_record).
 template <class P>
 struct RtCarve {
     P in, lin, vprev, dt, sq, x, z, col, red, vec0, vec1, vec2, big;

@@ -8,6 +8,8 @@
 //   vsmpc_rt_core.hpp     constants, the LDS carve-up, RtCtx, the substitution helpers, P0 .. P6, rt_write_solution
 //   vsmpc_rt_sens.hpp     the four extra phases of sens_kernel_rt (vsmpc_sensitivity_batch): rt_solve<RT_SENS>
 //   vsmpc_rt_adjoint.hpp  the five extra phases of adjoint_kernel_rt[_tuned] (vsmpc_adjoint_batch): rt_solve<RT_ADJOINT>
+//   vsmpc_rt_adjoint_record.hpp  the two phases adjoint_record_kernel_rt[_tuned] (vsmpc_adjoint_record_batch) add to those:
+//                         rt_solve<RT_ADJOINT_REC>
 //   this file             RtTunCfg and its staging, rt_solve, the kernels, runtime_dims and the launchers
 //
 // The phases that read the configuration take its type as a template parameter: DevCfg, the kernel argument
@@ -19,16 +21,18 @@
 #include "vsmpc_rt_core.hpp"
 #include "vsmpc_rt_sens.hpp"
 #include "vsmpc_rt_adjoint.hpp"
+#include "vsmpc_rt_adjoint_record.hpp"
 
 namespace vsmpc {
 
 namespace {
 
 // The solve of one instance: the phases in order.  cfg is a DevCfg or an RtTunCfg; `sens` is looked at with RT_SENS only,
-// `adj` with RT_ADJOINT only.
+// `adj` with RT_ADJOINT and RT_ADJOINT_REC only, `rec` with RT_ADJOINT_REC only.
 template <RtMode MODE, class Cfg>
 VS_DEV void rt_solve(const Cfg& cfg, const RtDims& d, const double* in, double* ws, double* xout, double* fmout,
-                     int* status_out, int* iters_out, const RtSensOut& sens = {}, const RtAdjIO& adj = {}) {
+                     int* status_out, int* iters_out, const RtSensOut& sens = {}, const RtAdjIO& adj = {},
+                     const RtAdjRecOut& rec = {}) {
     constexpr bool SENS = MODE == RT_SENS;
     const int inst = blockIdx.x;
     const RtCtx c{d, ws + size_t(inst) * size_t(d.ws_doubles), int(threadIdx.x), inst};
@@ -55,7 +59,7 @@ VS_DEV void rt_solve(const Cfg& cfg, const RtDims& d, const double* in, double* 
     }
     rt_write_solution(c, bad, xout, fmout, status_out, iters_out);
     if constexpr (SENS) rt_sens_write(c, box, factored, sens_ok, sens);
-    if constexpr (MODE == RT_ADJOINT) {
+    if constexpr (MODE == RT_ADJOINT || MODE == RT_ADJOINT_REC) {
         const bool adj_ok = !bad && s.flags[F_STATUS] == VSMPC_STATUS_SOLVED;   // (the same value in every thread)
         bool nonfinite = false;
         if (adj_ok) {
@@ -66,6 +70,10 @@ VS_DEV void rt_solve(const Cfg& cfg, const RtDims& d, const double* in, double* 
             rt_adj_costates(c, cfg, a);
         }
         rt_adj_reduce_write(c, cfg, box, factored, adj_ok, nonfinite, adj);
+        if constexpr (MODE == RT_ADJOINT_REC) {
+            if (adj_ok && !nonfinite) rt_adj_model(c, cfg);
+            rt_adj_record(c, cfg, box, adj_ok, nonfinite, rec);
+        }
     }
 }
 
@@ -157,6 +165,35 @@ __global__ __launch_bounds__(RT_BLOCK) void adjoint_kernel_rt_tuned(DevCfg hcfg,
                          RtAdjIO{xbar, fmbar, gx0, gcfg, active_out, flags_out});
 }
 
+// adjoint_kernel_rt + the record phases: dL/d record [batch][n_in] and dL/d(A | Bj | Bt | c) [batch][VSMPC_GRAD_MODEL_SIZE] out
+// as well (each may be null)
+__global__ __launch_bounds__(RT_BLOCK) void adjoint_record_kernel_rt(DevCfg cfg, RtDims d, const double* __restrict__ in,
+                                                                     double* __restrict__ ws, double* __restrict__ xout,
+                                                                     double* __restrict__ fmout, int* __restrict__ status_out,
+                                                                     int* __restrict__ iters_out, const double* __restrict__ xbar,
+                                                                     const double* __restrict__ fmbar, double* __restrict__ gx0,
+                                                                     double* __restrict__ gcfg, int* __restrict__ active_out,
+                                                                     int* __restrict__ flags_out, double* __restrict__ gin,
+                                                                     double* __restrict__ gmodel) {
+    rt_solve<RT_ADJOINT_REC>(cfg, d, in, ws, xout, fmout, status_out, iters_out, RtSensOut{},
+                             RtAdjIO{xbar, fmbar, gx0, gcfg, active_out, flags_out}, RtAdjRecOut{gin, gmodel});
+}
+// the same with per-instance tunables, staged as in solve_kernel_rt_tuned
+__global__ __launch_bounds__(RT_BLOCK) void adjoint_record_kernel_rt_tuned(DevCfg hcfg, RtDims d, const double* __restrict__ in,
+                                                                           double* __restrict__ ws, double* __restrict__ xout,
+                                                                           double* __restrict__ fmout, int* __restrict__ status_out,
+                                                                           int* __restrict__ iters_out,
+                                                                           const double* __restrict__ xbar,
+                                                                           const double* __restrict__ fmbar, double* __restrict__ gx0,
+                                                                           double* __restrict__ gcfg, int* __restrict__ active_out,
+                                                                           int* __restrict__ flags_out, double* __restrict__ gin,
+                                                                           double* __restrict__ gmodel,
+                                                                           const double* __restrict__ tun) {
+    const RtTunCfg& tcfg = rt_stage_tunables(hcfg, d, tun);
+    rt_solve<RT_ADJOINT_REC>(tcfg, d, in, ws, xout, fmout, status_out, iters_out, RtSensOut{},
+                             RtAdjIO{xbar, fmbar, gx0, gcfg, active_out, flags_out}, RtAdjRecOut{gin, gmodel});
+}
+
 // linearize_kernel_rt's LDS (doubles): the record, p0_linearize's block, the previous throttles
 struct LinLdsOff { int lin, vprev, size; };
 VS_HD LinLdsOff lin_lds_offsets(int n_in) {
@@ -187,7 +224,7 @@ __global__ __launch_bounds__(RT_BLOCK) void linearize_kernel_rt(DevCfg cfg, int 
     for (int i = tid; i < NX; i += RT_BLOCK) c[size_t(b) * NX + i] = sC[i];
 }
 
-RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon, bool sensitivity, bool adjoint) {
+RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon, bool sensitivity, bool adjoint, bool adjoint_record) {
     RtDims d{};
     d.n = n_iter;
     d.ns = n_iter_small;
@@ -205,6 +242,7 @@ RtDims runtime_dims(int n_iter, int n_iter_small, int control_horizon, bool sens
     int big = rt_big_condense(d) > rt_big_box_qp(d) ? rt_big_condense(d) : rt_big_box_qp(d);   // s.big holds one at a time
     if (sensitivity && RT_BIG_SENS > big) big = RT_BIG_SENS;
     if (adjoint && rt_big_adjoint(d) > big) big = rt_big_adjoint(d);
+    if (adjoint_record && rt_big_adjoint_record(d) > big) big = rt_big_adjoint_record(d);
     d.lds_doubles = int(rt_carve(d, size_t(0)).big) + big;
     return d;
 }
@@ -257,6 +295,21 @@ hipError_t launch_adjoint_runtime(const RtDims& d, const DevCfg& cfg, const doub
                                                   d_status, d_iters, d_xbar, d_fmbar, d_gx0, d_gcfg, d_active, d_flags, d_tun);
     return rt_launch<adjoint_kernel_rt>(runtime_lds_bytes(d), batch, stream, cfg, d, d_in, d_ws, d_x, d_fm, d_status, d_iters,
                                         d_xbar, d_fmbar, d_gx0, d_gcfg, d_active, d_flags);
+}
+
+hipError_t launch_adjoint_record_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
+                                         double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters,
+                                         const double* d_xbar, const double* d_fmbar, double* d_gx0, double* d_gcfg,
+                                         int* d_active, int* d_flags, double* d_gin, double* d_gmodel, hipStream_t stream) {
+    static_assert(2 * NX <= RT_BLOCK, "s.red holds nu_k and nu_{k-1}");
+    // runtime_dims(.., false, true, true): s.big holds G behind a_X and the costates
+    if (d.np != d.nz + 1 || d.lds_doubles < int(rt_carve(d, size_t(0)).big) + rt_big_adjoint_record(d)) return hipErrorInvalidValue;
+    if (d_tun != nullptr)
+        return rt_launch<adjoint_record_kernel_rt_tuned>(runtime_tuned_lds_bytes(d), batch, stream, cfg, d, d_in, d_ws, d_x, d_fm,
+                                                         d_status, d_iters, d_xbar, d_fmbar, d_gx0, d_gcfg, d_active, d_flags,
+                                                         d_gin, d_gmodel, d_tun);
+    return rt_launch<adjoint_record_kernel_rt>(runtime_lds_bytes(d), batch, stream, cfg, d, d_in, d_ws, d_x, d_fm, d_status,
+                                               d_iters, d_xbar, d_fmbar, d_gx0, d_gcfg, d_active, d_flags, d_gin, d_gmodel);
 }
 
 hipError_t launch_linearize_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,

@@ -97,6 +97,24 @@ GRAD_FIELDS = (("w_com_pos", 0, 3), ("w_com_pos_err", 3, 3), ("w_lin_mom", 6, 3)
 ADJ_DEGENERATE = 0x1
 ADJ_UNSOLVED = 0x2
 ADJOINT_KERNEL_NAMES = ("adjoint_kernel_rt", "adjoint_kernel_rt_tuned")
+ADJOINT_RECORD_KERNEL_NAMES = ("adjoint_record_kernel_rt", "adjoint_record_kernel_rt_tuned")
+
+# adjoint of the record (vsmpc_adjoint_record_batch, VSMPC_GRAD_MODEL_* in include/vsmpc.h): grad_model is dL/d(A | Bj | Bt | c),
+# row-major blocks at these offsets; grad_in follows the record, field by field
+CREATE_ADJOINT_RECORD = 0x80
+GRAD_MODEL_A, GRAD_MODEL_BJ, GRAD_MODEL_BT, GRAD_MODEL_C = 0, 676, 884, 988
+GRAD_MODEL_SIZE = 1014
+# (field, offset, length) of the fixed part of the record; the window follows (record_fields)
+RECORD_FIELDS = (("X0", IN_X0, 26), ("MASS", IN_MASS, 1), ("WRB", IN_WRB, 9), ("OMEGA", IN_OMEGA, 3), ("ALPHA", IN_ALPHA, 1),
+                 ("GRAV", IN_GRAV, 3), ("AMOM", IN_AMOM, 24), ("LLIN", IN_LLIN, 24), ("LANG", IN_LANG, 24),
+                 ("INERTIA", IN_INERTIA, 9), ("RPY", IN_RPY, 3), ("PREF", IN_PREF, 3), ("RPYINIT", IN_RPYINIT, 3),
+                 ("T0", IN_T0, 4), ("TD0", IN_TD0, 4), ("UPREV", IN_UPREV, 4), ("TDES", IN_TDES, 4), ("TDDES", IN_TDDES, 4),
+                 ("QERR", IN_QERR, 8), ("HOLD", IN_HOLD, 1))
+
+
+def record_fields(cfg) -> tuple:
+    """(field, offset, length) of every field of the record of `cfg`'s horizon, the reference window last"""
+    return RECORD_FIELDS + (("XREF", IN_XREF, 12 * cfg.n_ref_cols),)
 
 # closed-loop rollout: plant state / parameter layouts (VSMPC_PS_* / VSMPC_PP_* in include/vsmpc.h)
 PS_P, PS_HLIN, PS_RPY, PS_HANG, PS_T, PS_TD, PS_Q, PS_U, PS_TDES, PS_TDDES = 0, 3, 6, 9, 12, 16, 20, 28, 32, 36

@@ -62,26 +62,29 @@ class BatchedVSMPC:
     """`max_batch` independent MPC instances on one GPU (one workgroup per instance)."""
 
     def __init__(self, cfg: L.MPCConfig | None = None, device: int = 0, max_batch: int = 256, runtime: str = "never",
-                 sensitivity: bool = False, tunables: bool = False, certify: bool = False, adjoint: bool = False):
+                 sensitivity: bool = False, tunables: bool = False, certify: bool = False, adjoint: bool = False,
+                 adjoint_record: bool = False):
         """runtime: "never" -- the tuned kernel of a tabled horizon, other horizons are refused (vsmpc_create);
         "fallback" -- the runtime-sized kernel where the table has no instantiation; "always" -- the runtime-sized kernel
         for every horizon (vsmpc_create_ex, include/vsmpc.h).  sensitivity: also allocate what solve_sensitivity needs
         (VSMPC_CREATE_SENSITIVITY).  tunables: also allocate the staging of solve(records, configs=...), one row of
         weights and throttle box per instance (VSMPC_CREATE_TUNABLES).  certify: also allocate the staging of
-        certify(records, x) (VSMPC_CREATE_CERTIFY).  adjoint: also allocate what solve_adjoint needs (VSMPC_CREATE_ADJOINT)."""
+        certify(records, x) (VSMPC_CREATE_CERTIFY).  adjoint: also allocate what solve_adjoint needs (VSMPC_CREATE_ADJOINT).
+        adjoint_record: also allocate what solve_adjoint_record needs (VSMPC_CREATE_ADJOINT_RECORD; it includes `adjoint`)."""
         if runtime not in L.RUNTIME_MODES:
             raise ValueError(f"runtime must be one of {sorted(L.RUNTIME_MODES)}, not {runtime!r}")
         self.cfg = cfg or L.paper_config()
         self.lib = _lib.load()
         self._ccfg = self.cfg.to_c()
         self._h = ctypes.c_void_p()
-        if runtime == "never" and not sensitivity and not tunables and not certify and not adjoint:
+        self.adjoint_record = bool(adjoint_record)
+        if runtime == "never" and not sensitivity and not tunables and not certify and not adjoint and not adjoint_record:
             _lib.check(self.lib.vsmpc_create(ctypes.byref(self._ccfg), device, max_batch, ctypes.byref(self._h)),
                        "vsmpc_create")
         else:
             flags = (L.RUNTIME_MODES[runtime] | (L.CREATE_SENSITIVITY if sensitivity else 0)
                      | (L.CREATE_TUNABLES if tunables else 0) | (L.CREATE_CERTIFY if certify else 0)
-                     | (L.CREATE_ADJOINT if adjoint else 0))
+                     | (L.CREATE_ADJOINT if adjoint else 0) | (L.CREATE_ADJOINT_RECORD if adjoint_record else 0))
             _lib.check(self.lib.vsmpc_create_ex(ctypes.byref(self._ccfg), device, max_batch, flags, ctypes.byref(self._h)),
                        "vsmpc_create_ex")
         self.device = device
@@ -277,6 +280,16 @@ class BatchedVSMPC:
         (unsolved instances have zero gradients; a degenerate one has the one-sided gradient of its final active set).
         With `configs` (one MPCConfig per instance, through pack_tunables) or `tunables` (their packed rows) instance i is
         solved and differentiated under its own weights and throttle box."""
+        return self._solve_adjoint(False, records, xbar, fmbar, configs, tunables)
+
+    def solve_adjoint_record(self, records: np.ndarray, xbar: np.ndarray, fmbar=None, configs=None, tunables=None) -> dict:
+        """vsmpc_adjoint_record_batch (needs adjoint_record=True at construction): everything solve_adjoint returns, bit
+        for bit, and grad_in [B, n_in] = dL/d(record entry) in the layout of the record (L.RECORD_FIELDS;
+        grad_in[:, :26] is grad_x0, the hold flag and the entries nothing reads get 0) and grad_model
+        [B, L.GRAD_MODEL_SIZE] = dL/d(A | Bj | Bt | c) in the layout of linearize() (L.GRAD_MODEL_*)."""
+        return self._solve_adjoint(True, records, xbar, fmbar, configs, tunables)
+
+    def _solve_adjoint(self, record: bool, records, xbar, fmbar, configs, tunables) -> dict:
         records = np.ascontiguousarray(records, dtype=np.float64)
         if records.ndim != 2 or records.shape[1] != self.n_in:
             raise ValueError(f"records must be [batch, {self.n_in}]")
@@ -299,10 +312,15 @@ class BatchedVSMPC:
                "status": np.empty(B, dtype=np.int32), "iters": np.empty(B, dtype=np.int32),
                "grad_x0": np.empty((B, L.N_STATES)), "grad_cfg": np.empty((B, L.GRAD_SIZE)),
                "active": np.empty((B, self.n_v), dtype=np.int32), "flags": np.empty(B, dtype=np.int32)}
-        _lib.check(self.lib.vsmpc_adjoint_batch(
-            self._h, _ptr(records), _ptr(rows), _ptr(xbar), _ptr(fmbar), B, _ptr(out["x"]), _ptr(out["first_move"]),
-            _ptr(out["status"]), _ptr(out["iters"]), _ptr(out["grad_x0"]), _ptr(out["grad_cfg"]), _ptr(out["active"]),
-            _ptr(out["flags"]), None), "vsmpc_adjoint_batch")
+        args = [self._h, _ptr(records), _ptr(rows), _ptr(xbar), _ptr(fmbar), B, _ptr(out["x"]), _ptr(out["first_move"]),
+                _ptr(out["status"]), _ptr(out["iters"]), _ptr(out["grad_x0"]), _ptr(out["grad_cfg"]), _ptr(out["active"]),
+                _ptr(out["flags"])]
+        if record:
+            out["grad_in"], out["grad_model"] = np.empty((B, self.n_in)), np.empty((B, L.GRAD_MODEL_SIZE))
+            _lib.check(self.lib.vsmpc_adjoint_record_batch(*args, _ptr(out["grad_in"]), _ptr(out["grad_model"]), None),
+                       "vsmpc_adjoint_record_batch")
+        else:
+            _lib.check(self.lib.vsmpc_adjoint_batch(*args, None), "vsmpc_adjoint_batch")
         return out
 
     def solve_adjoint_device(self, d_in, d_tun, d_xbar, d_fmbar, d_x, d_fm, d_status, d_iters, d_grad_x0, d_grad_cfg,
@@ -320,6 +338,22 @@ class BatchedVSMPC:
             self._h, p(d_in), p(d_tun), p(d_xbar), p(d_fmbar), d_in.shape[0], p(d_x), p(d_fm), p(d_status), p(d_iters),
             p(d_grad_x0), p(d_grad_cfg), p(d_active), p(d_flags), ctypes.c_void_p(s.cuda_stream)),
             "vsmpc_adjoint_batch_device")
+
+    def solve_adjoint_record_device(self, d_in, d_tun, d_xbar, d_fmbar, d_x, d_fm, d_status, d_iters, d_grad_x0, d_grad_cfg,
+                                    d_active, d_flags, d_grad_in, d_grad_model, stream=None):
+        """vsmpc_adjoint_record_batch_device: solve_adjoint_device's arguments and d_grad_in [B, n_in], d_grad_model
+        [B, L.GRAD_MODEL_SIZE] (each may be None), enqueue only"""
+        import torch
+        for t in (d_in, d_tun, d_xbar, d_fmbar):
+            assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
+
+        def p(t):
+            return None if t is None else ctypes.c_void_p(t.data_ptr())
+        _lib.check(self.lib.vsmpc_adjoint_record_batch_device(
+            self._h, p(d_in), p(d_tun), p(d_xbar), p(d_fmbar), d_in.shape[0], p(d_x), p(d_fm), p(d_status), p(d_iters),
+            p(d_grad_x0), p(d_grad_cfg), p(d_active), p(d_flags), p(d_grad_in), p(d_grad_model),
+            ctypes.c_void_p(s.cuda_stream)), "vsmpc_adjoint_record_batch_device")
 
     def timing_begin(self, stream):
         _lib.check(self.lib.vsmpc_timing_begin(self._h, ctypes.c_void_p(stream.cuda_stream)), "vsmpc_timing_begin")

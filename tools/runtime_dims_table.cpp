@@ -1,5 +1,5 @@
-// Prints runtime_dims' LDS and workspace sizes for every horizon the configuration check accepts and the three kinds of
-// the runtime-sized kernels (plain, sensitivity, adjoint), one line each: the table two builds must agree on when the LDS
+// Prints runtime_dims' LDS and workspace sizes for every horizon the configuration check accepts and the four kinds of
+// the runtime-sized kernels (plain, sensitivity, adjoint, adjoint_record), one line each: the table two builds must agree on when the LDS
 // carve-up (csrc/vsmpc_rt_core.hpp) or runtime_dims (csrc/vsmpc_runtime.hip) is restated.  Host code only, no HIP call.
 //
 //   hipcc --offload-arch=gfx950 -std=c++17 -I <pkg>/csrc -c tools/runtime_dims_table.cpp -o dims_table.o
@@ -15,9 +15,10 @@ int main() {
     for (int n = 2; n <= MAX_STAGES; ++n)                  // config_valid (csrc/vsmpc_capi.hip): 2 <= ns <= hc <= n <= 40
         for (int hc = 2; hc <= n; ++hc)
             for (int ns = 2; ns <= hc; ++ns)
-                for (int kind = 0; kind < 3; ++kind) {
-                    const RtDims d = runtime_dims(n, ns, hc, kind == 1, kind == 2);
-                    std::printf("%d %d %d %s %d %d %zu %zu\n", n, ns, hc, kind == 0 ? "plain" : (kind == 1 ? "sensitivity" : "adjoint"),
+                for (int kind = 0; kind < 4; ++kind) {
+                    const RtDims d = runtime_dims(n, ns, hc, kind == 1, kind >= 2, kind == 3);
+                    const char* const names[4] = {"plain", "sensitivity", "adjoint", "adjoint_record"};
+                    std::printf("%d %d %d %s %d %d %zu %zu\n", n, ns, hc, names[kind],
                                 d.lds_doubles, d.ws_doubles, runtime_lds_bytes(d), runtime_tuned_lds_bytes(d));
                 }
     return 0;
