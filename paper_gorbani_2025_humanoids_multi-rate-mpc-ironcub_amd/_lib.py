@@ -10,24 +10,68 @@ from .layout import CConfig
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libvsmpc.so")
 
-# every symbol include/vsmpc.h declares
-EXPORTS = (
-    "vsmpc_create", "vsmpc_create_ex", "vsmpc_destroy", "vsmpc_num_variables", "vsmpc_num_constraints", "vsmpc_input_doubles",
-    "vsmpc_max_batch", "vsmpc_solve_batch", "vsmpc_solve_batch_device", "vsmpc_linearize_batch",
-    "vsmpc_assemble_dense", "vsmpc_condensed_dim", "vsmpc_debug_condensed", "vsmpc_timing_begin",
-    "vsmpc_timing_end", "vsmpc_strerror", "vsmpc_kernel_name", "vsmpc_debug_phase_cycles", "vsmpc_kinematics_batch",
-    "vsmpc_rollout_create", "vsmpc_rollout_destroy", "vsmpc_rollout_reset", "vsmpc_rollout_run",
-    "vsmpc_rollout_get_state", "vsmpc_rollout_get_records", "vsmpc_alloc_host", "vsmpc_free_host",
-    "vsmpc_set_kernel_form", "vsmpc_set_kinematics_options", "vsmpc_provider_batch", "vsmpc_rollout_set_attitude_tracks",
-    "vsmpc_tick", "vsmpc_rollout_set_tree", "vsmpc_num_throttle_unknowns", "vsmpc_sensitivity_batch",
-    "vsmpc_sensitivity_batch_device", "vsmpc_pack_tunables", "vsmpc_solve_batch_tuned", "vsmpc_solve_batch_tuned_device",
-    "vsmpc_rollout_set_tunables", "vsmpc_certify_batch", "vsmpc_certify_batch_device",
-    "vsmpc_set_small_batch_kernel", "vsmpc_small_batch_kernel_for", "vsmpc_small_batch_lds_bytes",
-    "vsmpc_adjoint_batch", "vsmpc_adjoint_batch_device", "vsmpc_adjoint_record_batch", "vsmpc_adjoint_record_batch_device",
+vp = dp = fp = ctypes.c_void_p   # handles and streams, arrays of double, arrays of float
+ip, c_int, c_double, c_float = ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_double, ctypes.c_float
+cfgp, outp = ctypes.POINTER(CConfig), ctypes.POINTER(ctypes.c_void_p)
+_SOLVE = [vp, dp, c_int, dp, dp, vp, vp, vp]                         # h, in, batch, x, first_move, status, iters, stream
+_ADJOINT = [vp, dp, dp, dp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp]   # h, in, tunables, xbar, fmbar, batch, x, first_move,
+#                                                                          status, iters, grad_x0, grad_cfg, active, adj_flags
+
+# every symbol include/vsmpc.h and include/vsmpc_jet.h declare: its argument types, and its result type where that is not int
+SIGNATURES = {
+    "vsmpc_create": [cfgp, c_int, c_int, outp],
+    "vsmpc_create_ex": [cfgp, c_int, c_int, ctypes.c_uint, outp],
+    "vsmpc_destroy": ([vp], None),
+    "vsmpc_num_variables": [vp], "vsmpc_num_constraints": [vp], "vsmpc_input_doubles": [vp], "vsmpc_max_batch": [vp],
+    "vsmpc_condensed_dim": [vp], "vsmpc_num_throttle_unknowns": [vp],
+    "vsmpc_solve_batch": _SOLVE, "vsmpc_solve_batch_device": _SOLVE,
+    "vsmpc_pack_tunables": [vp, cfgp, c_int, dp],
+    # h, in, tunables, batch, x, first_move, status, iters, stream
+    "vsmpc_solve_batch_tuned": [vp, dp, dp, c_int, dp, dp, vp, vp, vp],
+    "vsmpc_solve_batch_tuned_device": [vp, dp, dp, c_int, dp, dp, vp, vp, vp],
+    "vsmpc_rollout_set_tunables": [vp, dp],
+    # h, in, x, tunables, batch, y, cert (, stream)
+    "vsmpc_certify_batch": [vp, dp, dp, dp, c_int, dp, dp], "vsmpc_certify_batch_device": [vp, dp, dp, dp, c_int, dp, dp, vp],
+    # h, in, batch, x, first_move, status, iters, dx_dx0, dfm_dx0, active, sens_flags, stream
+    "vsmpc_sensitivity_batch": [vp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp, vp],
+    "vsmpc_sensitivity_batch_device": [vp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp, vp],
+    "vsmpc_adjoint_batch": _ADJOINT + [vp], "vsmpc_adjoint_batch_device": _ADJOINT + [vp],          # ..., stream
+    "vsmpc_adjoint_record_batch": _ADJOINT + [dp, dp, vp],                                          # ..., grad_in, grad_model, stream
+    "vsmpc_adjoint_record_batch_device": _ADJOINT + [dp, dp, vp],
+    "vsmpc_linearize_batch": [vp, dp, c_int, dp, dp, dp, dp, dp],
+    "vsmpc_assemble_dense": [vp, dp, dp, dp, dp, dp, dp],
+    "vsmpc_debug_condensed": [vp, dp, dp, dp],
+    "vsmpc_kinematics_batch": [vp, dp, c_int, dp, dp],
+    "vsmpc_debug_phase_cycles": [vp, dp, c_int, vp],
+    "vsmpc_timing_begin": [vp, vp],
+    "vsmpc_timing_end": [vp, vp, c_int, ctypes.POINTER(c_float)],
+    "vsmpc_rollout_create": [vp, c_int, dp, dp, c_int, dp, c_int, c_double, outp],
+    "vsmpc_rollout_destroy": ([vp], None),
+    "vsmpc_rollout_reset": [vp, dp, dp],
+    "vsmpc_rollout_run": [vp, c_int, dp, vp],
+    "vsmpc_rollout_get_state": [vp, dp], "vsmpc_rollout_get_records": [vp, dp],
+    "vsmpc_alloc_host": ([ctypes.c_size_t], vp),
+    "vsmpc_free_host": ([vp], None),
+    "vsmpc_set_kernel_form": [vp, c_int], "vsmpc_set_small_batch_kernel": [vp, c_int], "vsmpc_small_batch_kernel_for": [vp, c_int],
+    "vsmpc_small_batch_lds_bytes": ([c_int, c_int, c_int], ctypes.c_size_t),
+    "vsmpc_set_kinematics_options": [vp, ip, c_int],
+    "vsmpc_provider_batch": [vp, vp, dp, c_int, dp, dp, dp],
+    "vsmpc_rollout_set_attitude_tracks": [vp, dp, dp],
+    "vsmpc_rollout_set_tree": [vp, vp],
+    "vsmpc_tick": [vp, dp, dp, c_int, dp, dp, vp, vp, vp],
+    "vsmpc_rollout_set_jet_plant": [vp, vp, dp, dp],
+    "vsmpc_strerror": ([c_int], ctypes.c_char_p),
+    "vsmpc_kernel_name": ([vp], ctypes.c_char_p),
     # include/vsmpc_jet.h
-    "vsmpc_jet_create", "vsmpc_jet_destroy", "vsmpc_jet_nn_step", "vsmpc_jet_nn_sequence", "vsmpc_jet_ekf_update",
-    "vsmpc_jet_plant_run", "vsmpc_jet_plant_run_device", "vsmpc_rollout_set_jet_plant",
-)
+    "vsmpc_jet_create": [fp, fp, fp, fp, fp, fp, dp, c_int, c_int, c_int, outp],
+    "vsmpc_jet_destroy": ([vp], None),
+    "vsmpc_jet_nn_step": [vp, fp, fp, c_int, c_float, fp, fp, fp, fp],
+    "vsmpc_jet_nn_sequence": [vp, fp, c_int, c_int, c_float, fp, fp, fp, fp],
+    "vsmpc_jet_ekf_update": [vp, dp, dp, dp, dp, c_int, c_double, dp, dp],
+    "vsmpc_jet_plant_run": [vp, fp, dp, dp, fp, c_int, c_int, c_int, c_double, dp, dp, dp],
+    "vsmpc_jet_plant_run_device": [vp, fp, dp, dp, fp, c_int, c_int, c_int, c_double, dp, dp, dp, vp],
+}
+EXPORTS = tuple(SIGNATURES)
 
 _lib = None
 
@@ -49,118 +93,9 @@ def load():
     except Exception:  # pragma: no cover - torch is optional for the C-ABI itself
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    vp, ip, dp, c_int = ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.c_int
-    lib.vsmpc_create.argtypes = [ctypes.POINTER(CConfig), c_int, c_int, ctypes.POINTER(vp)]
-    lib.vsmpc_create.restype = c_int
-    lib.vsmpc_create_ex.argtypes = [ctypes.POINTER(CConfig), c_int, c_int, ctypes.c_uint, ctypes.POINTER(vp)]
-    lib.vsmpc_create_ex.restype = c_int
-    lib.vsmpc_destroy.argtypes = [vp]
-    lib.vsmpc_destroy.restype = None
-    for name in ("vsmpc_num_variables", "vsmpc_num_constraints", "vsmpc_input_doubles", "vsmpc_max_batch",
-                 "vsmpc_condensed_dim", "vsmpc_num_throttle_unknowns"):
-        getattr(lib, name).argtypes = [vp]
-        getattr(lib, name).restype = c_int
-    lib.vsmpc_solve_batch.argtypes = [vp, dp, c_int, dp, dp, vp, vp, vp]
-    lib.vsmpc_solve_batch.restype = c_int
-    lib.vsmpc_solve_batch_device.argtypes = [vp, dp, c_int, dp, dp, vp, vp, vp]
-    lib.vsmpc_solve_batch_device.restype = c_int
-    lib.vsmpc_pack_tunables.argtypes = [vp, ctypes.POINTER(CConfig), c_int, dp]
-    lib.vsmpc_pack_tunables.restype = c_int
-    # h, in, tunables, batch, x, first_move, status, iters, stream
-    lib.vsmpc_solve_batch_tuned.argtypes = [vp, dp, dp, c_int, dp, dp, vp, vp, vp]
-    lib.vsmpc_solve_batch_tuned.restype = c_int
-    lib.vsmpc_solve_batch_tuned_device.argtypes = [vp, dp, dp, c_int, dp, dp, vp, vp, vp]
-    lib.vsmpc_solve_batch_tuned_device.restype = c_int
-    lib.vsmpc_rollout_set_tunables.argtypes = [vp, dp]
-    lib.vsmpc_rollout_set_tunables.restype = c_int
-    # h, in, x, tunables, batch, y, cert (, stream)
-    lib.vsmpc_certify_batch.argtypes = [vp, dp, dp, dp, c_int, dp, dp]
-    lib.vsmpc_certify_batch.restype = c_int
-    lib.vsmpc_certify_batch_device.argtypes = [vp, dp, dp, dp, c_int, dp, dp, vp]
-    lib.vsmpc_certify_batch_device.restype = c_int
-    # h, in, batch, x, first_move, status, iters, dx_dx0, dfm_dx0, active, sens_flags, stream
-    lib.vsmpc_sensitivity_batch.argtypes = [vp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp, vp]
-    lib.vsmpc_sensitivity_batch.restype = c_int
-    lib.vsmpc_sensitivity_batch_device.argtypes = [vp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp, vp]
-    lib.vsmpc_sensitivity_batch_device.restype = c_int
-    # h, in, tunables, xbar, fmbar, batch, x, first_move, status, iters, grad_x0, grad_cfg, active, adj_flags, stream
-    lib.vsmpc_adjoint_batch.argtypes = [vp, dp, dp, dp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp, vp]
-    lib.vsmpc_adjoint_batch.restype = c_int
-    lib.vsmpc_adjoint_batch_device.argtypes = [vp, dp, dp, dp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp, vp]
-    lib.vsmpc_adjoint_batch_device.restype = c_int
-    # the same, with grad_in and grad_model in front of stream
-    for fn in (lib.vsmpc_adjoint_record_batch, lib.vsmpc_adjoint_record_batch_device):
-        fn.argtypes = [vp, dp, dp, dp, dp, c_int, dp, dp, vp, vp, dp, dp, vp, vp, dp, dp, vp]
-        fn.restype = c_int
-    lib.vsmpc_linearize_batch.argtypes = [vp, dp, c_int, dp, dp, dp, dp, dp]
-    lib.vsmpc_linearize_batch.restype = c_int
-    lib.vsmpc_assemble_dense.argtypes = [vp, dp, dp, dp, dp, dp, dp]
-    lib.vsmpc_assemble_dense.restype = c_int
-    lib.vsmpc_debug_condensed.argtypes = [vp, dp, dp, dp]
-    lib.vsmpc_debug_condensed.restype = c_int
-    lib.vsmpc_kinematics_batch.argtypes = [vp, dp, c_int, dp, dp]
-    lib.vsmpc_kinematics_batch.restype = c_int
-    lib.vsmpc_debug_phase_cycles.argtypes = [vp, dp, c_int, vp]
-    lib.vsmpc_debug_phase_cycles.restype = c_int
-    lib.vsmpc_timing_begin.argtypes = [vp, vp]
-    lib.vsmpc_timing_begin.restype = c_int
-    lib.vsmpc_timing_end.argtypes = [vp, vp, c_int, ctypes.POINTER(ctypes.c_float)]
-    lib.vsmpc_timing_end.restype = c_int
-    lib.vsmpc_rollout_create.argtypes = [vp, c_int, dp, dp, c_int, dp, c_int, ctypes.c_double, ctypes.POINTER(vp)]
-    lib.vsmpc_rollout_create.restype = c_int
-    lib.vsmpc_rollout_destroy.argtypes = [vp]
-    lib.vsmpc_rollout_destroy.restype = None
-    lib.vsmpc_rollout_reset.argtypes = [vp, dp, dp]
-    lib.vsmpc_rollout_reset.restype = c_int
-    lib.vsmpc_rollout_run.argtypes = [vp, c_int, dp, vp]
-    lib.vsmpc_rollout_run.restype = c_int
-    lib.vsmpc_rollout_get_state.argtypes = [vp, dp]
-    lib.vsmpc_rollout_get_state.restype = c_int
-    lib.vsmpc_rollout_get_records.argtypes = [vp, dp]
-    lib.vsmpc_rollout_get_records.restype = c_int
-    lib.vsmpc_alloc_host.argtypes = [ctypes.c_size_t]
-    lib.vsmpc_alloc_host.restype = vp
-    lib.vsmpc_free_host.argtypes = [vp]
-    lib.vsmpc_free_host.restype = None
-    lib.vsmpc_set_kernel_form.argtypes = [vp, c_int]
-    lib.vsmpc_set_kernel_form.restype = c_int
-    lib.vsmpc_set_small_batch_kernel.argtypes = [vp, c_int]
-    lib.vsmpc_set_small_batch_kernel.restype = c_int
-    lib.vsmpc_small_batch_kernel_for.argtypes = [vp, c_int]
-    lib.vsmpc_small_batch_kernel_for.restype = c_int
-    lib.vsmpc_small_batch_lds_bytes.argtypes = [c_int, c_int, c_int]
-    lib.vsmpc_small_batch_lds_bytes.restype = ctypes.c_size_t
-    lib.vsmpc_set_kinematics_options.argtypes = [vp, ip, c_int]
-    lib.vsmpc_set_kinematics_options.restype = c_int
-    lib.vsmpc_provider_batch.argtypes = [vp, vp, dp, c_int, dp, dp, dp]
-    lib.vsmpc_provider_batch.restype = c_int
-    lib.vsmpc_rollout_set_attitude_tracks.argtypes = [vp, dp, dp]
-    lib.vsmpc_rollout_set_attitude_tracks.restype = c_int
-    lib.vsmpc_rollout_set_tree.argtypes = [vp, vp]
-    lib.vsmpc_rollout_set_tree.restype = c_int
-    lib.vsmpc_tick.argtypes = [vp, dp, dp, c_int, dp, dp, vp, vp, vp]
-    lib.vsmpc_tick.restype = c_int
-    lib.vsmpc_rollout_set_jet_plant.argtypes = [vp, vp, dp, dp]
-    lib.vsmpc_rollout_set_jet_plant.restype = c_int
-    fp = ctypes.c_void_p
-    lib.vsmpc_jet_create.argtypes = [fp, fp, fp, fp, fp, fp, dp, c_int, c_int, c_int, ctypes.POINTER(vp)]
-    lib.vsmpc_jet_create.restype = c_int
-    lib.vsmpc_jet_destroy.argtypes = [vp]
-    lib.vsmpc_jet_destroy.restype = None
-    lib.vsmpc_jet_nn_step.argtypes = [vp, fp, fp, c_int, ctypes.c_float, fp, fp, fp, fp]
-    lib.vsmpc_jet_nn_step.restype = c_int
-    lib.vsmpc_jet_nn_sequence.argtypes = [vp, fp, c_int, c_int, ctypes.c_float, fp, fp, fp, fp]
-    lib.vsmpc_jet_nn_sequence.restype = c_int
-    lib.vsmpc_jet_ekf_update.argtypes = [vp, dp, dp, dp, dp, c_int, ctypes.c_double, dp, dp]
-    lib.vsmpc_jet_ekf_update.restype = c_int
-    lib.vsmpc_jet_plant_run.argtypes = [vp, fp, dp, dp, fp, c_int, c_int, c_int, ctypes.c_double, dp, dp, dp]
-    lib.vsmpc_jet_plant_run.restype = c_int
-    lib.vsmpc_jet_plant_run_device.argtypes = [vp, fp, dp, dp, fp, c_int, c_int, c_int, ctypes.c_double, dp, dp, dp, vp]
-    lib.vsmpc_jet_plant_run_device.restype = c_int
-    lib.vsmpc_strerror.argtypes = [c_int]
-    lib.vsmpc_strerror.restype = ctypes.c_char_p
-    lib.vsmpc_kernel_name.argtypes = [vp]
-    lib.vsmpc_kernel_name.restype = ctypes.c_char_p
+    for name, sig in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = (list(sig[0]), sig[1]) if isinstance(sig, tuple) else (list(sig), c_int)
     _lib = lib
     return lib
 

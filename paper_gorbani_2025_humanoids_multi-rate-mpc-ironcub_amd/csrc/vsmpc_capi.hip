@@ -152,14 +152,14 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     h->variant = variant;
     h->runtime = runtime ? 1 : 0;
     h->rt = rt;
-    h->sens = sens ? 1 : 0;
-    h->rts = rts;
+    h->sens.on = sens ? 1 : 0;
+    h->sens.dims = rts;
     h->tunables = (flags & VSMPC_CREATE_TUNABLES) != 0u ? 1 : 0;
     h->certify = (flags & VSMPC_CREATE_CERTIFY) != 0u ? 1 : 0;
-    h->adjoint = adjoint ? 1 : 0;
-    h->rta = rta;
-    h->adjoint_record = adjoint_record ? 1 : 0;
-    h->rtr = rtr;
+    h->adjoint.on = adjoint ? 1 : 0;
+    h->adjoint.dims = rta;
+    h->adjoint_record.on = adjoint_record ? 1 : 0;
+    h->adjoint_record.dims = rtr;
     h->form = runtime ? 0 : initial_kernel_form();
     for (int i = 0; i < VSMPC_N_JOINTS; ++i) h->kin.sel[i] = 3 + i;   // the shipped robot: joints 3..10
     h->kin.constant_lambda = 0;
@@ -181,6 +181,8 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     const size_t B = size_t(max_batch);
     hipError_t e = hipSuccess;   // the first failure wins: nothing is allocated after it
     auto need = [&e](auto& buf, size_t n, bool wanted = true) { if (wanted && e == hipSuccess) e = buf.alloc(n); };
+    // staging of a chunked entry: `width` elements for each of `chunk` instances (the copies read the width from the buffer)
+    auto stage = [&e](auto& buf, size_t chunk, size_t width, bool wanted) { if (wanted && e == hipSuccess) e = buf.alloc(chunk, width); };
     need(h->d_in, B * h->n_in);
     need(h->d_x, B * h->n_var);
     need(h->d_fm, B * VSMPC_FM_SIZE);
@@ -193,27 +195,27 @@ int vsmpc_create_ex(const vsmpc_config* cfg, int device, int max_batch, unsigned
     need(h->d_stamps, B * 16);
     need(h->d_ws, B * size_t(rt.ws_doubles), runtime);
     const size_t C = std::min(B, size_t(SENS_CHUNK));
-    need(h->d_sws, B * size_t(rts.ws_doubles), sens);
-    need(h->d_sdx, C * h->n_var * SENS_NPAR, sens);
-    need(h->d_sdfm, C * VSMPC_FM_SIZE * SENS_NPAR, sens);
-    need(h->d_sact, C * rts.nv, sens);
-    need(h->d_sflags, C, sens);
+    need(h->sens.ws, B * size_t(rts.ws_doubles), sens);
+    stage(h->sens.dx, C, size_t(h->n_var) * SENS_NPAR, sens);
+    stage(h->sens.dfm, C, size_t(VSMPC_FM_SIZE) * SENS_NPAR, sens);
+    stage(h->sens.active, C, rts.nv, sens);
+    stage(h->sens.flags, C, 1, sens);
     need(h->d_tun, B * VSMPC_TUNE_SIZE, h->tunables);
     need(h->d_cx, B * h->n_var, h->certify);
     need(h->d_cy, B * h->n_con, h->certify);
     need(h->d_ccert, B * VSMPC_CERT_SIZE, h->certify);
     need(h->d_ctun, B * VSMPC_TUNE_SIZE, h->certify);
     const size_t CA = std::min(B, size_t(ADJ_CHUNK));
-    need(h->d_aws, B * size_t(rta.ws_doubles), adjoint && !runtime);
-    need(h->d_axbar, CA * h->n_var, adjoint);
-    need(h->d_afmbar, CA * VSMPC_FM_SIZE, adjoint);
-    need(h->d_atun, CA * VSMPC_TUNE_SIZE, adjoint);
-    need(h->d_agx0, CA * NX, adjoint);
-    need(h->d_agcfg, CA * VSMPC_GRAD_SIZE, adjoint);
-    need(h->d_aact, CA * rta.nv, adjoint);
-    need(h->d_aflags, CA, adjoint);
-    need(h->d_agin, CA * h->n_in, adjoint_record);
-    need(h->d_agmodel, CA * VSMPC_GRAD_MODEL_SIZE, adjoint_record);
+    need(h->adjoint.ws, B * size_t(rta.ws_doubles), adjoint && !runtime);
+    stage(h->adjoint.xbar, CA, h->n_var, adjoint);
+    stage(h->adjoint.fmbar, CA, VSMPC_FM_SIZE, adjoint);
+    stage(h->adjoint.tun, CA, VSMPC_TUNE_SIZE, adjoint);
+    stage(h->adjoint.gx0, CA, NX, adjoint);
+    stage(h->adjoint.gcfg, CA, VSMPC_GRAD_SIZE, adjoint);
+    stage(h->adjoint.active, CA, rta.nv, adjoint);
+    stage(h->adjoint.flags, CA, 1, adjoint);
+    stage(h->adjoint_record.gin, CA, h->n_in, adjoint_record);
+    stage(h->adjoint_record.gmodel, CA, VSMPC_GRAD_MODEL_SIZE, adjoint_record);
     for (int i = 0; i < PIPE_STREAMS && e == hipSuccess; ++i) {
         e = hipStreamCreateWithFlags(h->pipe[i].put(), hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(h->pipe_done[i].put(), hipEventDisableTiming);

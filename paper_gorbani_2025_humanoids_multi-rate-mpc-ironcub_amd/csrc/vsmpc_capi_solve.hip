@@ -1,20 +1,28 @@
 // C-ABI of include/vsmpc.h, the hot entries: solve (device and host pointers, per-instance tunables), sensitivities,
-// certificates and the one-submission tick, with their host<->device staging.
+// adjoints, certificates and the one-submission tick, with their host<->device staging.  The runtime-sized kernels are
+// launched through launch_runtime over an RtLaunch (vsmpc_launch.hpp); their chunked host-pointer entries are chunked_host
+// and a table of staged rows each.
 #include "vsmpc_host.hpp"
 
 using namespace vsmpc;
 
+// the fields of an RtLaunch that every entry of the runtime family has (the workspace and the kind's own are the caller's)
+static RtLaunch solve_args(const double* d_in, const double* d_tun, double* d_x, double* d_fm, int* d_status, int* d_iters) {
+    RtLaunch a;
+    a.in = d_in; a.tun = d_tun;
+    a.x = d_x; a.fm = d_fm; a.status = d_status; a.iters = d_iters;
+    return a;
+}
+
 hipError_t vsmpc::solve_launch(const vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_fm, int* d_status,
                                int* d_iters, size_t first, hipStream_t s, const double* d_tun) {
-    if (d_tun != nullptr) {
-        if (h->runtime)
-            return launch_solve_runtime_tuned(h->rt, h->dev, d_in, d_tun, batch, h->d_ws + first * size_t(h->rt.ws_doubles), d_x,
-                                              d_fm, d_status, d_iters, s);
-        return launch_solve_tuned(h->variant, h->form, h->dev, d_in, d_tun, batch, d_x, d_fm, d_status, d_iters, s);
+    if (h->runtime) {
+        RtLaunch a = solve_args(d_in, d_tun, d_x, d_fm, d_status, d_iters);
+        a.ws = h->d_ws + first * size_t(h->rt.ws_doubles);
+        return launch_runtime(RT_SOLVE, h->rt, h->dev, batch, a, s);
     }
-    if (h->runtime)
-        return launch_solve_runtime(h->rt, h->dev, d_in, batch, h->d_ws + first * size_t(h->rt.ws_doubles), d_x, d_fm,
-                                    d_status, d_iters, s);
+    if (d_tun != nullptr)
+        return launch_solve_tuned(h->variant, h->form, h->dev, d_in, d_tun, batch, d_x, d_fm, d_status, d_iters, s);
     if (small_batch_kernel(h, batch))
         return launch_solve_small(h->variant, h->dev, d_in, batch, d_x, d_fm, d_status, d_iters, nullptr, s);
     return launch_solve(h->variant, h->form, h->dev, d_in, batch, d_x, d_fm, d_status, d_iters, nullptr, nullptr, nullptr, s);
@@ -125,6 +133,89 @@ int solve_batch_host(vsmpc_handle* h, const double* in, const double* tun, int b
     return VSMPC_OK;
 }
 
+// What the batch entries check behind their own null and alignment checks, in the precedence of the return codes: the create
+// flag the entry needs (`why`: the text that names it, nullptr the plain one), the batch against the handle's, the empty
+// batch.  GO: the entry goes on; any other value is what it returns.
+constexpr int GO = 1;
+int batch_entry(const vsmpc_handle* h, int batch, bool has_flag = true, const char* why = nullptr) {
+    if (!has_flag) return unsupported(why);
+    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
+    return batch == 0 ? VSMPC_OK : GO;
+}
+
+// The chunked host-pointer driver of the runtime family (vsmpc_sensitivity_batch, vsmpc_adjoint_batch,
+// vsmpc_adjoint_record_batch).  An entry is its kind and a table of staged rows, one per argument beyond the solve's own.
+struct RtFamily {
+    RtMode kind;
+    const RtDims& d;
+    double* ws;          // workspace of instance 0, max_batch x d.ws_doubles
+    int chunk;           // instances per launch: what the staging holds
+    const char* entry;   // the name a HIP failure is reported under
+};
+struct HostSolve { const double* in; double *x, *first_move; int *status, *iters; };   // what every host-pointer solve has
+// the caller's rows (nullptr: not given / not wanted, nothing is enqueued), the device staging of one chunk, the bytes of one
+// instance, the direction
+struct StagedRow { void* host; void* dev; size_t bytes; bool upload; };
+// a row of the table; `arg`, the field of the RtLaunch it serves, gets the staging where the caller gave a pointer
+template <typename T>
+StagedRow upload(const T* host, const StageBuf<T>& buf, const T*& arg) {
+    arg = host ? buf.get() : nullptr;
+    return {const_cast<T*>(host), buf.get(), buf.width * sizeof(T), true};
+}
+template <typename T>
+StagedRow download(T* host, const StageBuf<T>& buf, T*& arg) {
+    arg = host ? buf.get() : nullptr;
+    return {host, buf.get(), buf.width * sizeof(T), false};
+}
+// instances first .. first + n - 1 of every row of one direction, in table order; stops enqueuing at the first failure
+hipError_t copy_staged(const StagedRow* rows, size_t n_rows, bool up, size_t first, size_t n, hipStream_t s) {
+    for (const StagedRow* r = rows; r != rows + n_rows; ++r) {
+        if (r->upload != up || r->host == nullptr) continue;
+        char* const host = static_cast<char*>(r->host) + first * r->bytes;
+        const hipError_t e = up ? hipMemcpyAsync(r->dev, host, n * r->bytes, hipMemcpyHostToDevice, s)
+                                : hipMemcpyAsync(host, r->dev, n * r->bytes, hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+// Chunks of f.chunk instances in stream order: upload, launch, download; the staging of one chunk is read back before the
+// next overwrites it.  `a` holds the staged rows' fields (and nothing else yet).  The first error is kept, nothing is
+// enqueued behind it, and nothing returns while copies into the caller's buffers are queued.
+int chunked_host(vsmpc_handle* h, const RtFamily& f, const HostSolve& io, int batch, RtLaunch a, const StagedRow* rows,
+                 size_t n_rows, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ON_DEVICE(h->device);
+    hipError_t err = hipSuccess;
+    for (int first = 0; first < batch && err == hipSuccess; first += f.chunk) {
+        const int n = std::min(f.chunk, batch - first);
+        const size_t o = size_t(first), N = size_t(n);
+        a.in = h->d_in + o * h->n_in;
+        a.ws = f.ws + o * size_t(f.d.ws_doubles);
+        a.x = io.x ? h->d_x + o * h->n_var : nullptr;
+        a.fm = io.first_move ? h->d_fm + o * VSMPC_FM_SIZE : nullptr;
+        a.status = h->d_status + o;
+        a.iters = io.iters ? h->d_iters + o : nullptr;
+        err = upload_rows(h->d_in, io.in, o, N, h->n_in, s);
+        if (err == hipSuccess) err = copy_staged(rows, n_rows, true, o, N, s);
+        if (err == hipSuccess) err = launch_runtime(f.kind, f.d, h->dev, n, a, s);
+        if (err == hipSuccess) err = download_results(h, o, N, io.x, io.first_move, io.status, io.iters, s);
+        if (err == hipSuccess) err = copy_staged(rows, n_rows, false, o, N, s);
+    }
+    const hipError_t e = hipStreamSynchronize(s);
+    if (err == hipSuccess) err = e;
+    if (err != hipSuccess) return hip_fail(err, f.entry);
+    return VSMPC_OK;
+}
+
+// adjoint_kernel_rt and adjoint_record_kernel_rt run on the workspace of the runtime handle, or the one
+// VSMPC_CREATE_ADJOINT allocated
+double* adjoint_workspace(const vsmpc_handle* h) { return h->runtime ? h->d_ws.get() : h->adjoint.ws.get(); }
+const char* const ADJOINT_NEEDS_FLAG = "vsmpc_adjoint_batch needs a handle created with VSMPC_CREATE_ADJOINT (vsmpc_create_ex)";
+const char* const ADJOINT_RECORD_NEEDS_FLAG =
+    "vsmpc_adjoint_record_batch needs a handle created with VSMPC_CREATE_ADJOINT_RECORD (vsmpc_create_ex)";
+// (the kernels load a row of tunables 16 bytes per lane)
+bool misaligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) != 0; }
+
 }  // namespace
 
 extern "C" {
@@ -132,8 +223,7 @@ extern "C" {
 int vsmpc_solve_batch_device(vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_first_move,
                              int* d_status, int* d_iters, void* stream) {
     if (h == nullptr || d_in == nullptr || d_status == nullptr || batch < 0) return invalid_arg();
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
+    if (const int rc = batch_entry(h, batch); rc != GO) return rc;
     ON_DEVICE(h->device);   // an enqueue-only entry must not change the caller's current device either
     HIP_TRY(solve_launch(h, d_in, batch, d_x, d_first_move, d_status, d_iters, 0, static_cast<hipStream_t>(stream)));
     return VSMPC_OK;
@@ -142,17 +232,15 @@ int vsmpc_solve_batch_device(vsmpc_handle* h, const double* d_in, int batch, dou
 int vsmpc_solve_batch(vsmpc_handle* h, const double* in, int batch, double* x, double* first_move, int* status,
                       int* iters, void* stream) {
     if (h == nullptr || in == nullptr || status == nullptr || batch < 0) return invalid_arg();
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
+    if (const int rc = batch_entry(h, batch); rc != GO) return rc;
     return solve_batch_host(h, in, nullptr, batch, x, first_move, status, iters, stream);
 }
 
 int vsmpc_solve_batch_tuned_device(vsmpc_handle* h, const double* d_in, const double* d_tunables, int batch, double* d_x,
                                    double* d_first_move, int* d_status, int* d_iters, void* stream) {
     if (h == nullptr || d_in == nullptr || d_tunables == nullptr || d_status == nullptr || batch < 0) return invalid_arg();
-    if ((reinterpret_cast<size_t>(d_tunables) & 15) != 0) return invalid_arg();   // the kernels load 16 bytes per lane
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
+    if (misaligned16(d_tunables)) return invalid_arg();
+    if (const int rc = batch_entry(h, batch); rc != GO) return rc;
     ON_DEVICE(h->device);
     HIP_TRY(solve_launch(h, d_in, batch, d_x, d_first_move, d_status, d_iters, 0, static_cast<hipStream_t>(stream), d_tunables));
     return VSMPC_OK;
@@ -161,132 +249,50 @@ int vsmpc_solve_batch_tuned_device(vsmpc_handle* h, const double* d_in, const do
 int vsmpc_solve_batch_tuned(vsmpc_handle* h, const double* in, const double* tunables, int batch, double* x,
                             double* first_move, int* status, int* iters, void* stream) {
     if (h == nullptr || in == nullptr || tunables == nullptr || status == nullptr || batch < 0) return invalid_arg();
-    if (!h->tunables) return unsupported();
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
+    if (const int rc = batch_entry(h, batch, h->tunables); rc != GO) return rc;
     return solve_batch_host(h, in, tunables, batch, x, first_move, status, iters, stream);
 }
 
+// Sensitivities of the solution to X0 (include/vsmpc.h): sens_kernel_rt on the workspace VSMPC_CREATE_SENSITIVITY allocated
 int vsmpc_sensitivity_batch_device(vsmpc_handle* h, const double* d_in, int batch, double* d_x, double* d_first_move,
                                    int* d_status, int* d_iters, double* d_dx_dx0, double* d_dfm_dx0, int* d_active,
                                    int* d_sens_flags, void* stream) {
     if (h == nullptr || d_in == nullptr || d_status == nullptr || batch < 0) return invalid_arg();
-    if (!h->sens) return unsupported();
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
+    if (const int rc = batch_entry(h, batch, h->sens.on); rc != GO) return rc;
     ON_DEVICE(h->device);
-    HIP_TRY(launch_sensitivity_runtime(h->rts, h->dev, d_in, batch, h->d_sws, d_x, d_first_move, d_status, d_iters, d_dx_dx0,
-                                       d_dfm_dx0, d_active, d_sens_flags, static_cast<hipStream_t>(stream)));
+    RtLaunch a = solve_args(d_in, nullptr, d_x, d_first_move, d_status, d_iters);
+    a.ws = h->sens.ws;
+    a.dx = d_dx_dx0; a.dfm = d_dfm_dx0; a.active = d_active; a.flags = d_sens_flags;
+    HIP_TRY(launch_runtime(RT_SENS, h->sens.dims, h->dev, batch, a, static_cast<hipStream_t>(stream)));
     return VSMPC_OK;
 }
 
 int vsmpc_sensitivity_batch(vsmpc_handle* h, const double* in, int batch, double* x, double* first_move, int* status,
                             int* iters, double* dx_dx0, double* dfm_dx0, int* active, int* sens_flags, void* stream) {
     if (h == nullptr || in == nullptr || status == nullptr || batch < 0) return invalid_arg();
-    if (!h->sens) return unsupported();
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    ON_DEVICE(h->device);
-    const size_t NV = size_t(h->rts.nv), J = SENS_NPAR, FM = VSMPC_FM_SIZE;
-    // chunks of SENS_CHUNK instances in stream order: the staging of one chunk is read back before the next overwrites it
-    hipError_t err = hipSuccess;
-    auto ok = [&](hipError_t e) { if (e != hipSuccess && err == hipSuccess) err = e; return err == hipSuccess; };
-    for (int first = 0; first < batch && err == hipSuccess; first += SENS_CHUNK) {
-        const int n = std::min(SENS_CHUNK, batch - first);
-        const size_t o = size_t(first), N = size_t(n);
-        if (!ok(upload_rows(h->d_in, in, o, N, h->n_in, s))) break;
-        if (!ok(launch_sensitivity_runtime(h->rts, h->dev, h->d_in + o * h->n_in, n, h->d_sws + o * size_t(h->rts.ws_doubles),
-                                           x ? h->d_x + o * h->n_var : nullptr, first_move ? h->d_fm + o * FM : nullptr,
-                                           h->d_status + o, iters ? h->d_iters + o : nullptr, dx_dx0 ? h->d_sdx : nullptr,
-                                           dfm_dx0 ? h->d_sdfm : nullptr, active ? h->d_sact : nullptr,
-                                           sens_flags ? h->d_sflags : nullptr, s)))
-            break;
-        ok(download_results(h, o, N, x, first_move, status, iters, s));
-        if (dx_dx0)
-            ok(hipMemcpyAsync(dx_dx0 + o * h->n_var * J, h->d_sdx, N * h->n_var * J * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (dfm_dx0) ok(hipMemcpyAsync(dfm_dx0 + o * FM * J, h->d_sdfm, N * FM * J * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (active) ok(hipMemcpyAsync(active + o * NV, h->d_sact, N * NV * sizeof(int), hipMemcpyDeviceToHost, s));
-        if (sens_flags) ok(hipMemcpyAsync(sens_flags + o, h->d_sflags, N * sizeof(int), hipMemcpyDeviceToHost, s));
-    }
-    const hipError_t e = hipStreamSynchronize(s);   // nothing returns while copies into the caller's buffers are queued
-    if (err == hipSuccess) err = e;
-    if (err != hipSuccess) return hip_fail(err, "vsmpc_sensitivity_batch");
-    return VSMPC_OK;
+    if (const int rc = batch_entry(h, batch, h->sens.on); rc != GO) return rc;
+    const vsmpc_handle::Sens& k = h->sens;
+    RtLaunch a;
+    const StagedRow rows[] = {download(dx_dx0, k.dx, a.dx), download(dfm_dx0, k.dfm, a.dfm), download(active, k.active, a.active),
+                              download(sens_flags, k.flags, a.flags)};
+    return chunked_host(h, {RT_SENS, k.dims, k.ws, SENS_CHUNK, "vsmpc_sensitivity_batch"}, {in, x, first_move, status, iters},
+                        batch, a, rows, std::size(rows), stream);
 }
 
-// Adjoint of the solve (include/vsmpc.h): adjoint_kernel_rt, or adjoint_kernel_rt_tuned with rows of tunables, on the
-// workspace of the runtime handle or the one VSMPC_CREATE_ADJOINT allocated
-static double* adjoint_workspace(const vsmpc_handle* h) { return h->runtime ? h->d_ws.get() : h->d_aws.get(); }
-static const char* const ADJOINT_NEEDS_FLAG =
-    "vsmpc_adjoint_batch needs a handle created with VSMPC_CREATE_ADJOINT (vsmpc_create_ex)";
-
+// Adjoint of the solve (include/vsmpc.h): adjoint_kernel_rt, or adjoint_kernel_rt_tuned with rows of tunables
 int vsmpc_adjoint_batch_device(vsmpc_handle* h, const double* d_in, const double* d_tunables, const double* d_xbar,
                                const double* d_fmbar, int batch, double* d_x, double* d_first_move, int* d_status,
                                int* d_iters, double* d_grad_x0, double* d_grad_cfg, int* d_active, int* d_adj_flags,
                                void* stream) {
     if (h == nullptr || d_in == nullptr || d_xbar == nullptr || d_status == nullptr || batch < 0) return invalid_arg();
-    if ((reinterpret_cast<size_t>(d_tunables) & 15) != 0) return invalid_arg();   // the kernel loads 16 bytes per lane
-    if (!h->adjoint) return unsupported(ADJOINT_NEEDS_FLAG);
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
+    if (misaligned16(d_tunables)) return invalid_arg();
+    if (const int rc = batch_entry(h, batch, h->adjoint.on, ADJOINT_NEEDS_FLAG); rc != GO) return rc;
     ON_DEVICE(h->device);
-    HIP_TRY(launch_adjoint_runtime(h->rta, h->dev, d_in, d_tunables, batch, adjoint_workspace(h), d_x, d_first_move, d_status,
-                                   d_iters, d_xbar, d_fmbar, d_grad_x0, d_grad_cfg, d_active, d_adj_flags,
-                                   static_cast<hipStream_t>(stream)));
-    return VSMPC_OK;
-}
-
-// the host-pointer entries of the adjoint and of the record adjoint (`record`: adjoint_record_kernel_rt, which also writes
-// grad_in and grad_model): chunks of ADJ_CHUNK instances in stream order, the staging of one chunk is read back before the
-// next overwrites it
-static int adjoint_batch_host(vsmpc_handle* h, bool record, const double* in, const double* tunables, const double* xbar,
-                              const double* fmbar, int batch, double* x, double* first_move, int* status, int* iters,
-                              double* grad_x0, double* grad_cfg, int* active, int* adj_flags, double* grad_in,
-                              double* grad_model, void* stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    ON_DEVICE(h->device);
-    const RtDims& d = record ? h->rtr : h->rta;
-    const size_t NV = size_t(d.nv), FM = VSMPC_FM_SIZE, T = VSMPC_TUNE_SIZE, G = VSMPC_GRAD_SIZE, GM = VSMPC_GRAD_MODEL_SIZE;
-    hipError_t err = hipSuccess;
-    auto ok = [&](hipError_t e) { if (e != hipSuccess && err == hipSuccess) err = e; return err == hipSuccess; };
-    for (int first = 0; first < batch && err == hipSuccess; first += ADJ_CHUNK) {
-        const int n = std::min(ADJ_CHUNK, batch - first);
-        const size_t o = size_t(first), N = size_t(n);
-        if (!ok(upload_rows(h->d_in, in, o, N, h->n_in, s))) break;
-        if (!ok(hipMemcpyAsync(h->d_axbar, xbar + o * h->n_var, N * h->n_var * sizeof(double), hipMemcpyHostToDevice, s))) break;
-        if (fmbar && !ok(hipMemcpyAsync(h->d_afmbar, fmbar + o * FM, N * FM * sizeof(double), hipMemcpyHostToDevice, s))) break;
-        if (tunables && !ok(hipMemcpyAsync(h->d_atun, tunables + o * T, N * T * sizeof(double), hipMemcpyHostToDevice, s))) break;
-        const double* d_in = h->d_in + o * h->n_in;
-        const double* d_tun = tunables ? h->d_atun.get() : nullptr;
-        double* d_ws = adjoint_workspace(h) + o * size_t(d.ws_doubles);
-        double* d_x = x ? h->d_x + o * h->n_var : nullptr;
-        double* d_fm = first_move ? h->d_fm + o * FM : nullptr;
-        int* d_it = iters ? h->d_iters + o : nullptr;
-        const double* d_fmbar = fmbar ? h->d_afmbar.get() : nullptr;
-        double* d_gx0 = grad_x0 ? h->d_agx0.get() : nullptr;
-        double* d_gcfg = grad_cfg ? h->d_agcfg.get() : nullptr;
-        int* d_act = active ? h->d_aact.get() : nullptr;
-        int* d_fl = adj_flags ? h->d_aflags.get() : nullptr;
-        if (!ok(record ? launch_adjoint_record_runtime(d, h->dev, d_in, d_tun, n, d_ws, d_x, d_fm, h->d_status + o, d_it, h->d_axbar,
-                                                       d_fmbar, d_gx0, d_gcfg, d_act, d_fl, grad_in ? h->d_agin.get() : nullptr,
-                                                       grad_model ? h->d_agmodel.get() : nullptr, s)
-                       : launch_adjoint_runtime(d, h->dev, d_in, d_tun, n, d_ws, d_x, d_fm, h->d_status + o, d_it, h->d_axbar,
-                                                d_fmbar, d_gx0, d_gcfg, d_act, d_fl, s)))
-            break;
-        ok(download_results(h, o, N, x, first_move, status, iters, s));
-        if (grad_x0) ok(hipMemcpyAsync(grad_x0 + o * NX, h->d_agx0, N * NX * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (grad_cfg) ok(hipMemcpyAsync(grad_cfg + o * G, h->d_agcfg, N * G * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (active) ok(hipMemcpyAsync(active + o * NV, h->d_aact, N * NV * sizeof(int), hipMemcpyDeviceToHost, s));
-        if (adj_flags) ok(hipMemcpyAsync(adj_flags + o, h->d_aflags, N * sizeof(int), hipMemcpyDeviceToHost, s));
-        if (record && grad_in)
-            ok(hipMemcpyAsync(grad_in + o * h->n_in, h->d_agin, N * h->n_in * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (record && grad_model)
-            ok(hipMemcpyAsync(grad_model + o * GM, h->d_agmodel, N * GM * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    const hipError_t e = hipStreamSynchronize(s);   // nothing returns while copies into the caller's buffers are queued
-    if (err == hipSuccess) err = e;
-    if (err != hipSuccess) return hip_fail(err, record ? "vsmpc_adjoint_record_batch" : "vsmpc_adjoint_batch");
+    RtLaunch a = solve_args(d_in, d_tunables, d_x, d_first_move, d_status, d_iters);
+    a.ws = adjoint_workspace(h);
+    a.xbar = d_xbar; a.fmbar = d_fmbar;
+    a.gx0 = d_grad_x0; a.gcfg = d_grad_cfg; a.active = d_active; a.flags = d_adj_flags;
+    HIP_TRY(launch_runtime(RT_ADJOINT, h->adjoint.dims, h->dev, batch, a, static_cast<hipStream_t>(stream)));
     return VSMPC_OK;
 }
 
@@ -294,31 +300,32 @@ int vsmpc_adjoint_batch(vsmpc_handle* h, const double* in, const double* tunable
                         int batch, double* x, double* first_move, int* status, int* iters, double* grad_x0, double* grad_cfg,
                         int* active, int* adj_flags, void* stream) {
     if (h == nullptr || in == nullptr || xbar == nullptr || status == nullptr || batch < 0) return invalid_arg();
-    if (!h->adjoint) return unsupported(ADJOINT_NEEDS_FLAG);
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
-    return adjoint_batch_host(h, false, in, tunables, xbar, fmbar, batch, x, first_move, status, iters, grad_x0, grad_cfg, active,
-                              adj_flags, nullptr, nullptr, stream);
+    if (const int rc = batch_entry(h, batch, h->adjoint.on, ADJOINT_NEEDS_FLAG); rc != GO) return rc;
+    const vsmpc_handle::Adjoint& k = h->adjoint;
+    RtLaunch a;
+    const StagedRow rows[] = {upload(xbar, k.xbar, a.xbar), upload(fmbar, k.fmbar, a.fmbar), upload(tunables, k.tun, a.tun),
+                              download(grad_x0, k.gx0, a.gx0), download(grad_cfg, k.gcfg, a.gcfg),
+                              download(active, k.active, a.active), download(adj_flags, k.flags, a.flags)};
+    return chunked_host(h, {RT_ADJOINT, k.dims, adjoint_workspace(h), ADJ_CHUNK, "vsmpc_adjoint_batch"},
+                        {in, x, first_move, status, iters}, batch, a, rows, std::size(rows), stream);
 }
 
 // Adjoint of the record (include/vsmpc.h): adjoint_record_kernel_rt[_tuned] on the adjoint entry's workspace and staging,
 // with the staging VSMPC_CREATE_ADJOINT_RECORD allocated for the two further outputs
-static const char* const ADJOINT_RECORD_NEEDS_FLAG =
-    "vsmpc_adjoint_record_batch needs a handle created with VSMPC_CREATE_ADJOINT_RECORD (vsmpc_create_ex)";
-
 int vsmpc_adjoint_record_batch_device(vsmpc_handle* h, const double* d_in, const double* d_tunables, const double* d_xbar,
                                       const double* d_fmbar, int batch, double* d_x, double* d_first_move, int* d_status,
                                       int* d_iters, double* d_grad_x0, double* d_grad_cfg, int* d_active, int* d_adj_flags,
                                       double* d_grad_in, double* d_grad_model, void* stream) {
     if (h == nullptr || d_in == nullptr || d_xbar == nullptr || d_status == nullptr || batch < 0) return invalid_arg();
-    if ((reinterpret_cast<size_t>(d_tunables) & 15) != 0) return invalid_arg();   // the kernel loads 16 bytes per lane
-    if (!h->adjoint_record) return unsupported(ADJOINT_RECORD_NEEDS_FLAG);
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
+    if (misaligned16(d_tunables)) return invalid_arg();
+    if (const int rc = batch_entry(h, batch, h->adjoint_record.on, ADJOINT_RECORD_NEEDS_FLAG); rc != GO) return rc;
     ON_DEVICE(h->device);
-    HIP_TRY(launch_adjoint_record_runtime(h->rtr, h->dev, d_in, d_tunables, batch, adjoint_workspace(h), d_x, d_first_move,
-                                          d_status, d_iters, d_xbar, d_fmbar, d_grad_x0, d_grad_cfg, d_active, d_adj_flags,
-                                          d_grad_in, d_grad_model, static_cast<hipStream_t>(stream)));
+    RtLaunch a = solve_args(d_in, d_tunables, d_x, d_first_move, d_status, d_iters);
+    a.ws = adjoint_workspace(h);
+    a.xbar = d_xbar; a.fmbar = d_fmbar;
+    a.gx0 = d_grad_x0; a.gcfg = d_grad_cfg; a.active = d_active; a.flags = d_adj_flags;
+    a.gin = d_grad_in; a.gmodel = d_grad_model;
+    HIP_TRY(launch_runtime(RT_ADJOINT_REC, h->adjoint_record.dims, h->dev, batch, a, static_cast<hipStream_t>(stream)));
     return VSMPC_OK;
 }
 
@@ -327,11 +334,16 @@ int vsmpc_adjoint_record_batch(vsmpc_handle* h, const double* in, const double* 
                                double* grad_x0, double* grad_cfg, int* active, int* adj_flags, double* grad_in,
                                double* grad_model, void* stream) {
     if (h == nullptr || in == nullptr || xbar == nullptr || status == nullptr || batch < 0) return invalid_arg();
-    if (!h->adjoint_record) return unsupported(ADJOINT_RECORD_NEEDS_FLAG);
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
-    return adjoint_batch_host(h, true, in, tunables, xbar, fmbar, batch, x, first_move, status, iters, grad_x0, grad_cfg, active,
-                              adj_flags, grad_in, grad_model, stream);
+    if (const int rc = batch_entry(h, batch, h->adjoint_record.on, ADJOINT_RECORD_NEEDS_FLAG); rc != GO) return rc;
+    const vsmpc_handle::Adjoint& k = h->adjoint;
+    const vsmpc_handle::AdjointRecord& r = h->adjoint_record;
+    RtLaunch a;
+    const StagedRow rows[] = {upload(xbar, k.xbar, a.xbar), upload(fmbar, k.fmbar, a.fmbar), upload(tunables, k.tun, a.tun),
+                              download(grad_x0, k.gx0, a.gx0), download(grad_cfg, k.gcfg, a.gcfg),
+                              download(active, k.active, a.active), download(adj_flags, k.flags, a.flags),
+                              download(grad_in, r.gin, a.gin), download(grad_model, r.gmodel, a.gmodel)};
+    return chunked_host(h, {RT_ADJOINT_REC, r.dims, adjoint_workspace(h), ADJ_CHUNK, "vsmpc_adjoint_record_batch"},
+                        {in, x, first_move, status, iters}, batch, a, rows, std::size(rows), stream);
 }
 
 // Duals and KKT certificate of given primals: certify_kernel restates the oracle's solve_exact (the duals, OSQP's sign:
@@ -343,8 +355,7 @@ int vsmpc_certify_batch_device(vsmpc_handle* h, const double* d_in, const double
     if (((reinterpret_cast<size_t>(d_in) | reinterpret_cast<size_t>(d_x) | reinterpret_cast<size_t>(d_tunables) |
           reinterpret_cast<size_t>(d_y)) & 15) != 0 || (reinterpret_cast<size_t>(d_cert) & 7) != 0)
         return invalid_arg();
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
+    if (const int rc = batch_entry(h, batch); rc != GO) return rc;
     ON_DEVICE(h->device);
     HIP_TRY(launch_certify(h->rt, h->dev, d_in, d_x, d_tunables, batch, d_y, d_cert, static_cast<hipStream_t>(stream)));
     return VSMPC_OK;
@@ -353,10 +364,10 @@ int vsmpc_certify_batch_device(vsmpc_handle* h, const double* d_in, const double
 int vsmpc_certify_batch(vsmpc_handle* h, const double* in, const double* x, const double* tunables, int batch, double* y,
                         double* cert) {
     if (h == nullptr || in == nullptr || x == nullptr || cert == nullptr || batch < 0) return invalid_arg();
-    if (!h->certify)
-        return unsupported("vsmpc_certify_batch needs a handle created with VSMPC_CREATE_CERTIFY (vsmpc_create_ex)");
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
+    if (const int rc = batch_entry(h, batch, h->certify,
+                                   "vsmpc_certify_batch needs a handle created with VSMPC_CREATE_CERTIFY (vsmpc_create_ex)");
+        rc != GO)
+        return rc;
     ON_DEVICE(h->device);
     const size_t B = size_t(batch);
     HIP_TRY(hipMemcpy(h->d_in, in, B * h->n_in * sizeof(double), hipMemcpyHostToDevice));
@@ -374,8 +385,7 @@ int vsmpc_certify_batch(vsmpc_handle* h, const double* in, const double* x, cons
 int vsmpc_tick(vsmpc_handle* h, const double* kin, double* in, int batch, double* x, double* first_move, int* status,
                int* iters, void* stream) {
     if (h == nullptr || kin == nullptr || in == nullptr || status == nullptr || batch < 0) return invalid_arg();
-    if (batch > h->max_batch) return VSMPC_ERR_BATCH_TOO_LARGE;
-    if (batch == 0) return VSMPC_OK;
+    if (const int rc = batch_entry(h, batch); rc != GO) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     ON_DEVICE(h->device);
     const size_t B = size_t(batch);

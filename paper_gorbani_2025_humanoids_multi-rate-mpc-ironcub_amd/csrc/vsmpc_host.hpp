@@ -41,6 +41,13 @@ struct DevBuf : Owned<T*, dev_free<T>> {   // `n` elements of device memory
     }
     T* get() const { return this->h; }
 };
+// Device staging of one argument of a chunked host-pointer entry: `width` elements per instance, for one chunk of instances.
+// vsmpc_create_ex states the width once; the allocation and every copy take it from here.
+template <typename T>
+struct StageBuf : DevBuf<T> {
+    size_t width = 0;
+    hipError_t alloc(size_t instances, size_t w) { width = w; return DevBuf<T>::alloc(instances * w); }
+};
 
 // Rows first .. first + n - 1 ([..][width]) between a caller's buffer and device staging, on a stream.  A null host pointer
 // is an input or output the caller does not want: nothing is enqueued.  (T comes from the host pointer: a DevBuf converts.)
@@ -86,30 +93,31 @@ struct vsmpc_handle {
     int runtime;     // solve with the runtime-sized kernel (vsmpc_create_ex)
     vsmpc::RtDims rt;               // its sizes; on every handle: the linearise and certify kernels are sized by them too
     vsmpc::DevBuf<double> d_ws;     // its per-instance workspace, max_batch x rt.ws_doubles
-    // VSMPC_CREATE_SENSITIVITY: sizes of sens_kernel_rt, its workspace (max_batch x rts.ws_doubles) and the staging of the
-    // host-pointer entry (SENS_CHUNK instances at a time)
-    int sens;
-    vsmpc::RtDims rts;
-    vsmpc::DevBuf<double> d_sws, d_sdx, d_sdfm;
-    vsmpc::DevBuf<int> d_sact, d_sflags;
+    // What each create flag of the runtime family owns: `on`, the sizes of its kernel (filled on every handle), its workspace
+    // (max_batch x dims.ws_doubles) and the staging of its host-pointer entry, one chunk of instances at a time.
+    struct RtOwned { int on; vsmpc::RtDims dims; vsmpc::DevBuf<double> ws; };
+    // VSMPC_CREATE_SENSITIVITY: sens_kernel_rt; the outputs of SENS_CHUNK instances
+    struct Sens : RtOwned {
+        vsmpc::StageBuf<double> dx, dfm;
+        vsmpc::StageBuf<int> active, flags;
+    } sens;
+    // VSMPC_CREATE_ADJOINT: adjoint_kernel_rt[_tuned]; `ws` where the handle is not a runtime one (there d_ws serves); the
+    // cotangents, the rows of tunables and the outputs of ADJ_CHUNK instances
+    struct Adjoint : RtOwned {
+        vsmpc::StageBuf<double> xbar, fmbar, tun, gx0, gcfg;
+        vsmpc::StageBuf<int> active, flags;
+    } adjoint;
+    // VSMPC_CREATE_ADJOINT_RECORD (implies `adjoint`, whose workspace and staging serve; `ws` stays empty):
+    // adjoint_record_kernel_rt[_tuned]; its two further outputs of ADJ_CHUNK instances
+    struct AdjointRecord : RtOwned {
+        vsmpc::StageBuf<double> gin, gmodel;
+    } adjoint_record;
     // VSMPC_CREATE_TUNABLES: device staging of the rows of vsmpc_solve_batch_tuned, max_batch x VSMPC_TUNE_SIZE
     int tunables;
     vsmpc::DevBuf<double> d_tun;
     // VSMPC_CREATE_CERTIFY: device staging of vsmpc_certify_batch for max_batch instances: x, y | certificate, tunables
     int certify;
     vsmpc::DevBuf<double> d_cx, d_cy, d_ccert, d_ctun;
-    // VSMPC_CREATE_ADJOINT: sizes of adjoint_kernel_rt, its workspace where the handle is not a runtime one (max_batch x
-    // rta.ws_doubles; a runtime handle's d_ws serves) and the staging of the host-pointer entry: the cotangents, the rows and
-    // the outputs of ADJ_CHUNK instances at a time
-    int adjoint;
-    vsmpc::RtDims rta;
-    vsmpc::DevBuf<double> d_aws, d_axbar, d_afmbar, d_atun, d_agx0, d_agcfg;
-    vsmpc::DevBuf<int> d_aact, d_aflags;
-    // VSMPC_CREATE_ADJOINT_RECORD (implies `adjoint`): sizes of adjoint_record_kernel_rt (rta's workspace serves) and the
-    // staging of its two outputs, ADJ_CHUNK instances at a time
-    int adjoint_record;
-    vsmpc::RtDims rtr;
-    vsmpc::DevBuf<double> d_agin, d_agmodel;
     int form;       // condensing form of the solve kernel (vsmpc_set_kernel_form)
     int small_mode; // which kernel serves small batches (vsmpc_set_small_batch_kernel): 0 auto, 1 never, 2 always
     int cu_count;   // compute units of `device` (read once, at create): auto takes the small-batch kind up to this batch

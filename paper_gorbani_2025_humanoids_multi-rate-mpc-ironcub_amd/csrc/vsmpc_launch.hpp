@@ -108,33 +108,35 @@ size_t runtime_lds_bytes(const RtDims& d);
 // the same with the staged row of the per-instance-tunables kinds behind it (solve_kernel_rt_tuned, adjoint_kernel_rt_tuned)
 size_t runtime_tuned_lds_bytes(const RtDims& d);
 const char* runtime_kernel_name();
-// d_ws: workspace of the launch's first instance (instance b of the launch uses d_ws + b * d.ws_doubles)
-hipError_t launch_solve_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws, double* d_x,
-                                double* d_fm, int* d_status, int* d_iters, hipStream_t stream);
-// sens_kernel_rt (vsmpc_sensitivity_batch): the solve outputs plus dx_dx0 [batch][nVar][26], dfm_dx0 [batch][24][26],
-// active [batch][NV] and the VSMPC_SENS_* flags [batch]; d from runtime_dims(.., true), d_ws as for the solve
-// solve_kernel_rt_tuned: the same body with every tunable read from the instance's row of d_tun
-hipError_t launch_solve_runtime_tuned(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
-                                      double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters,
-                                      hipStream_t stream);
-hipError_t launch_sensitivity_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws,
-                                      double* d_x, double* d_fm, int* d_status, int* d_iters, double* d_dx, double* d_dfm,
-                                      int* d_active, int* d_flags, hipStream_t stream);
-// adjoint_kernel_rt (d_tun == nullptr: the handle's configuration) or adjoint_kernel_rt_tuned (rows of per-instance tunables,
-// 16-byte aligned): the solve outputs plus, for the cotangents d_xbar [batch][nVar] and d_fmbar [batch][24] (or nullptr),
-// dL/dX0 [batch][26], dL/dcfg [batch][VSMPC_GRAD_SIZE], active [batch][NV] and the VSMPC_ADJ_* flags [batch] (each may be
-// nullptr); d from runtime_dims(.., false, true), d_ws as for the solve
-hipError_t launch_adjoint_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
-                                  double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters, const double* d_xbar,
-                                  const double* d_fmbar, double* d_gx0, double* d_gcfg, int* d_active, int* d_flags,
-                                  hipStream_t stream);
-// adjoint_record_kernel_rt[_tuned] (vsmpc_adjoint_record_batch): launch_adjoint_runtime's arguments and outputs plus dL/d record
-// [batch][n_in] and dL/d(A | Bj | Bt | c) [batch][VSMPC_GRAD_MODEL_SIZE] (each may be nullptr); d from
-// runtime_dims(.., false, true, true)
-hipError_t launch_adjoint_record_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
-                                         double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters,
-                                         const double* d_xbar, const double* d_fmbar, double* d_gx0, double* d_gcfg,
-                                         int* d_active, int* d_flags, double* d_gin, double* d_gmodel, hipStream_t stream);
+// The kinds of the runtime-sized kernel (the instantiations of rt_solve) and their C entries:
+enum RtMode {
+    RT_SOLVE,        // solve_kernel_rt[_tuned]: vsmpc_solve_batch[_tuned] on a runtime handle; d from runtime_dims(..)
+    RT_SENS,         // sens_kernel_rt: vsmpc_sensitivity_batch; d from runtime_dims(.., true); no tuned kind
+    RT_ADJOINT,      // adjoint_kernel_rt[_tuned]: vsmpc_adjoint_batch; d from runtime_dims(.., false, true)
+    RT_ADJOINT_REC   // adjoint_record_kernel_rt[_tuned]: vsmpc_adjoint_record_batch; d from runtime_dims(.., false, true, true)
+};
+// Every pointer of one launch, by name (device memory, one row per instance of the launch).  A caller sets what its kind
+// reads and what it wants written; of the outputs only `status` is required, and a kind ignores the fields of the others.
+struct RtLaunch {
+    const double* in = nullptr;    // records [n_in]
+    const double* tun = nullptr;   // rows of per-instance tunables [VSMPC_TUNE_SIZE], 16-byte aligned: the kind's tuned kernel
+                                   // runs; nullptr: the handle's configuration for every instance
+    double* ws = nullptr;          // workspace of the launch's first instance (instance b uses ws + b * d.ws_doubles)
+    double *x = nullptr, *fm = nullptr;           // primal [nVar], first move [24]
+    int *status = nullptr, *iters = nullptr;
+    // every kind but RT_SOLVE: final throttle states [NV] and the VSMPC_SENS_* / VSMPC_ADJ_* flags
+    int *active = nullptr, *flags = nullptr;
+    // RT_SENS: dx_dx0 [nVar][26], dfm_dx0 [24][26]
+    double *dx = nullptr, *dfm = nullptr;
+    // RT_ADJOINT, RT_ADJOINT_REC: the cotangents [nVar] (required) and [24] in, dL/dX0 [26] and dL/dcfg [VSMPC_GRAD_SIZE] out
+    const double *xbar = nullptr, *fmbar = nullptr;
+    double *gx0 = nullptr, *gcfg = nullptr;
+    // RT_ADJOINT_REC: dL/d record [n_in], dL/d(A | Bj | Bt | c) [VSMPC_GRAD_MODEL_SIZE]
+    double *gin = nullptr, *gmodel = nullptr;
+};
+// launches the kernel of `kind` (its tuned one when a.tun is given) over `batch` instances; hipErrorInvalidValue when `d`
+// is not the kind's runtime_dims, or the kind has no tuned kernel
+hipError_t launch_runtime(RtMode kind, const RtDims& d, const DevCfg& cfg, int batch, const RtLaunch& a, hipStream_t stream);
 // linearize_kernel_rt (vsmpc_linearize_batch, on every handle): p0_linearize alone
 hipError_t launch_linearize_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,
                                     double* Bt, double* c, hipStream_t stream);

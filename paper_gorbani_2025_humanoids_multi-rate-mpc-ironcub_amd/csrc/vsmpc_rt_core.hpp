@@ -41,7 +41,6 @@ constexpr int RT_BLOCK = 256;
 constexpr int RT_CPT = 2;    // columns per thread: NP <= 8 * 40 + 4 * 39 + 1 = 477 (+ 26 parameter columns: 503) < 512
 constexpr int RT_NPAR = NX;  // parameter columns of sens_kernel_rt: one per entry of X0
 constexpr int RT_NWAVES = RT_BLOCK / 64;
-enum RtMode { RT_SOLVE, RT_SENS, RT_ADJOINT, RT_ADJOINT_REC };   // the instantiations of rt_solve
 enum { F_STATUS = 0, F_ITERS, F_NF, F_BEST, F_PATIENCE };   // LDS flag slots
 
 VS_DEV size_t tri(int i) { return size_t(i) * size_t(i + 1) / 2; }

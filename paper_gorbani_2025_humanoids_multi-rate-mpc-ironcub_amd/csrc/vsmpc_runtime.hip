@@ -10,13 +10,16 @@
 //   vsmpc_rt_adjoint.hpp  the five extra phases of adjoint_kernel_rt[_tuned] (vsmpc_adjoint_batch): rt_solve<RT_ADJOINT>
 //   vsmpc_rt_adjoint_record.hpp  the two phases adjoint_record_kernel_rt[_tuned] (vsmpc_adjoint_record_batch) add to those:
 //                         rt_solve<RT_ADJOINT_REC>
-//   this file             RtTunCfg and its staging, rt_solve, the kernels, runtime_dims and the launchers
+//   this file             RtTunCfg and its staging, rt_solve, the kernels, runtime_dims and launch_runtime: the one launcher
+//                         of the family, which picks the kernel from an RtMode and unpacks an RtLaunch (vsmpc_launch.hpp:
+//                         every pointer of a launch by name) into the kernel's positional arguments
 //
 // The phases that read the configuration take its type as a template parameter: DevCfg, the kernel argument
 // (solve_kernel_rt, sens_kernel_rt), or RtTunCfg, the instance's row of tunables staged in LDS (solve_kernel_rt_tuned,
 // vsmpc_solve_batch_tuned).
 #include <atomic>
 #include <cstddef>
+#include <type_traits>
 
 #include "vsmpc_rt_core.hpp"
 #include "vsmpc_rt_sens.hpp"
@@ -79,6 +82,7 @@ VS_DEV void rt_solve(const Cfg& cfg, const RtDims& d, const double* in, double* 
 
 }  // namespace
 
+// Positional __restrict__ pointers are the kernels' ABI: in by-value structs they lose alias analysis (+86..131 instructions, measured)
 __global__ __launch_bounds__(RT_BLOCK) void solve_kernel_rt(DevCfg cfg, RtDims d, const double* __restrict__ in,
                                                             double* __restrict__ ws, double* __restrict__ xout,
                                                             double* __restrict__ fmout, int* __restrict__ status_out,
@@ -263,53 +267,41 @@ hipError_t rt_launch(size_t lds, int batch, hipStream_t stream, Args... args) {
     return hipGetLastError();
 }
 
-hipError_t launch_solve_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws, double* d_x,
-                                double* d_fm, int* d_status, int* d_iters, hipStream_t stream) {
-    return rt_launch<solve_kernel_rt>(runtime_lds_bytes(d), batch, stream, cfg, d, d_in, d_ws, d_x, d_fm, d_status, d_iters);
+// One kind of the family: Kernel, or Tuned (nullptr: the kind has none) when the launch carries rows of tunables.  Here, and
+// nowhere else, an RtLaunch becomes positional arguments: the eight every kernel begins with, the kind's own (`more`, in
+// the order of its kernel's signature), and the rows last.  The staged row of the tuned kernel lies behind the body's
+// carve-up (the largest valid horizon needs 129 KB).
+template <auto Kernel, auto Tuned, class... More>
+hipError_t rt_launch_kind(const RtDims& d, const DevCfg& cfg, int batch, const RtLaunch& a, hipStream_t stream, More... more) {
+    if (a.tun == nullptr)
+        return rt_launch<Kernel>(runtime_lds_bytes(d), batch, stream, cfg, d, a.in, a.ws, a.x, a.fm, a.status, a.iters, more...);
+    if constexpr (!std::is_null_pointer_v<decltype(Tuned)>)
+        return rt_launch<Tuned>(runtime_tuned_lds_bytes(d), batch, stream, cfg, d, a.in, a.ws, a.x, a.fm, a.status, a.iters,
+                                more..., a.tun);
+    else
+        return hipErrorInvalidValue;
 }
 
-hipError_t launch_solve_runtime_tuned(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
-                                      double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters,
-                                      hipStream_t stream) {
-    // the staged row lies behind the body's carve-up (the largest valid horizon needs 129 KB)
-    return rt_launch<solve_kernel_rt_tuned>(runtime_tuned_lds_bytes(d), batch, stream, cfg, d, d_in, d_ws, d_x, d_fm, d_status,
-                                            d_iters, d_tun);
-}
-
-hipError_t launch_sensitivity_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* d_ws,
-                                      double* d_x, double* d_fm, int* d_status, int* d_iters, double* d_dx, double* d_dfm,
-                                      int* d_active, int* d_flags, hipStream_t stream) {
-    if (d.np != d.nz + 1 + RT_NPAR || d.np > RT_BLOCK * RT_CPT) return hipErrorInvalidValue;   // runtime_dims(.., true)
-    return rt_launch<sens_kernel_rt>(runtime_lds_bytes(d), batch, stream, cfg, d, d_in, d_ws, d_x, d_fm, d_status, d_iters, d_dx,
-                                     d_dfm, d_active, d_flags);
-}
-
-hipError_t launch_adjoint_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
-                                  double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters, const double* d_xbar,
-                                  const double* d_fmbar, double* d_gx0, double* d_gcfg, int* d_active, int* d_flags,
-                                  hipStream_t stream) {
+hipError_t launch_runtime(RtMode kind, const RtDims& d, const DevCfg& cfg, int batch, const RtLaunch& a, hipStream_t stream) {
     static_assert(VSMPC_GRAD_SIZE * RT_NWAVES <= RT_BLOCK && 2 * NX + RT_NWAVES <= RT_BLOCK, "s.red holds the partial sums and lambda");
-    if (d.np != d.nz + 1) return hipErrorInvalidValue;                                    // runtime_dims(.., false, true)
-    if (d_tun != nullptr)
-        return rt_launch<adjoint_kernel_rt_tuned>(runtime_tuned_lds_bytes(d), batch, stream, cfg, d, d_in, d_ws, d_x, d_fm,
-                                                  d_status, d_iters, d_xbar, d_fmbar, d_gx0, d_gcfg, d_active, d_flags, d_tun);
-    return rt_launch<adjoint_kernel_rt>(runtime_lds_bytes(d), batch, stream, cfg, d, d_in, d_ws, d_x, d_fm, d_status, d_iters,
-                                        d_xbar, d_fmbar, d_gx0, d_gcfg, d_active, d_flags);
-}
-
-hipError_t launch_adjoint_record_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, const double* d_tun, int batch,
-                                         double* d_ws, double* d_x, double* d_fm, int* d_status, int* d_iters,
-                                         const double* d_xbar, const double* d_fmbar, double* d_gx0, double* d_gcfg,
-                                         int* d_active, int* d_flags, double* d_gin, double* d_gmodel, hipStream_t stream) {
     static_assert(2 * NX <= RT_BLOCK, "s.red holds nu_k and nu_{k-1}");
-    // runtime_dims(.., false, true, true): s.big holds G behind a_X and the costates
-    if (d.np != d.nz + 1 || d.lds_doubles < int(rt_carve(d, size_t(0)).big) + rt_big_adjoint_record(d)) return hipErrorInvalidValue;
-    if (d_tun != nullptr)
-        return rt_launch<adjoint_record_kernel_rt_tuned>(runtime_tuned_lds_bytes(d), batch, stream, cfg, d, d_in, d_ws, d_x, d_fm,
-                                                         d_status, d_iters, d_xbar, d_fmbar, d_gx0, d_gcfg, d_active, d_flags,
-                                                         d_gin, d_gmodel, d_tun);
-    return rt_launch<adjoint_record_kernel_rt>(runtime_lds_bytes(d), batch, stream, cfg, d, d_in, d_ws, d_x, d_fm, d_status,
-                                               d_iters, d_xbar, d_fmbar, d_gx0, d_gcfg, d_active, d_flags, d_gin, d_gmodel);
+    switch (kind) {
+        case RT_SOLVE:
+            return rt_launch_kind<solve_kernel_rt, solve_kernel_rt_tuned>(d, cfg, batch, a, stream);
+        case RT_SENS:
+            if (d.np != d.nz + 1 + RT_NPAR || d.np > RT_BLOCK * RT_CPT) return hipErrorInvalidValue;   // runtime_dims(.., true)
+            return rt_launch_kind<sens_kernel_rt, nullptr>(d, cfg, batch, a, stream, a.dx, a.dfm, a.active, a.flags);
+        case RT_ADJOINT:
+            if (d.np != d.nz + 1) return hipErrorInvalidValue;                                    // runtime_dims(.., false, true)
+            return rt_launch_kind<adjoint_kernel_rt, adjoint_kernel_rt_tuned>(d, cfg, batch, a, stream, a.xbar, a.fmbar, a.gx0,
+                                                                              a.gcfg, a.active, a.flags);
+        case RT_ADJOINT_REC:
+            // runtime_dims(.., false, true, true): s.big holds G behind a_X and the costates
+            if (d.np != d.nz + 1 || d.lds_doubles < int(rt_carve(d, size_t(0)).big) + rt_big_adjoint_record(d)) return hipErrorInvalidValue;
+            return rt_launch_kind<adjoint_record_kernel_rt, adjoint_record_kernel_rt_tuned>(
+                d, cfg, batch, a, stream, a.xbar, a.fmbar, a.gx0, a.gcfg, a.active, a.flags, a.gin, a.gmodel);
+    }
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_linearize_runtime(const RtDims& d, const DevCfg& cfg, const double* d_in, int batch, double* A, double* Bj,

@@ -24,6 +24,25 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _dptr(t):
+    """the device pointer of a torch tensor, or NULL for None"""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _stream(t, stream):
+    """the stream argument of a device entry: `stream`, or torch's current stream on the device of `t`"""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream(t.device)
+    return ctypes.c_void_p(s.cuda_stream)
+
+
+def _assert_f64_device(*tensors):
+    """the inputs of a device entry: contiguous float64 CUDA tensors (None: an optional one that is not given)"""
+    import torch
+    for t in tensors:
+        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+
+
 KERNEL_FORM_AUTO, KERNEL_FORM_STRUCTURED, KERNEL_FORM_SYRK = 0, 1, 2
 # columns of the certificate of BatchedVSMPC.certify (VSMPC_CERT_* in include/vsmpc.h)
 CERT_STATIONARITY, CERT_STAT_SCALE, CERT_PRIMAL = L.CERT_STATIONARITY, L.CERT_STAT_SCALE, L.CERT_PRIMAL
@@ -142,25 +161,38 @@ class BatchedVSMPC:
         """True when this handle solves with the runtime-sized kernel instead of a tuned per-horizon instantiation."""
         return self.kernel_name == L.RUNTIME_KERNEL_NAME
 
+    def _records(self, a, name: str) -> np.ndarray:
+        """`a` as the contiguous float64 records [batch, n_in] that the host entries take"""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != self.n_in:
+            raise ValueError(f"{name} must be [batch, {self.n_in}]")
+        return a
+
+    def _rows(self, B: int, configs, tunables):
+        """the rows of per-instance tunables [B, L.TUNE_SIZE]: of `configs` (through pack_tunables) or `tunables` (packed
+        already); None when neither is given"""
+        if configs is None and tunables is None:
+            return None
+        if configs is not None and tunables is not None:
+            raise ValueError("give configs or tunables, not both")
+        rows = pack_tunables(self, configs) if configs is not None else np.ascontiguousarray(tunables, dtype=np.float64)
+        if rows.shape != (B, L.TUNE_SIZE):
+            raise ValueError(f"one configuration / one row of {L.TUNE_SIZE} tunables per instance ({B})")
+        return rows
+
     # ---- host-buffer entry (vsmpc_solve_batch)
     def solve(self, inputs: np.ndarray, configs=None, tunables=None):
         """vsmpc_solve_batch; with `configs` (one MPCConfig per instance) or `tunables` (their packed rows, pack_tunables)
         vsmpc_solve_batch_tuned: instance i is solved under its own weights and throttle box (needs tunables=True at
         construction)."""
-        inputs = np.ascontiguousarray(inputs, dtype=np.float64)
-        if inputs.ndim != 2 or inputs.shape[1] != self.n_in:
-            raise ValueError(f"inputs must be [batch, {self.n_in}]")
+        inputs = self._records(inputs, "inputs")
         B = inputs.shape[0]
         x = np.empty((B, self.n_var))
         fm = np.empty((B, L.FM_SIZE))
         status = np.empty(B, dtype=np.int32)
         iters = np.empty(B, dtype=np.int32)
-        if configs is not None or tunables is not None:
-            if configs is not None and tunables is not None:
-                raise ValueError("give configs or tunables, not both")
-            rows = pack_tunables(self, configs) if configs is not None else np.ascontiguousarray(tunables, dtype=np.float64)
-            if rows.shape != (B, L.TUNE_SIZE):
-                raise ValueError(f"one configuration / one row of {L.TUNE_SIZE} tunables per instance ({B})")
+        rows = self._rows(B, configs, tunables)
+        if rows is not None:
             _lib.check(self.lib.vsmpc_solve_batch_tuned(self._h, _ptr(inputs), _ptr(rows), B, _ptr(x), _ptr(fm), _ptr(status),
                                                         _ptr(iters), None), "vsmpc_solve_batch_tuned")
             return x, fm, status, iters
@@ -170,34 +202,20 @@ class BatchedVSMPC:
 
     # ---- device-resident entry (vsmpc_solve_batch_device); arguments are torch CUDA tensors
     def solve_device(self, d_in, d_x, d_fm, d_status, d_iters, stream=None):
-        import torch
-        assert d_in.is_cuda and d_in.dtype == torch.float64 and d_in.is_contiguous()
-        B = d_in.shape[0]
-        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
+        _assert_f64_device(d_in)
         _lib.check(self.lib.vsmpc_solve_batch_device(
-            self._h, ctypes.c_void_p(d_in.data_ptr()), B,
-            ctypes.c_void_p(d_x.data_ptr()) if d_x is not None else None,
-            ctypes.c_void_p(d_fm.data_ptr()) if d_fm is not None else None,
-            ctypes.c_void_p(d_status.data_ptr()),
-            ctypes.c_void_p(d_iters.data_ptr()) if d_iters is not None else None,
-            ctypes.c_void_p(s.cuda_stream)), "vsmpc_solve_batch_device")
+            self._h, _dptr(d_in), d_in.shape[0], _dptr(d_x), _dptr(d_fm), _dptr(d_status), _dptr(d_iters),
+            _stream(d_in, stream)), "vsmpc_solve_batch_device")
 
     def solve_device_tuned(self, d_in, d_tun, d_x, d_fm, d_status, d_iters, stream=None):
         """vsmpc_solve_batch_tuned_device: solve_device with d_tun [batch, L.TUNE_SIZE], the rows of pack_tunables on the
         device (needs no construction flag)"""
-        import torch
-        assert d_in.is_cuda and d_in.dtype == torch.float64 and d_in.is_contiguous()
-        assert d_tun.is_cuda and d_tun.dtype == torch.float64 and d_tun.is_contiguous()
+        _assert_f64_device(d_in, d_tun)
         B = d_in.shape[0]
         assert tuple(d_tun.shape) == (B, L.TUNE_SIZE)
-        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
         _lib.check(self.lib.vsmpc_solve_batch_tuned_device(
-            self._h, ctypes.c_void_p(d_in.data_ptr()), ctypes.c_void_p(d_tun.data_ptr()), B,
-            ctypes.c_void_p(d_x.data_ptr()) if d_x is not None else None,
-            ctypes.c_void_p(d_fm.data_ptr()) if d_fm is not None else None,
-            ctypes.c_void_p(d_status.data_ptr()),
-            ctypes.c_void_p(d_iters.data_ptr()) if d_iters is not None else None,
-            ctypes.c_void_p(s.cuda_stream)), "vsmpc_solve_batch_tuned_device")
+            self._h, _dptr(d_in), _dptr(d_tun), B, _dptr(d_x), _dptr(d_fm), _dptr(d_status), _dptr(d_iters),
+            _stream(d_in, stream)), "vsmpc_solve_batch_tuned_device")
 
     # ---- duals and KKT certificate of given primals (vsmpc_certify_batch); needs certify=True at construction
     def certify(self, records: np.ndarray, x: np.ndarray, configs=None, tunables=None, duals: bool = True):
@@ -206,20 +224,12 @@ class BatchedVSMPC:
         usually solve()'s, but any x is judged.  With `configs` (one MPCConfig per instance, through pack_tunables) or
         `tunables` (their packed rows) instance i is certified under its own weights and throttle box.  duals=False: y is
         not wanted (returned as None)."""
-        records = np.ascontiguousarray(records, dtype=np.float64)
         x = np.ascontiguousarray(x, dtype=np.float64)
-        if records.ndim != 2 or records.shape[1] != self.n_in:
-            raise ValueError(f"records must be [batch, {self.n_in}]")
+        records = self._records(records, "records")
         B = records.shape[0]
         if x.shape != (B, self.n_var):
             raise ValueError(f"x must be [{B}, {self.n_var}]")
-        rows = None
-        if configs is not None or tunables is not None:
-            if configs is not None and tunables is not None:
-                raise ValueError("give configs or tunables, not both")
-            rows = pack_tunables(self, configs) if configs is not None else np.ascontiguousarray(tunables, dtype=np.float64)
-            if rows.shape != (B, L.TUNE_SIZE):
-                raise ValueError(f"one configuration / one row of {L.TUNE_SIZE} tunables per instance ({B})")
+        rows = self._rows(B, configs, tunables)
         y = np.empty((B, self.n_con)) if duals else None
         cert = np.empty((B, L.CERT_SIZE))
         _lib.check(self.lib.vsmpc_certify_batch(self._h, _ptr(records), _ptr(x), _ptr(rows), B, _ptr(y), _ptr(cert)),
@@ -229,23 +239,15 @@ class BatchedVSMPC:
     def certify_device(self, d_in, d_x, d_tun, d_y, d_cert, stream=None):
         """vsmpc_certify_batch_device: torch CUDA tensors (d_tun and d_y may be None), enqueue only; needs no
         construction flag"""
-        import torch
-        for t in (d_in, d_x, d_tun, d_y, d_cert):
-            assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
-        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
-
-        def p(t):
-            return None if t is None else ctypes.c_void_p(t.data_ptr())
-        _lib.check(self.lib.vsmpc_certify_batch_device(self._h, p(d_in), p(d_x), p(d_tun), d_in.shape[0], p(d_y), p(d_cert),
-                                                       ctypes.c_void_p(s.cuda_stream)), "vsmpc_certify_batch_device")
+        _assert_f64_device(d_in, d_x, d_tun, d_y, d_cert)
+        _lib.check(self.lib.vsmpc_certify_batch_device(self._h, _dptr(d_in), _dptr(d_x), _dptr(d_tun), d_in.shape[0], _dptr(d_y),
+                                                       _dptr(d_cert), _stream(d_in, stream)), "vsmpc_certify_batch_device")
 
     # ---- sensitivities of the solution to X0 (vsmpc_sensitivity_batch); needs sensitivity=True at construction
     def solve_sensitivity(self, inputs: np.ndarray, jacobian: bool = True) -> dict:
         """x, first_move, status, iters as solve(); dx_dx0 [B, n_var, 26] (only when `jacobian`) and dfm_dx0 [B, 24, 26]:
         d x / d X0 and d first_move / d X0; active [B, n_v]: final throttle states (L.ACTIVE_*); flags [B]: L.SENS_*."""
-        inputs = np.ascontiguousarray(inputs, dtype=np.float64)
-        if inputs.ndim != 2 or inputs.shape[1] != self.n_in:
-            raise ValueError(f"inputs must be [batch, {self.n_in}]")
+        inputs = self._records(inputs, "inputs")
         B, J = inputs.shape[0], L.N_STATES
         out = {"x": np.empty((B, self.n_var)), "first_move": np.empty((B, L.FM_SIZE)),
                "status": np.empty(B, dtype=np.int32), "iters": np.empty(B, dtype=np.int32),
@@ -261,15 +263,11 @@ class BatchedVSMPC:
 
     def solve_sensitivity_device(self, d_in, d_x, d_fm, d_status, d_iters, d_dx, d_dfm, d_active, d_flags, stream=None):
         """vsmpc_sensitivity_batch_device: torch CUDA tensors (every output but d_status may be None), enqueue only"""
-        import torch
-        assert d_in.is_cuda and d_in.dtype == torch.float64 and d_in.is_contiguous()
-        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
-
-        def p(t):
-            return None if t is None else ctypes.c_void_p(t.data_ptr())
+        _assert_f64_device(d_in)
+        p = _dptr
         _lib.check(self.lib.vsmpc_sensitivity_batch_device(
             self._h, p(d_in), d_in.shape[0], p(d_x), p(d_fm), p(d_status), p(d_iters), p(d_dx), p(d_dfm), p(d_active),
-            p(d_flags), ctypes.c_void_p(s.cuda_stream)), "vsmpc_sensitivity_batch_device")
+            p(d_flags), _stream(d_in, stream)), "vsmpc_sensitivity_batch_device")
 
     # ---- adjoint of the solve (vsmpc_adjoint_batch); needs adjoint=True at construction
     def solve_adjoint(self, records: np.ndarray, xbar: np.ndarray, fmbar=None, configs=None, tunables=None) -> dict:
@@ -290,9 +288,7 @@ class BatchedVSMPC:
         return self._solve_adjoint(True, records, xbar, fmbar, configs, tunables)
 
     def _solve_adjoint(self, record: bool, records, xbar, fmbar, configs, tunables) -> dict:
-        records = np.ascontiguousarray(records, dtype=np.float64)
-        if records.ndim != 2 or records.shape[1] != self.n_in:
-            raise ValueError(f"records must be [batch, {self.n_in}]")
+        records = self._records(records, "records")
         B = records.shape[0]
         xbar = np.ascontiguousarray(xbar, dtype=np.float64)
         if xbar.shape != (B, self.n_var):
@@ -301,13 +297,7 @@ class BatchedVSMPC:
             fmbar = np.ascontiguousarray(fmbar, dtype=np.float64)
             if fmbar.shape != (B, L.FM_SIZE):
                 raise ValueError(f"fmbar must be [{B}, {L.FM_SIZE}]")
-        rows = None
-        if configs is not None or tunables is not None:
-            if configs is not None and tunables is not None:
-                raise ValueError("give configs or tunables, not both")
-            rows = pack_tunables(self, configs) if configs is not None else np.ascontiguousarray(tunables, dtype=np.float64)
-            if rows.shape != (B, L.TUNE_SIZE):
-                raise ValueError(f"one configuration / one row of {L.TUNE_SIZE} tunables per instance ({B})")
+        rows = self._rows(B, configs, tunables)
         out = {"x": np.empty((B, self.n_var)), "first_move": np.empty((B, L.FM_SIZE)),
                "status": np.empty(B, dtype=np.int32), "iters": np.empty(B, dtype=np.int32),
                "grad_x0": np.empty((B, L.N_STATES)), "grad_cfg": np.empty((B, L.GRAD_SIZE)),
@@ -327,33 +317,23 @@ class BatchedVSMPC:
                              d_active, d_flags, stream=None):
         """vsmpc_adjoint_batch_device: torch CUDA tensors (d_tun, d_fmbar and every output but d_status may be None),
         enqueue only"""
-        import torch
-        for t in (d_in, d_tun, d_xbar, d_fmbar):
-            assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
-        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
-
-        def p(t):
-            return None if t is None else ctypes.c_void_p(t.data_ptr())
-        _lib.check(self.lib.vsmpc_adjoint_batch_device(
-            self._h, p(d_in), p(d_tun), p(d_xbar), p(d_fmbar), d_in.shape[0], p(d_x), p(d_fm), p(d_status), p(d_iters),
-            p(d_grad_x0), p(d_grad_cfg), p(d_active), p(d_flags), ctypes.c_void_p(s.cuda_stream)),
-            "vsmpc_adjoint_batch_device")
+        self._adjoint_device("vsmpc_adjoint_batch_device", (d_in, d_tun, d_xbar, d_fmbar),
+                             (d_x, d_fm, d_status, d_iters, d_grad_x0, d_grad_cfg, d_active, d_flags), stream)
 
     def solve_adjoint_record_device(self, d_in, d_tun, d_xbar, d_fmbar, d_x, d_fm, d_status, d_iters, d_grad_x0, d_grad_cfg,
                                     d_active, d_flags, d_grad_in, d_grad_model, stream=None):
         """vsmpc_adjoint_record_batch_device: solve_adjoint_device's arguments and d_grad_in [B, n_in], d_grad_model
         [B, L.GRAD_MODEL_SIZE] (each may be None), enqueue only"""
-        import torch
-        for t in (d_in, d_tun, d_xbar, d_fmbar):
-            assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
-        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
+        self._adjoint_device("vsmpc_adjoint_record_batch_device", (d_in, d_tun, d_xbar, d_fmbar),
+                             (d_x, d_fm, d_status, d_iters, d_grad_x0, d_grad_cfg, d_active, d_flags, d_grad_in, d_grad_model),
+                             stream)
 
-        def p(t):
-            return None if t is None else ctypes.c_void_p(t.data_ptr())
-        _lib.check(self.lib.vsmpc_adjoint_record_batch_device(
-            self._h, p(d_in), p(d_tun), p(d_xbar), p(d_fmbar), d_in.shape[0], p(d_x), p(d_fm), p(d_status), p(d_iters),
-            p(d_grad_x0), p(d_grad_cfg), p(d_active), p(d_flags), p(d_grad_in), p(d_grad_model),
-            ctypes.c_void_p(s.cuda_stream)), "vsmpc_adjoint_record_batch_device")
+    def _adjoint_device(self, entry: str, inputs, outputs, stream):
+        """inputs = (d_in, d_tun, d_xbar, d_fmbar), then the batch, `outputs` in the entry's order and the stream"""
+        _assert_f64_device(*inputs)
+        d_in = inputs[0]
+        _lib.check(getattr(self.lib, entry)(self._h, *[_dptr(t) for t in inputs], d_in.shape[0], *[_dptr(t) for t in outputs],
+                                            _stream(d_in, stream)), entry)
 
     def timing_begin(self, stream):
         _lib.check(self.lib.vsmpc_timing_begin(self._h, ctypes.c_void_p(stream.cuda_stream)), "vsmpc_timing_begin")

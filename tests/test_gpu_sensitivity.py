@@ -152,6 +152,39 @@ def test_degeneracy_flag(solver_mod, synth, layout):
     assert relerr(out2["x"][0], out["x"][0]) < 1e-9
 
 
+@pytest.mark.parametrize("jacobian", [True, False])
+def test_host_entry_over_two_chunks_equals_the_device_entry(solver_mod, synth, layout, jacobian):
+    """257 instances at (2, 2, 2): one chunk of the host entry (256) and a second of a single instance, against one launch
+    of the device entry -- the same kernel, so every output is equal bit for bit (NaN == NaN).  Hover and take-off records,
+    one held tick and one with a NaN in X0 among them, both in the first chunk."""
+    import torch
+    cfg = layout.MPCConfig(n_iter=2, n_iter_small=2, control_horizon=2)
+    B = 257
+    recs = np.concatenate([synth.make_batch(cfg, 129, workload="hover", first_index=3),
+                           synth.make_batch(cfg, 128, workload="takeoff", first_index=3)])
+    recs[70, layout.IN_HOLD] = 1.0
+    recs[200, layout.IN_X0 + 4] = np.nan
+    dev = torch.device("cuda:0")
+    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)
+    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
+    m = solver_mod.BatchedVSMPC(cfg, device=0, max_batch=B, runtime="always", sensitivity=True)
+    try:
+        whole = m.solve_sensitivity(recs, jacobian=jacobian)
+        t = {"x": f64(B, m.n_var), "first_move": f64(B, 24), "status": i32(B), "iters": i32(B),
+             "dx_dx0": f64(B, m.n_var, 26) if jacobian else None, "dfm_dx0": f64(B, 24, 26), "active": i32(B, m.n_v),
+             "flags": i32(B)}
+        m.solve_sensitivity_device(torch.from_numpy(recs).to(dev), *t.values())
+        torch.cuda.synchronize()
+        got = {k: v.cpu().numpy() for k, v in t.items() if v is not None}
+    finally:
+        m.close()
+    assert (np.delete(whole["status"], 200) == layout.STATUS_SOLVED).all() and np.isnan(whole["x"][200]).any()
+    assert sorted(whole) == sorted(got) and ("dx_dx0" in whole) == jacobian
+    for k in whole:
+        assert np.array_equal(got[k], whole[k], equal_nan=True), (
+            k, [b for b in range(B) if not np.array_equal(got[k][b], whole[k][b], equal_nan=True)])
+
+
 def test_contracts(solver_mod, synth, layout):
     import torch
     cfg = layout.MPCConfig(n_iter=20, n_iter_small=5, control_horizon=9)

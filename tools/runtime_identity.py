@@ -4,9 +4,9 @@
     python tools/runtime_identity.py compare A.npz B.npz  # anywhere; exit status 1 unless everything is equal
 
 dump runs, per shape, on the library of the tree it is started from: solve on a runtime="always" handle, solve(configs=...)
-with rows that differ per instance, solve_sensitivity(jacobian=True), solve_adjoint without and with `configs`, certify of
-the solve's primals, and linearize.  The records and the configuration rows are stored beside the outputs, so that compare
-can tell that both dumps answered the same questions.
+with rows that differ per instance, solve_sensitivity(jacobian=True), solve_adjoint and solve_adjoint_record without and with
+the rows, certify of the solve's primals, and linearize.  The records and the configuration rows are stored beside the
+outputs, so that compare can tell that both dumps answered the same questions.
 
 Shapes (nIter, nIterSmall, controlHorizon), the smallest that reach every loop bound: (2,2,2) one throttle block, so that a
 held tick has an empty free set and every substitution runs with n = 0; (6,2,3); (12,12,12); (20,5,9); the paper's (17,7,12),
@@ -109,7 +109,7 @@ def dump(path):
         rng = np.random.default_rng(17)
         xbar, fmbar = rng.standard_normal((B, cfg.n_var)), rng.standard_normal((B, L.FM_SIZE))
         m = solver.BatchedVSMPC(cfg, device=0, max_batch=1 if one else B, runtime="always", sensitivity=True, tunables=True,
-                                certify=True, adjoint=True)
+                                certify=True, adjoint_record=True)
         try:
             assert m.uses_runtime_kernel
             x, fm, st, it = _per_launch(lambda s: m.solve(recs[s]), B, one)
@@ -122,6 +122,9 @@ def dump(path):
             ent["solve_adjoint"] = _per_launch(lambda s: m.solve_adjoint(recs[s], xbar[s], fmbar[s]), B, one)
             ent["solve_adjoint_configs"] = _per_launch(lambda s: m.solve_adjoint(recs[s], xbar[s], fmbar[s], tunables=rows[s]),
                                                        B, one)
+            ent["solve_adjoint_record"] = _per_launch(lambda s: m.solve_adjoint_record(recs[s], xbar[s], fmbar[s]), B, one)
+            ent["solve_adjoint_record_configs"] = _per_launch(
+                lambda s: m.solve_adjoint_record(recs[s], xbar[s], fmbar[s], tunables=rows[s]), B, one)
             xc = np.where((st == L.STATUS_NUMERICAL)[:, None], 0.0, x)  # (certify judges any x: no LDS residue in its input)
             ent["certify"] = dict(zip(("y", "cert"), _per_launch(lambda s: m.certify(recs[s], xc[s]), B, one)))
             ent["linearize"] = dict(zip(("A", "Bj", "Bt", "c"), _per_launch(lambda s: m.linearize(recs[s])[:4], B, one)),
@@ -139,7 +142,8 @@ def dump(path):
             count[CLASSES[2]] += int((solved & (recs[:, L.IN_HOLD] != 0.0)).sum())
         count[CLASSES[3]] += int((~np.isfinite(recs).all(axis=1) & (st == L.STATUS_NUMERICAL)).sum())
         count[CLASSES[4]] += sum(int((ent[e]["flags"] & L.SENS_DEGENERATE != 0).sum())
-                                 for e in ("solve_sensitivity", "solve_adjoint", "solve_adjoint_configs"))
+                                 for e in ("solve_sensitivity", "solve_adjoint", "solve_adjoint_configs", "solve_adjoint_record",
+                                           "solve_adjoint_record_configs"))
         count[CLASSES[5]] += int(len(np.unique(rows, axis=0)) > 1)
         print(f"{tag}: {B} instances, status {np.bincount(st, minlength=4)[1:]}, iterations up to {it.max()}", flush=True)
     np.savez_compressed(path, **out)
@@ -164,7 +168,7 @@ def compare(pa, pb):
     for (tag, entry), names in sorted(groups.items()):
         if not entry:                                                   # the inputs
             same = all(np.array_equal(a[f"{tag}/{n}"], b[f"{tag}/{n}"], equal_nan=True) for n in names)
-            print(f"{tag:>10s} {'inputs':22s} {' '.join(sorted(names))}: {'equal' if same else 'DIFFERENT'}")
+            print(f"{tag:>10s} {'inputs':28s} {' '.join(sorted(names))}: {'equal' if same else 'DIFFERENT'}")
             bad += not same
             continue
         get = lambda d, n: d[f"{tag}/{entry}/{n}"]                      # noqa: E731
@@ -188,7 +192,7 @@ def compare(pa, pb):
                 elif n not in wrong:
                     wrong.append(n)
         count = len(get(a, sorted(names)[0])) if entry != "linearize" else len(get(a, "A"))
-        text = f"{tag:>10s} {entry:22s} {count:2d} instances  {' '.join(sorted(names))}: "
+        text = f"{tag:>10s} {entry:28s} {count:2d} instances  {' '.join(sorted(names))}: "
         if wrong:
             text += "DIFFERENT in " + " ".join(wrong)
         else:
