@@ -593,6 +593,57 @@ int vsmpc_rollout_set_tunables(vsmpc_rollout* r, const double* tunables);
 int vsmpc_rollout_get_state(vsmpc_rollout* r, double* state);
 int vsmpc_rollout_get_records(vsmpc_rollout* r, double* records);
 
+/*
+ * Adjoint of the rollout: the gradient of a scalar loss L on the FLOWN trajectory -- on the log rows and on the final plant
+ * state -- with respect to the plant state at the start of the run and to the gains, through every tick: record -> solve ->
+ * first move -> plant -> next record ("Adjoint of the rollout"; executable model: tests/rollout_adjoint_model.py).
+ *
+ * vsmpc_rollout_run_taped does what vsmpc_rollout_run does -- same results, same log, bit for bit -- and keeps, for every tick
+ * t of this run, in device memory the rollout owns: the plant state in front of the tick, the record the tick solved, the
+ * solve's first move and its status, taken by device-to-device copies between the tick's launches (the ticks are launched
+ * directly; the captured graph of vsmpc_rollout_run is not used and not touched).  The tape is allocated, or grown, by this
+ * call: per instance and tick VSMPC_PLANT_STATE + n_in + VSMPC_FM_SIZE doubles plus one int (and VSMPC_ROLLOUT_LOG doubles
+ * of staging for vsmpc_rollout_backward's log_bar), beside a few rows per instance for the sweep.  An allocation failure
+ * returns VSMPC_ERR_ALLOC and leaves the rollout runnable, without a tape.  A later vsmpc_rollout_reset, _set_tree,
+ * _set_tunables, _set_attitude_tracks, _set_jet_plant or untaped vsmpc_rollout_run invalidates the tape.
+ * Supported: the parametric plant with the polynomial jet model.  A rollout with a tree (vsmpc_rollout_set_tree), with the jet
+ * plant option or with an RPYDot track is refused: VSMPC_ERR_UNSUPPORTED_CONFIG, and vsmpc_strerror names the option.
+ *
+ * vsmpc_rollout_backward sweeps the tape from the last tick to the first, in stream order.  Per tick: the transpose of the plant
+ * advance (advance_adjoint_kernel: the sub-steps are recomputed from the tape and run backwards) turns dL/d(state after the
+ * tick), with the tick's log_bar row added, into the direct part of dL/d(state in front of it) and the cotangent of the first
+ * move; the `_device` body of vsmpc_adjoint_record_batch on the taped record, with xbar = 0 and that fmbar and the rollout's
+ * rows of tunables if it has any, gives dL/d(record) and the tick's dL/d(gains); the transpose of the record assembly (the
+ * same kernel, in front of the previous tick's plant half) maps dL/d(record) back to the plant state and to the reference
+ * window, whose cotangent (12 n_ref doubles per instance) the sweep carries: it shifts back one column at every release tick,
+ * where the pushed column's h_lin entry R^T m v_ref hands its share to rpy, and ends at the first tick after a reset, where
+ * every column was built with that tick's attitude.
+ *   log_bar[ticks][batch][VSMPC_ROLLOUT_LOG]   dL/d(log rows of the taped run): p, rpy, T, throttle %; entries 14 and 15
+ *                                              (status, iterations) are ignored.  May be NULL.
+ *   state_bar[batch][VSMPC_PLANT_STATE]        dL/d(plant state after the last tick); entries 40.. are ignored.  May be NULL.
+ *                                              Both NULL: VSMPC_ERR_INVALID_ARG, as is a rollout without a tape.
+ *   grad_state0[batch][VSMPC_PLANT_STATE]      dL/d(plant state at the start of the taped run), entries 0..39; the jet-plant
+ *                                              slots get +0.0
+ *   grad_cfg[batch][VSMPC_GRAD_SIZE]           dL/d(every weight and throttle limit), summed over the ticks, in the order
+ *                                              and units of VSMPC_GRAD_* (vsmpc_adjoint_batch); with rows of
+ *                                              vsmpc_rollout_set_tunables every instance under its own row
+ *   flags[batch]                               OR over the ticks of VSMPC_ADJ_DEGENERATE and VSMPC_ADJ_UNSOLVED
+ * Every output may be NULL.  A tick whose taped status is not Solved did not consume its move: the cotangent of the move is
+ * zero, the latched entries (joints, throttle, thrust references) pass straight through, VSMPC_ADJ_UNSOLVED is set.  The
+ * sum over the ticks has an order fixed by the tick count alone: repeated and permuted batches are bit-identical.  Gradients
+ * with respect to the plant parameters and the trajectories are not returned; the tick grid, the hold pattern, the
+ * disturbance window and the alpha track are structural.  Needs a handle created with VSMPC_CREATE_ADJOINT_RECORD
+ * (otherwise VSMPC_ERR_UNSUPPORTED_CONFIG, and vsmpc_strerror names the flag); it uses that entry's workspace, so it must
+ * be ordered against the handle's other adjoint calls.
+ */
+int vsmpc_rollout_run_taped(vsmpc_rollout* r, int ticks, double* log, void* stream);
+/* Host buffers; returns after the results are in them. */
+int vsmpc_rollout_backward(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0,
+                           double* grad_cfg, int* flags, void* stream);
+/* Same, all pointers are DEVICE pointers and the call only enqueues work on `stream`. */
+int vsmpc_rollout_backward_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar, double* d_grad_state0,
+                                  double* d_grad_cfg, int* d_flags, void* stream);
+
 /* Pinned host memory for the caller's in/x/first_move/status buffers (thin wrappers of hipHostMalloc / hipHostFree,
  * so that a C caller need not link the HIP runtime).  With pinned OUTPUT buffers vsmpc_solve_batch lets the kernel write
  * the results straight into them (no device-to-host copies) while the uploads of the next chunk overlap the solves of

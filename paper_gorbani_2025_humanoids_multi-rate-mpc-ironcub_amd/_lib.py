@@ -50,6 +50,9 @@ SIGNATURES = {
     "vsmpc_rollout_reset": [vp, dp, dp],
     "vsmpc_rollout_run": [vp, c_int, dp, vp],
     "vsmpc_rollout_get_state": [vp, dp], "vsmpc_rollout_get_records": [vp, dp],
+    "vsmpc_rollout_run_taped": [vp, c_int, dp, vp],
+    # r, log_bar, state_bar, grad_state0, grad_cfg, flags, stream
+    "vsmpc_rollout_backward": [vp, dp, dp, dp, dp, vp, vp], "vsmpc_rollout_backward_device": [vp, dp, dp, dp, dp, vp, vp],
     "vsmpc_alloc_host": ([ctypes.c_size_t], vp),
     "vsmpc_free_host": ([vp], None),
     "vsmpc_set_kernel_form": [vp, c_int], "vsmpc_set_small_batch_kernel": [vp, c_int], "vsmpc_small_batch_kernel_for": [vp, c_int],

@@ -14,6 +14,13 @@ throttle, the linearisation point, the posture error and the model data -- throu
     x, first_move, status = plan(mpc, records.requires_grad_(), x0, gains)
     loss(x, first_move).backward()                               # records.grad (zero in the X0 columns), x0.grad, gains.grad
 
+A whole closed loop is differentiable too -- a loss on the flown trajectory backpropagates through every tick to the initial
+plant state and to the gains, in one backward sweep over the tape of the forward run ("Adjoint of the rollout"):
+
+    ro = ClosedLoopRollout(cfg, B, pos, vel, alpha, alpha_dt, adjoint=True)
+    log, final_state = rollout(ro, state0, gains, params, ticks)  # state0 [B, 40], gains [B, GRAD_SIZE], params [B, PLANT_PARAMS]
+    loss(log, final_state).backward()                            # state0.grad, gains.grad
+
 All numerics run in libvsmpc.so (HIP); there is no CPU path.
 """
 from __future__ import annotations
@@ -114,3 +121,64 @@ def plan(mpc: BatchedVSMPC, records, x0, gains=None, info: dict | None = None):
     """(x, first_move, status) of the batch, differentiable with respect to `x0` and `gains`, and on a handle created with
     adjoint_record=True with respect to `records` (PlanFunction)"""
     return PlanFunction.apply(mpc, records, x0, gains, info)
+
+
+NS_LIVE = 40   # entries of the plant state the parametric plant uses (the jet-plant slots behind them carry no gradient)
+
+
+class RolloutFunction(torch.autograd.Function):
+    """forward(ro, state0, gains, params, ticks, info) -> (log [ticks, B, 14], final_state [B, 40])
+
+    Forward: the rollout `ro` (a ClosedLoopRollout created with adjoint=True) is reset to `state0` [B, 40] (CUDA or CPU,
+    float64; the jet-plant slots of the plant state are zero) with the plant parameters `params` [B, PLANT_PARAMS] (numpy or
+    tensor, not differentiable) and, when `gains` [B, L.GRAD_SIZE] is given, one row of tunables per loop; then `ticks` taped
+    ticks run.  reset, set_tunables and the log go through the HOST, as ClosedLoopRollout's own methods do.
+    Backward: ONE vsmpc_rollout_backward_device sweep with the incoming cotangents of the log columns 0..13 and of the final
+    state.  `info` (a dict, or None) receives "flags" (OR over the ticks of L.ADJ_*) as a CUDA tensor."""
+
+    @staticmethod
+    def forward(ctx, ro, state0, gains, params, ticks, info):
+        B = ro.batch
+        assert tuple(state0.shape) == (B, NS_LIVE) and state0.dtype == torch.float64
+        st = np.zeros((B, L.PLANT_STATE))
+        st[:, :NS_LIVE] = state0.detach().cpu().numpy()
+        pa = params.detach().cpu().numpy() if isinstance(params, torch.Tensor) else np.asarray(params, dtype=np.float64)
+        if gains is not None:
+            assert tuple(gains.shape) == (B, L.GRAD_SIZE) and gains.dtype == torch.float64
+            ro.set_tunables(configs=configs_of(ro.cfg, gains.detach().cpu().numpy()))
+        else:
+            ro.set_tunables(None)
+        ro.reset(st, pa)
+        log = ro.run(int(ticks), tape=True)
+        dev = state0.device if state0.is_cuda else torch.device("cuda", ro.mpc.device)
+        ctx.ro, ctx.info, ctx.dev, ctx.ticks = ro, info, dev, int(ticks)
+        ctx.out_dev = state0.device
+        return (torch.from_numpy(log[:, :, :14].copy()).to(state0.device),
+                torch.from_numpy(ro.state()[:, :NS_LIVE].copy()).to(state0.device))
+
+    @staticmethod
+    def backward(ctx, glog, gfinal):
+        ro, dev, B = ctx.ro, ctx.dev, ctx.ro.batch
+        lb = sb = None
+        if glog is not None:
+            lb = torch.zeros((ctx.ticks, B, L.ROLLOUT_LOG), dtype=torch.float64, device=dev)
+            lb[:, :, :14] = glog.to(dev)
+        if gfinal is not None:
+            sb = torch.zeros((B, L.PLANT_STATE), dtype=torch.float64, device=dev)
+            sb[:, :NS_LIVE] = gfinal.to(dev)
+        if lb is None and sb is None:
+            return None, None, None, None, None, None
+        g0 = torch.empty((B, L.PLANT_STATE), dtype=torch.float64, device=dev)
+        gg = torch.empty((B, L.GRAD_SIZE), dtype=torch.float64, device=dev)
+        flags = torch.empty(B, dtype=torch.int32, device=dev)
+        ro.backward_device(lb, sb, g0, gg, flags)
+        if ctx.info is not None:
+            ctx.info["flags"] = flags
+        return (None, g0[:, :NS_LIVE].to(ctx.out_dev) if ctx.needs_input_grad[1] else None,
+                gg.to(ctx.out_dev) if ctx.needs_input_grad[2] else None, None, None, None)
+
+
+def rollout(ro, state0, gains, params, ticks: int, info: dict | None = None):
+    """(log [ticks, B, 14], final_state [B, 40]) of `ticks` closed-loop ticks from `state0`, differentiable with respect to
+    `state0` and `gains` (RolloutFunction)"""
+    return RolloutFunction.apply(ro, state0, gains, params, ticks, info)

@@ -32,6 +32,7 @@ void invalidate(vsmpc_rollout* r) {
     if (r->gexec) { (void)hipGraphExecDestroy(r->gexec); r->gexec = nullptr; }
     r->graph_state = 0;
     r->valid = 0;
+    r->tape.ticks = 0;
 }
 
 }  // namespace
@@ -105,6 +106,7 @@ int vsmpc_rollout_reset(vsmpc_rollout* r, const double* state, const double* par
     HIP_TRY(hipMemcpy(r->d_params, params, B * VSMPC_PLANT_PARAMS * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(r->d_tick, 0, B * sizeof(int)));
     r->ticks_done = 0;
+    r->tape.ticks = 0;
     // record of tick 0; from here on every tick's advance kernel leaves the record of the following tick
     r->valid = 0;
     if (r->use_tree) HIP_TRY(enqueue_tree(r, nullptr, nullptr, nullptr));
@@ -232,6 +234,126 @@ void build_tick_graph(vsmpc_rollout* r, hipStream_t s) {
     if (graph) (void)hipGraphDestroy(graph);
 }
 
+
+// what a run does in front of its ticks: the device log of `ticks` rows (grown when shorter) and the control block
+int begin_run(vsmpc_rollout* r, int ticks, double* log, hipStream_t s) {
+    const size_t row = size_t(r->batch) * VSMPC_ROLLOUT_LOG;
+    if (log != nullptr && r->log_ticks < ticks) {
+        r->log_ticks = 0;
+        hipError_t e = r->d_log.alloc(size_t(ticks) * row);   // (frees the shorter one first)
+        if (e != hipSuccess) return e == hipErrorOutOfMemory ? VSMPC_ERR_ALLOC : hip_fail(e, "vsmpc_rollout_run");
+        r->log_ticks = ticks;
+    }
+    const RolloutCtl ctl = {log ? r->d_log : nullptr, r->ticks_done, log ? ticks : 0};
+    HIP_TRY(hipMemcpyAsync(r->d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // `ctl` lives on this stack frame
+    return VSMPC_OK;
+}
+// and behind them: the log comes back, the run has completed
+int end_run(vsmpc_rollout* r, int ticks, double* log, hipStream_t s) {
+    HIP_TRY(download_rows(log, r->d_log, 0, size_t(ticks), size_t(r->batch) * VSMPC_ROLLOUT_LOG, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    r->ticks_done += ticks;
+    r->valid = 1;
+    return VSMPC_OK;
+}
+
+const char* const BACKWARD_NEEDS_FLAG =
+    "vsmpc_rollout_backward needs a rollout on a handle created with VSMPC_CREATE_ADJOINT_RECORD (vsmpc_create_ex)";
+
+// Tape of `ticks` ticks and the rows of the backward sweep.  A failure leaves no tape and the rollout as it was.
+hipError_t grow_tape(vsmpc_rollout* r, int ticks) {
+    vsmpc_rollout::Tape& tp = r->tape;
+    const vsmpc_handle* h = r->h;
+    const size_t B = size_t(r->batch), T = size_t(ticks);
+    hipError_t e = hipSuccess;
+    if (tp.cap < ticks) {
+        tp.cap = 0;
+        e = tp.s.alloc(T * B * VSMPC_PLANT_STATE);
+        if (e == hipSuccess) e = tp.rec.alloc(T * B * h->n_in);
+        if (e == hipSuccess) e = tp.fm.alloc(T * B * VSMPC_FM_SIZE);
+        if (e == hipSuccess) e = tp.status.alloc(T * B);
+        if (e == hipSuccess) e = tp.log_bar.alloc(T * B * VSMPC_ROLLOUT_LOG);
+        if (e != hipSuccess) return e;
+        tp.cap = ticks;
+    }
+    if (tp.bstatus == nullptr) {   // (allocated last: its presence says that all of them are there)
+        e = tp.sbar.alloc(B * VSMPC_PLANT_STATE);
+        if (e == hipSuccess) e = tp.wbar.alloc(B * 12 * r->rd.n_ref);
+        if (e == hipSuccess) e = tp.fmbar.alloc(B * VSMPC_FM_SIZE);
+        if (e == hipSuccess) e = tp.xbar.alloc(B * h->n_var);
+        if (e == hipSuccess) e = hipMemset(tp.xbar, 0, B * h->n_var * sizeof(double));   // the sweep's xbar is zero
+        if (e == hipSuccess) e = tp.gin.alloc(B * h->n_in);
+        if (e == hipSuccess) e = tp.gcfg_t.alloc(B * VSMPC_GRAD_SIZE);
+        if (e == hipSuccess) e = tp.gcfg.alloc(B * VSMPC_GRAD_SIZE);
+        if (e == hipSuccess) e = tp.flags_t.alloc(B);
+        if (e == hipSuccess) e = tp.flags.alloc(B);
+        if (e == hipSuccess) e = tp.bstatus.alloc(B);
+    }
+    return e;
+}
+
+// enqueue_tick of the parametric plant with the tape's rows of tick `t` of this run copied out between its launches
+hipError_t enqueue_tick_taped(vsmpc_rollout* r, int t, hipStream_t s) {
+    vsmpc_handle* h = r->h;
+    vsmpc_rollout::Tape& tp = r->tape;
+    const size_t B = size_t(r->batch), o = size_t(t) * B;
+    auto keep = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s); };
+    hipError_t e = keep(tp.s + o * VSMPC_PLANT_STATE, r->d_state, B * VSMPC_PLANT_STATE * sizeof(double));
+    if (e == hipSuccess) e = keep(tp.rec + o * h->n_in, r->d_rec, B * h->n_in * sizeof(double));
+    if (e == hipSuccess)
+        e = solve_launch(h, r->d_rec, r->batch, h->d_x, h->d_fm, h->d_status, h->d_iters, 0, s, r->use_tun ? r->d_tun : nullptr);
+    if (e == hipSuccess) e = keep(tp.fm + o * VSMPC_FM_SIZE, h->d_fm, B * VSMPC_FM_SIZE * sizeof(double));
+    if (e == hipSuccess) e = keep(tp.status + o, h->d_status, B * sizeof(int));
+    if (e == hipSuccess)
+        e = launch_advance(r->rd, r->batch, r->d_state, r->d_params, r->d_tick, h->d_fm, h->d_status, h->d_iters,
+                           r->d_talpha, r->d_ctl, r->substeps, r->d_tpos, r->d_tvel, r->d_tstate, r->d_rec, s);
+    return e;
+}
+
+// The backward sweep over the tape, last tick to first, in stream order: tape.sbar holds dL/d(final state) on entry and
+// dL/d(state at the start of the taped run) on exit; tape.gcfg and tape.flags receive the sums over the ticks.  Launch k of
+// advance_adjoint_kernel is the record half of tick k behind the plant half of tick k - 1, with the record adjoint of tick
+// k - 1 (the `_device` body of vsmpc_adjoint_record_batch: xbar = 0, fmbar = the plant half's) between launches k and k - 1.
+int enqueue_sweep(vsmpc_rollout* r, const double* d_log_bar, hipStream_t s) {
+    vsmpc_handle* h = r->h;
+    vsmpc_rollout::Tape& tp = r->tape;
+    const size_t B = size_t(r->batch);
+    const int T = tp.ticks;
+    HIP_TRY(hipMemsetAsync(tp.wbar, 0, B * 12 * r->rd.n_ref * sizeof(double), s));
+    HIP_TRY(hipMemsetAsync(tp.gcfg, 0, B * VSMPC_GRAD_SIZE * sizeof(double), s));
+    HIP_TRY(hipMemsetAsync(tp.flags, 0, B * sizeof(int), s));
+    RolloutAdj a = {};
+    a.batch = r->batch;
+    a.substeps = r->substeps;
+    a.params = r->d_params;
+    a.traj_vel = r->d_tvel;
+    a.traj_alpha = r->d_talpha;
+    a.gin = tp.gin; a.gcfg_t = tp.gcfg_t; a.flags_t = tp.flags_t;
+    a.sbar = tp.sbar; a.wbar = tp.wbar; a.fmbar = tp.fmbar; a.gcfg = tp.gcfg; a.flags = tp.flags;
+    for (int k = T; k >= 0; --k) {
+        if (k < T) {
+            const int rc = vsmpc_adjoint_record_batch_device(h, tp.rec + size_t(k) * B * h->n_in, r->use_tun ? r->d_tun.get() : nullptr,
+                                                             tp.xbar, tp.fmbar, r->batch, nullptr, nullptr, tp.bstatus, nullptr,
+                                                             nullptr, tp.gcfg_t, nullptr, tp.flags_t, tp.gin, nullptr, s);
+            if (rc != VSMPC_OK) return rc;
+        }
+        a.tick_rec = k < T ? tp.tick_base + k : -1;
+        a.first = k < T && tp.tick_base + k == 0;
+        a.s_rec = k < T ? tp.s + size_t(k) * B * VSMPC_PLANT_STATE : nullptr;
+        a.tick_plant = k > 0 ? tp.tick_base + k - 1 : -1;
+        if (k > 0) {
+            const size_t o = size_t(k - 1) * B;
+            a.s_plant = tp.s + o * VSMPC_PLANT_STATE;
+            a.fm = tp.fm + o * VSMPC_FM_SIZE;
+            a.status = tp.status + o;
+            a.log_bar = d_log_bar ? d_log_bar + o * VSMPC_ROLLOUT_LOG : nullptr;
+        }
+        HIP_TRY(launch_advance_adjoint(r->rd, a, s));
+    }
+    return VSMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -243,16 +365,8 @@ int vsmpc_rollout_run(vsmpc_rollout* r, int ticks, double* log, void* stream) {
     vsmpc_handle* h = r->h;
     ON_DEVICE(h->device);
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->own_stream.h;
-    const size_t row = size_t(r->batch) * VSMPC_ROLLOUT_LOG;
-    if (log != nullptr && r->log_ticks < ticks) {
-        r->log_ticks = 0;
-        hipError_t e = r->d_log.alloc(size_t(ticks) * row);   // (frees the shorter one first)
-        if (e != hipSuccess) return e == hipErrorOutOfMemory ? VSMPC_ERR_ALLOC : hip_fail(e, "vsmpc_rollout_run");
-        r->log_ticks = ticks;
-    }
-    const RolloutCtl ctl = {log ? r->d_log : nullptr, r->ticks_done, log ? ticks : 0};
-    HIP_TRY(hipMemcpyAsync(r->d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));  // `ctl` lives on this stack frame
+    if (const int rc = begin_run(r, ticks, log, s); rc != VSMPC_OK) return rc;
+    r->tape.ticks = 0;                  // the tape describes the run in front of this one
     r->valid = 0;                       // until the whole run has completed: a failure below leaves the counters ahead
     int t = 0;
     // the captured launches are of the other condensing form, or of the other kernel for this batch size
@@ -261,10 +375,74 @@ int vsmpc_rollout_run(vsmpc_rollout* r, int ticks, double* log, void* stream) {
     if (r->graph_state == 1)
         for (; ticks - t >= GRAPH_TICKS; t += GRAPH_TICKS) HIP_TRY(hipGraphLaunch(r->gexec, s));
     for (; t < ticks; ++t) HIP_TRY(enqueue_tick(r, s));
-    HIP_TRY(download_rows(log, r->d_log, 0, size_t(ticks), row, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    r->ticks_done += ticks;
-    r->valid = 1;
+    return end_run(r, ticks, log, s);
+}
+
+int vsmpc_rollout_run_taped(vsmpc_rollout* r, int ticks, double* log, void* stream) {
+    if (r == nullptr || ticks < 0) return invalid_arg();
+    if (!r->valid) return invalid_arg();
+    // what the backward sweep has no transpose of
+    if (r->use_tree) return unsupported("vsmpc_rollout_run_taped: no adjoint of the kinematic-tree plant (vsmpc_rollout_set_tree)");
+    if (r->rd.jet_nn) return unsupported("vsmpc_rollout_run_taped: no adjoint of the jet plant option (vsmpc_rollout_set_jet_plant)");
+    if (r->rd.traj_rpyd != nullptr)
+        return unsupported("vsmpc_rollout_run_taped: no adjoint of an RPYDot track (vsmpc_rollout_set_attitude_tracks)");
+    vsmpc_handle* h = r->h;
+    ON_DEVICE(h->device);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->own_stream.h;
+    r->tape.ticks = 0;
+    if (ticks == 0) return VSMPC_OK;
+    if (const hipError_t e = grow_tape(r, ticks); e != hipSuccess)   // (the rollout itself is untouched: still runnable)
+        return e == hipErrorOutOfMemory ? VSMPC_ERR_ALLOC : hip_fail(e, "vsmpc_rollout_run_taped");
+    if (const int rc = begin_run(r, ticks, log, s); rc != VSMPC_OK) return rc;
+    r->valid = 0;
+    // direct launches: the captured graph has no room for the copies between its kernels
+    for (int t = 0; t < ticks; ++t) HIP_TRY(enqueue_tick_taped(r, t, s));
+    if (const int rc = end_run(r, ticks, log, s); rc != VSMPC_OK) return rc;
+    r->tape.ticks = ticks;
+    r->tape.tick_base = r->ticks_done - ticks;
+    return VSMPC_OK;
+}
+
+int vsmpc_rollout_backward_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar, double* d_grad_state0,
+                                  double* d_grad_cfg, int* d_flags, void* stream) {
+    if (r == nullptr || (d_log_bar == nullptr && d_state_bar == nullptr) || r->tape.ticks == 0) return invalid_arg();
+    if (!r->h->adjoint_record.on) return unsupported(BACKWARD_NEEDS_FLAG);
+    ON_DEVICE(r->h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);   // the caller's, the null stream too: its tensors are ordered on it
+    const size_t B = size_t(r->batch);
+    vsmpc_rollout::Tape& tp = r->tape;
+    if (d_state_bar != nullptr)
+        HIP_TRY(hipMemcpyAsync(tp.sbar, d_state_bar, B * VSMPC_PLANT_STATE * sizeof(double), hipMemcpyDeviceToDevice, s));
+    else
+        HIP_TRY(hipMemsetAsync(tp.sbar, 0, B * VSMPC_PLANT_STATE * sizeof(double), s));
+    if (const int rc = enqueue_sweep(r, d_log_bar, s); rc != VSMPC_OK) return rc;
+    if (d_grad_state0 != nullptr)
+        HIP_TRY(hipMemcpyAsync(d_grad_state0, tp.sbar, B * VSMPC_PLANT_STATE * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (d_grad_cfg != nullptr)
+        HIP_TRY(hipMemcpyAsync(d_grad_cfg, tp.gcfg, B * VSMPC_GRAD_SIZE * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (d_flags != nullptr) HIP_TRY(hipMemcpyAsync(d_flags, tp.flags, B * sizeof(int), hipMemcpyDeviceToDevice, s));
+    return VSMPC_OK;
+}
+
+int vsmpc_rollout_backward(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0,
+                           double* grad_cfg, int* flags, void* stream) {
+    if (r == nullptr || (log_bar == nullptr && state_bar == nullptr) || r->tape.ticks == 0) return invalid_arg();
+    if (!r->h->adjoint_record.on) return unsupported(BACKWARD_NEEDS_FLAG);
+    ON_DEVICE(r->h->device);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->own_stream.h;
+    const size_t B = size_t(r->batch);
+    vsmpc_rollout::Tape& tp = r->tape;
+    HIP_TRY(upload_rows(tp.log_bar.get(), log_bar, 0, size_t(tp.ticks), B * VSMPC_ROLLOUT_LOG, s));
+    HIP_TRY(upload_rows(tp.sbar.get(), state_bar, 0, B, VSMPC_PLANT_STATE, s));
+    if (state_bar == nullptr) HIP_TRY(hipMemsetAsync(tp.sbar, 0, B * VSMPC_PLANT_STATE * sizeof(double), s));
+    int rc = enqueue_sweep(r, log_bar ? tp.log_bar.get() : nullptr, s);
+    hipError_t e = hipSuccess;
+    if (rc == VSMPC_OK) e = download_rows(grad_state0, tp.sbar.get(), 0, B, VSMPC_PLANT_STATE, s);
+    if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(grad_cfg, tp.gcfg.get(), 0, B, VSMPC_GRAD_SIZE, s);
+    if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(flags, tp.flags.get(), 0, B, 1, s);
+    const hipError_t e2 = hipStreamSynchronize(s);   // nothing returns while copies from the caller's buffers are queued
+    if (rc != VSMPC_OK) return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, "vsmpc_rollout_backward");
     return VSMPC_OK;
 }
 

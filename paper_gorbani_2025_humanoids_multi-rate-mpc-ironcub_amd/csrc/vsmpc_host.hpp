@@ -177,6 +177,19 @@ struct vsmpc_rollout {
     // per-instance tunables (vsmpc_rollout_set_tunables)
     int use_tun;
     vsmpc::DevBuf<double> d_tun;  // rows [batch][VSMPC_TUNE_SIZE]
+    // tape of the last vsmpc_rollout_run_taped and the scratch of vsmpc_rollout_backward: allocated or grown by run_taped
+    struct Tape {
+        int ticks = 0;        // ticks on the tape; 0: none (never taped, or invalidated by reset / set_* / an untaped run)
+        int cap = 0;          // ticks the four buffers below hold
+        int tick_base = 0;    // the rollout's tick counter at the start of the taped run
+        vsmpc::DevBuf<double> s, rec, fm;   // [cap][batch][VSMPC_PLANT_STATE | n_in | VSMPC_FM_SIZE]
+        vsmpc::DevBuf<int> status;          // [cap][batch]
+        // per-instance rows of the sweep: cotangents of the plant state, the window and the first move; the record adjoint's
+        // xbar (zeros, [n_var]), grad_in, grad_cfg, flags and status of one tick; the sums over the ticks
+        vsmpc::DevBuf<double> sbar, wbar, fmbar, xbar, gin, gcfg_t, gcfg, log_bar;
+        vsmpc::DevBuf<int> flags_t, flags, bstatus;
+        int log_bar_ticks = 0;              // rows of ticks the host entry's log_bar staging holds
+    } tape;
 };
 
 namespace vsmpc {

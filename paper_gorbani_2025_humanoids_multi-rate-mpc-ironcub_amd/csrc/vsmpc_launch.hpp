@@ -204,4 +204,30 @@ hipError_t launch_advance(const RolloutDev& rd, int batch, double* state, const 
                           const double* traj_pos, const double* traj_vel, double* tstate, double* rec_next,
                           hipStream_t stream);
 
+// One launch of the rollout's backward sweep (vsmpc_rollout_adjoint.hip): the record half of tick `tick_rec`, then the plant
+// half of tick `tick_plant` (ticks as the rollout counts them since its reset; -1: that half is absent).  All device pointers,
+// [batch][..] rows.  sbar, wbar, gcfg and flags are read and written in place.
+struct RolloutAdj {
+    int batch, substeps;
+    int tick_rec, first;         // `first`: tick_rec built the reference window (the first tick after a reset)
+    int tick_plant;
+    const double* params;        // [VSMPC_PLANT_PARAMS]
+    const double* traj_vel;
+    const double* traj_alpha;
+    const double* s_rec;         // taped plant state in front of tick_rec [VSMPC_PLANT_STATE]
+    const double* gin;           // the record adjoint's outputs of tick_rec: grad_in [n_in], grad_cfg [VSMPC_GRAD_SIZE], flags
+    const double* gcfg_t;
+    const int* flags_t;
+    const double* s_plant;       // tape of tick_plant: plant state in front of it, first move [VSMPC_FM_SIZE], status
+    const double* fm;
+    const int* status;
+    const double* log_bar;       // cotangent of tick_plant's log row [VSMPC_ROLLOUT_LOG], or nullptr
+    double* sbar;                // cotangent of the plant state [VSMPC_PLANT_STATE]
+    double* wbar;                // cotangent of the reference window [12 n_ref]
+    double* fmbar;               // out: cotangent of tick_plant's first move [VSMPC_FM_SIZE]
+    double* gcfg;                // accumulated over the ticks [VSMPC_GRAD_SIZE]
+    int* flags;
+};
+hipError_t launch_advance_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream);
+
 }  // namespace vsmpc

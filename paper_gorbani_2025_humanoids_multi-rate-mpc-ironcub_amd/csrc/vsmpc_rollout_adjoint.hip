@@ -1,0 +1,377 @@
+// Adjoint of the closed-loop rollout (include/vsmpc.h: vsmpc_rollout_backward): the transposes of the two rollout kernels of
+// vsmpc_rollout.hip, in one kernel that the backward sweep launches between the record adjoints of consecutive ticks.
+//
+//   advance_adjoint_kernel   second half of tick t, then first half of tick t - 1 (either may be absent):
+//     record half   transpose of assemble_record at the taped state s_t: the solve adjoint's grad_in of tick t is pulled
+//                   back to the plant state (X0, the errors against window column 0, R and I_G = R I_B R^T through rpy,
+//                   omega through I_B^-1, A_mom and the posture error through q, Lambda = DJ T and the linearisation point
+//                   through T, the previous commands) and to the reference window; then the transpose of the window FIFO:
+//                   on a release tick the pushed column's h_lin entry R^T m v_ref goes to rpy and the cotangent shifts back
+//                   one column; at a tick that built the window (`first`) every column's h_lin entry does.  The tick's
+//                   grad_cfg and flags are accumulated here, in tick order.
+//     plant half    transpose of advance_kernel at the taped (s_{t-1}, first move, status): the sub-steps are recomputed and
+//                   kept in LDS, then run backwards, one state component per lane as the forward kernel runs them.  Out come
+//                   the direct part of dL/ds_{t-1} and the cotangent of the first move; on a tick that was not Solved the
+//                   move was not consumed: its cotangent is zero and the latched entries pass straight through.
+//
+// Mirror of tests/rollout_adjoint_model.py (plant_adjoint, record_adjoint), which is checked against central differences
+// of the forward loop model.  Parametric plant with the polynomial jet model only (the entry refuses the others).
+#include "vsmpc_device.hpp"
+#include "vsmpc_launch.hpp"
+#include "vsmpc_rollout_device.hpp"
+
+namespace vsmpc {
+
+// R(rpy) as rot_from_rpy builds it, and its partials to roll, pitch, yaw: dR + 9 a, row-major
+VS_DEV void rot_partials(double sr, double cr, double sp, double cp, double sy, double cy, double* R, double* dR) {
+    R[0] = cy * cp; R[1] = cy * sp * sr - sy * cr; R[2] = cy * sp * cr + sy * sr;
+    R[3] = sy * cp; R[4] = sy * sp * sr + cy * cr; R[5] = sy * sp * cr - cy * sr;
+    R[6] = -sp;     R[7] = cp * sr;                R[8] = cp * cr;
+    dR[0] = 0.0; dR[1] = cy * sp * cr + sy * sr; dR[2] = -cy * sp * sr + sy * cr;
+    dR[3] = 0.0; dR[4] = sy * sp * cr - cy * sr; dR[5] = -sy * sp * sr - cy * cr;
+    dR[6] = 0.0; dR[7] = cp * cr;                dR[8] = -cp * sr;
+    dR[9] = -cy * sp;  dR[10] = cy * cp * sr; dR[11] = cy * cp * cr;
+    dR[12] = -sy * sp; dR[13] = sy * cp * sr; dR[14] = sy * cp * cr;
+    dR[15] = -cp;      dR[16] = -sp * sr;     dR[17] = -sp * cr;
+    dR[18] = -sy * cp; dR[19] = -sy * sp * sr - cy * cr; dR[20] = -sy * sp * cr + cy * sr;
+    dR[21] = cy * cp;  dR[22] = cy * sp * sr - sy * cr;  dR[23] = cy * sp * cr + sy * sr;
+    dR[24] = 0.0;      dR[25] = 0.0;                     dR[26] = 0.0;
+}
+
+// (dR_a w) . (m v): what a window column's h_lin entry R^T m v_ref, with cotangent w, hands to rpy component a
+VS_DEV double hlin_to_rpy(const double* __restrict__ dRa, const double* __restrict__ w, const double* __restrict__ v, double m) {
+    double acc = 0.0;
+    for (int r = 0; r < 3; ++r) acc += (dRa[3 * r] * w[0] + dRa[3 * r + 1] * w[1] + dRa[3 * r + 2] * w[2]) * (m * v[r]);
+    return acc;
+}
+
+// One wavefront per instance, as advance_kernel.  Every global load is requested in front of the first barrier.
+__global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd, RolloutAdj a) {
+    __shared__ double s[VSMPC_PLANT_STATE], p[VSMPC_PLANT_PARAMS + 1], f[VSMPC_FM_SIZE], sb[VSMPC_PLANT_STATE];
+    __shared__ double gi[VSMPC_IN_XREF + 12 * MAX_STAGES], wb[12 * MAX_STAGES];
+    __shared__ double R[9], dR[27], IBi[9], Aq[24], Ab[24], vb[4], vthr[4], alpha_s[16];
+    __shared__ double xs[16 * 20], lam[20], sc[6], omv[3], omb[3];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= a.batch) return;
+    const bool rec = a.tick_rec >= 0, plant = a.tick_plant >= 0;
+    const int nref = rd.n_ref, nwin = 12 * rd.n_ref;
+    stage_in<VSMPC_PLANT_STATE>(a.sbar + size_t(b) * VSMPC_PLANT_STATE, sb, lane);
+    stage_in<VSMPC_PLANT_PARAMS>(a.params + size_t(b) * VSMPC_PLANT_PARAMS, p, lane);
+    for (int e = lane; e < nwin; e += RO_BLOCK) wb[e] = a.wbar[size_t(b) * nwin + e];
+    if (rec) {
+        stage_in<VSMPC_PLANT_STATE>(a.s_rec + size_t(b) * VSMPC_PLANT_STATE, s, lane);
+        for (int e = lane; e < rd.n_in; e += RO_BLOCK) gi[e] = a.gin[size_t(b) * rd.n_in + e];
+        if (lane < VSMPC_GRAD_SIZE) a.gcfg[size_t(b) * VSMPC_GRAD_SIZE + lane] += a.gcfg_t[size_t(b) * VSMPC_GRAD_SIZE + lane];
+        if (lane == VSMPC_GRAD_SIZE) a.flags[b] |= a.flags_t[b];
+    }
+    // the plant half's rows wait in registers until the record half is through with `s`
+    double sp0 = 0.0, sp1 = 0.0, fm = 0.0, lbar = 0.0;
+    int st = 0;
+    if (plant) {
+        sp0 = a.s_plant[size_t(b) * VSMPC_PLANT_STATE + lane];
+        if (lane + RO_BLOCK < VSMPC_PLANT_STATE) sp1 = a.s_plant[size_t(b) * VSMPC_PLANT_STATE + lane + RO_BLOCK];
+        if (lane < VSMPC_FM_SIZE) fm = a.fm[size_t(b) * VSMPC_FM_SIZE + lane];
+        st = a.status[b];
+        if (a.log_bar != nullptr && lane < 14) lbar = a.log_bar[size_t(b) * VSMPC_ROLLOUT_LOG + lane];
+    }
+    __syncthreads();
+    const double m = p[VSMPC_PP_MASS];
+    const double* DJ = p + VSMPC_PP_DJ;
+
+    if (rec) {
+        const int tk = a.tick_rec + int(p[VSMPC_PP_TICK0]);
+        if (lane == 0) {
+            double sr, cr, sp, cp, sy, cy;
+            sincos(s[VSMPC_PS_RPY], &sr, &cr); sincos(s[VSMPC_PS_RPY + 1], &sp, &cp); sincos(s[VSMPC_PS_RPY + 2], &sy, &cy);
+            rot_partials(sr, cr, sp, cp, sy, cy, R, dR);
+        } else if (lane == 1) {
+            inv3(p + VSMPC_PP_INERTIA_B, IBi);
+        }
+        for (int e = lane; e < nwin; e += RO_BLOCK) wb[e] += gi[VSMPC_IN_XREF + e];
+        __syncthreads();
+        if (lane < 3) {   // X0[20:26] and PREF read column 0 of the window
+            wb[lane] += gi[VSMPC_IN_PREF + lane] - gi[VSMPC_IN_X0 + 20 + lane];
+            wb[6 + lane] -= gi[VSMPC_IN_X0 + 23 + lane];
+        }
+        __syncthreads();
+        double add = 0.0;
+        if (lane < 20) add = gi[VSMPC_IN_X0 + lane];               // X0: identity (the unwrapped RPY has derivative 1)
+        if (lane < 3) {
+            add += gi[VSMPC_IN_X0 + 20 + lane];
+        } else if (lane >= 6 && lane < 9) {
+            const int c = lane - 6;
+            const double* dRa = dR + 9 * c;
+            const double* IB = p + VSMPC_PP_INERTIA_B;
+            add += gi[VSMPC_IN_X0 + 23 + c] + gi[VSMPC_IN_RPY + c];
+            for (int k = 0; k < 9; ++k) add += gi[VSMPC_IN_WRB + k] * dRa[k];
+            // I_G = R I_B R^T: sum_ij G_ij (dR_a I_B R^T + R I_B dR_a^T)_ij
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    double t = 0.0;
+                    for (int u = 0; u < 3; ++u)
+                        for (int v = 0; v < 3; ++v)
+                            t += (dRa[3 * i + u] * R[3 * j + v] + R[3 * i + u] * dRa[3 * j + v]) * IB[3 * u + v];
+                    add += gi[VSMPC_IN_INERTIA + 3 * i + j] * t;
+                }
+            if (tk % rd.ratio == rd.ratio - 1) {   // the column this tick pushed, at this tick's R
+                int idx = 1 + (tk + 1) / rd.ratio;
+                idx = idx < rd.n_traj ? idx : rd.n_traj - 1;
+                add += hlin_to_rpy(dRa, wb + 12 * (nref - 1) + 3, a.traj_vel + 3 * idx, m);
+            }
+        } else if (lane >= 9 && lane < 12) {
+            const int c = lane - 9;
+            add += IBi[c] * gi[VSMPC_IN_OMEGA] + IBi[3 + c] * gi[VSMPC_IN_OMEGA + 1] + IBi[6 + c] * gi[VSMPC_IN_OMEGA + 2];
+        } else if (lane >= 12 && lane < 16) {                       // T: T0 and Lambda column j = DJ[j] T
+            const int c = lane - 12;
+            add += gi[VSMPC_IN_T0 + c];
+            for (int j = 0; j < 8; ++j)
+                for (int row = 0; row < 6; ++row)
+                    add += DJ[24 * j + 4 * row + c] * (row < 3 ? gi[VSMPC_IN_LLIN + 8 * row + j] : gi[VSMPC_IN_LANG + 8 * (row - 3) + j]);
+        } else if (lane >= 16 && lane < 20) {
+            add += gi[VSMPC_IN_TD0 + lane - 16];
+        } else if (lane >= 20 && lane < 28) {                       // q: A_mom(q) and the posture error
+            const int j = lane - 20;
+            add = gi[VSMPC_IN_QERR + j];
+            for (int l = 0; l < 24; ++l) add += DJ[24 * j + l] * gi[VSMPC_IN_AMOM + l];
+        } else if (lane >= 28 && lane < 32) {
+            add = gi[VSMPC_IN_UPREV + lane - 28];
+        } else if (lane >= 32 && lane < 36) {
+            add = gi[VSMPC_IN_TDES + lane - 32];
+        } else if (lane >= 36 && lane < 40) {
+            add = gi[VSMPC_IN_TDDES + lane - 36];
+        }
+        __syncthreads();
+        if (tk % rd.ratio == rd.ratio - 1) {   // the FIFO shifted at this tick: the cotangent shifts back, column 0 was new to it
+            constexpr int KMAX = (12 * MAX_STAGES + RO_BLOCK - 1) / RO_BLOCK;
+            double keep[KMAX];
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k) {
+                const int e = lane + k * RO_BLOCK;
+                keep[k] = (e < nwin && e >= 12) ? wb[e - 12] : 0.0;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k) {
+                const int e = lane + k * RO_BLOCK;
+                if (e < nwin) wb[e] = keep[k];
+            }
+            __syncthreads();
+        }
+        if (a.first) {   // this tick filled the window: every column was frozen with this tick's R
+            if (lane >= 6 && lane < 9) {
+                const int ns0 = 1 + tk / rd.ratio;
+                for (int j = 0; j < nref; ++j) {
+                    int idx = ns0 - (nref - 1 - j);
+                    idx = idx > 0 ? idx : 0;
+                    idx = idx < rd.n_traj ? idx : rd.n_traj - 1;
+                    add += hlin_to_rpy(dR + 9 * (lane - 6), wb + 12 * j + 3, a.traj_vel + 3 * idx, m);
+                }
+            }
+            __syncthreads();
+            for (int e = lane; e < nwin; e += RO_BLOCK) wb[e] = 0.0;
+        }
+        if (lane < 40) sb[lane] += add;
+        __syncthreads();
+    }
+
+    double out0 = lane < 40 ? sb[lane] : 0.0;   // the new sbar of this lane's entry (the jet-plant slots carry nothing)
+    if (plant) {
+        __syncthreads();
+        if (lane < 14)   // the log row of this tick reads the state after it: p, rpy, T, throttle
+            sb[lane < 3 ? lane : lane < 6 ? 6 + lane - 3 : lane < 10 ? 12 + lane - 6 : VSMPC_PS_U + lane - 10] += lbar;
+        s[lane] = sp0;
+        if (lane + RO_BLOCK < VSMPC_PLANT_STATE) s[lane + RO_BLOCK] = sp1;
+        if (lane < VSMPC_FM_SIZE) f[lane] = fm;
+        __syncthreads();
+        const bool solved = st == VSMPC_STATUS_SOLVED;
+        const int tk = a.tick_plant + int(p[VSMPC_PP_TICK0]);
+        const int substeps = a.substeps;
+        if (lane >= 32 && lane < 32 + substeps && lane < 48) {
+            const int ss = lane - 32;
+            const double t = (double(tk) + double(ss) / double(substeps)) * rd.period_mpc;
+            alpha_s[ss] = interp_clamped(a.traj_alpha, rd.n_alpha, t / rd.alpha_dt);
+        }
+        if (solved) {   // the move the forward tick consumed
+            if (lane < 8) s[VSMPC_PS_Q + lane] += f[VSMPC_FM_DQ + lane];
+            if (lane >= 8 && lane < 12) s[VSMPC_PS_U + lane - 8] = f[VSMPC_FM_THROTTLE + lane - 8];
+        }
+        __syncthreads();
+        if (lane < 24) {
+            double acc = p[VSMPC_PP_AMOM0 + lane];
+            for (int j = 0; j < 8; ++j) acc += DJ[24 * j + lane] * (s[VSMPC_PS_Q + j] - p[VSMPC_PP_QREF0 + j]);
+            Aq[lane] = acc;
+        } else if (lane == 24) {
+            inv3(p + VSMPC_PP_INERTIA_B, IBi);
+        } else if (lane >= 28 && lane < 32) {
+            vthr[lane - 28] = Jet::v_of_throttle(s[VSMPC_PS_U + lane - 28]);
+        }
+        if (lane < 20) xs[lane] = s[lane];
+        __syncthreads();
+        const double h = rd.period_mpc / double(substeps);
+        // forward: the sub-steps of advance_kernel, every one's 20-vector kept (xs + 20 ss is the state IN FRONT of sub-step ss)
+        for (int ss = 0; ss + 1 < substeps; ++ss) {
+            const double* x = xs + 20 * ss;
+            const double t = (double(tk) + double(ss) / double(substeps)) * rd.period_mpc;
+            const double alpha = alpha_s[ss];
+            const bool dist = t >= p[VSMPC_PP_DIST_T0] && t < p[VSMPC_PP_DIST_T1];
+            if (lane < 3) {
+                double sn, cs;
+                sincos(x[6 + lane], &sn, &cs);
+                sc[2 * lane] = sn;
+                sc[2 * lane + 1] = cs;
+            } else if (lane >= 8 && lane < 11) {
+                const int i = lane - 8;
+                omv[i] = IBi[3 * i] * x[9] + IBi[3 * i + 1] * x[10] + IBi[3 * i + 2] * x[11];
+            }
+            __syncthreads();
+            const double sr = sc[0], cr = sc[1], sp = sc[2], cp = sc[3], sy = sc[4], cy = sc[5];
+            if (lane == 0) {
+                R[0] = cy * cp; R[1] = cy * sp * sr - sy * cr; R[2] = cy * sp * cr + sy * sr;
+                R[3] = sy * cp; R[4] = sy * sp * sr + cy * cr; R[5] = sy * sp * cr - cy * sr;
+                R[6] = -sp;     R[7] = cp * sr;                R[8] = cp * cr;
+            }
+            __syncthreads();
+            double d = 0.0;
+            if (lane < 3) {
+                d = (R[3 * lane] * x[3] + R[3 * lane + 1] * x[4] + R[3 * lane + 2] * x[5]) / m;
+            } else if (lane < 6 || (lane >= 9 && lane < 12)) {
+                const bool lin = lane < 6;
+                const int r = lin ? lane - 3 : lane - 9, h0 = lin ? 3 : 9;
+                const int r1 = (r + 1) % 3, r2 = (r + 2) % 3;
+                const double cross = omv[r1] * x[h0 + r2] - omv[r2] * x[h0 + r1];
+                double fo = -cross;
+                if (lin) fo += alpha * m * (R[6 + r] * (-9.81));
+                for (int j = 0; j < 4; ++j) fo += Aq[4 * (lin ? r : 3 + r) + j] * x[12 + j];
+                if (dist)
+                    fo += lin ? R[r] * p[VSMPC_PP_DIST_F] + R[3 + r] * p[VSMPC_PP_DIST_F + 1] + R[6 + r] * p[VSMPC_PP_DIST_F + 2]
+                              : p[VSMPC_PP_DIST_TAU + r];
+                d = fo;
+            } else if (lane < 9) {
+                const double tp = sp / cp;
+                d = lane == 6 ? omv[0] + sr * tp * omv[1] + cr * tp * omv[2]
+                  : lane == 7 ? cr * omv[1] - sr * omv[2]
+                              : (sr * omv[1] + cr * omv[2]) / cp;
+            } else if (lane < 16) {
+                d = x[lane + 4];
+            } else if (lane < 20) {
+                const int j = lane - 16;
+                const double Tb = Jet::stdT(x[12 + j]), Tdb = Jet::stdTd(x[16 + j]);
+                d = Jet::sgT * (Jet::f(Tb, Tdb) + Jet::g(Tb, Tdb) * vthr[j]);
+            }
+            if (lane < 20) xs[20 * (ss + 1) + lane] = x[lane] + h * d;
+            __syncthreads();
+        }
+        // backward: lam = dL/d(the 20-vector behind sub-step ss); lanes 32..55 collect the cotangent of A_mom(q), 56..59 of v(u)
+        if (lane < 20) lam[lane] = sb[lane];
+        double abar = 0.0;
+        __syncthreads();
+        for (int ss = substeps - 1; ss >= 0; --ss) {
+            const double* x = xs + 20 * ss;
+            const double t = (double(tk) + double(ss) / double(substeps)) * rd.period_mpc;
+            const double alpha = alpha_s[ss];
+            const bool dist = t >= p[VSMPC_PP_DIST_T0] && t < p[VSMPC_PP_DIST_T1];
+            if (lane < 3) {
+                double sn, cs;
+                sincos(x[6 + lane], &sn, &cs);
+                sc[2 * lane] = sn;
+                sc[2 * lane + 1] = cs;
+            } else if (lane >= 8 && lane < 11) {
+                const int i = lane - 8;
+                omv[i] = IBi[3 * i] * x[9] + IBi[3 * i + 1] * x[10] + IBi[3 * i + 2] * x[11];
+            }
+            __syncthreads();
+            const double sr = sc[0], cr = sc[1], sp = sc[2], cp = sc[3], sy = sc[4], cy = sc[5];
+            const double tp = sp / cp;
+            if (lane == 0) {
+                rot_partials(sr, cr, sp, cp, sy, cy, R, dR);
+            } else if (lane >= 1 && lane < 4) {
+                // cotangent of omega: -omega x h in both momenta, and rpy' = W^-1(rpy) omega
+                const int i = lane - 1, i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+                double o = (lam[3 + i1] * x[3 + i2] - lam[3 + i2] * x[3 + i1]) + (lam[9 + i1] * x[9 + i2] - lam[9 + i2] * x[9 + i1]);
+                o += i == 0 ? lam[6]
+                   : i == 1 ? sr * tp * lam[6] + cr * lam[7] + sr / cp * lam[8]
+                            : cr * tp * lam[6] - sr * lam[7] + cr / cp * lam[8];
+                omb[i] = o;
+            }
+            __syncthreads();
+            double g = 0.0;
+            if (lane >= 3 && lane < 6) {           // h_lin: p' = R h_lin / m, -omega x h_lin
+                const int c = lane - 3, c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+                g = (R[c] * lam[0] + R[3 + c] * lam[1] + R[6 + c] * lam[2]) / m + (omv[c1] * lam[3 + c2] - omv[c2] * lam[3 + c1]);
+            } else if (lane >= 6 && lane < 9) {    // rpy: R in p' and in R^T (alpha m g + push), W^-1
+                const double* dRa = dR + 9 * (lane - 6);
+                double fw[3] = {0.0, 0.0, alpha * m * (-9.81)};
+                if (dist) { fw[0] += p[VSMPC_PP_DIST_F]; fw[1] += p[VSMPC_PP_DIST_F + 1]; fw[2] += p[VSMPC_PP_DIST_F + 2]; }
+                for (int r = 0; r < 3; ++r) {
+                    g += lam[r] * (dRa[3 * r] * x[3] + dRa[3 * r + 1] * x[4] + dRa[3 * r + 2] * x[5]) / m;
+                    g += (dRa[3 * r] * lam[3] + dRa[3 * r + 1] * lam[4] + dRa[3 * r + 2] * lam[5]) * fw[r];
+                }
+                if (lane == 6)
+                    g += lam[6] * (cr * tp * omv[1] - sr * tp * omv[2]) + lam[7] * (-sr * omv[1] - cr * omv[2])
+                       + lam[8] * (cr * omv[1] - sr * omv[2]) / cp;
+                else if (lane == 7)
+                    g += lam[6] * (sr * omv[1] + cr * omv[2]) / (cp * cp) + lam[8] * (sr * omv[1] + cr * omv[2]) * tp / cp;
+            } else if (lane >= 9 && lane < 12) {   // h_ang: -omega x h_ang, and omega = I_B^-1 h_ang
+                const int c = lane - 9, c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+                g = (omv[c1] * lam[9 + c2] - omv[c2] * lam[9 + c1]) + IBi[c] * omb[0] + IBi[3 + c] * omb[1] + IBi[6 + c] * omb[2];
+            } else if (lane >= 12 && lane < 20) {  // T, Tdot: A_mom(q) T, T' = Tdot, the jet polynomial
+                const int j = (lane - 12) & 3;
+                const double Tb = Jet::stdT(x[12 + j]), Tdb = Jet::stdTd(x[16 + j]);
+                if (lane < 16) {
+                    for (int r = 0; r < 3; ++r) g += lam[3 + r] * Aq[4 * r + j] + lam[9 + r] * Aq[4 * (3 + r) + j];
+                    g += lam[16 + j] * (Jet::df_dT(Tb, Tdb) + Jet::dg_dT(Tb, Tdb) * vthr[j]);
+                } else {
+                    g = lam[12 + j] + lam[16 + j] * (Jet::df_dTd(Tb, Tdb) + Jet::dg_dTd(Tb, Tdb) * vthr[j]);
+                }
+            } else if (lane >= 32 && lane < 56) {  // A_mom(q) T is bilinear: row (lane - 32) / 4 of the momenta, thrust column
+                const int l = lane - 32, row = l >> 2;
+                abar += h * lam[row < 3 ? 3 + row : 9 + row - 3] * x[12 + (l & 3)];
+            } else if (lane >= 56 && lane < 60) {
+                const int j = lane - 56;
+                abar += h * lam[16 + j] * Jet::sgT * Jet::g(Jet::stdT(x[12 + j]), Jet::stdTd(x[16 + j]));
+            }
+            __syncthreads();
+            if (lane < 20) lam[lane] += h * g;
+            __syncthreads();
+        }
+        if (lane >= 32 && lane < 56) Ab[lane - 32] = abar;
+        if (lane >= 56 && lane < 60) vb[lane - 56] = abar;
+        __syncthreads();
+        double fmb = 0.0;
+        if (lane < 20) {
+            out0 = lam[lane];
+        } else if (lane < 28) {                    // q through A_mom(q); the move added dq to it
+            const int j = lane - 20;
+            double q = sb[lane];
+            for (int l = 0; l < 24; ++l) q += DJ[24 * j + l] * Ab[l];
+            out0 = q;
+        } else if (lane < 32) {                    // the latched throttle through v(u)
+            const int j = lane - 28;
+            out0 = sb[lane] + vb[j] * Jet::dv_du(Jet::stdU(s[VSMPC_PS_U + j])) * Jet::isgU;
+        } else if (lane < 40) {
+            out0 = sb[lane];
+        }
+        // Solved: the move overwrote the latched entries and was added to q; otherwise it was not consumed
+        if (solved && lane >= 20 && lane < 40) {
+            fmb = out0;
+            if (lane >= 28) out0 = 0.0;
+        }
+        if (lane >= 20 && lane < 40) sb[lane] = fmb;
+        __syncthreads();
+        if (lane < VSMPC_FM_SIZE) {
+            // first move: DQ 0:8 | V0 8:12 | THROTTLE 12:16 | THRUST 16:20 | THRUSTDOT 20:24; state: Q 20 | U 28 | TDES 32 | TDDES 36
+            const double v = lane < 8 ? sb[VSMPC_PS_Q + lane] : lane < 12 ? 0.0 : sb[VSMPC_PS_U + lane - 12];
+            a.fmbar[size_t(b) * VSMPC_FM_SIZE + lane] = v;
+        }
+    }
+    a.sbar[size_t(b) * VSMPC_PLANT_STATE + lane] = out0;
+    if (lane + RO_BLOCK < VSMPC_PLANT_STATE) a.sbar[size_t(b) * VSMPC_PLANT_STATE + lane + RO_BLOCK] = 0.0;
+    for (int e = lane; e < nwin; e += RO_BLOCK) a.wbar[size_t(b) * nwin + e] = wb[e];
+}
+
+hipError_t launch_advance_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream) {
+    hipLaunchKernelGGL(advance_adjoint_kernel, dim3(a.batch), dim3(RO_BLOCK), 0, stream, rd, a);
+    return hipGetLastError();
+}
+
+}  // namespace vsmpc

@@ -168,10 +168,11 @@ class ClosedLoopRollout:
     """`batch` closed loops resident on one GPU.  reset() uploads plant states, run(ticks) advances them."""
 
     def __init__(self, cfg: L.MPCConfig, batch: int, traj_pos, traj_vel, traj_alpha, alpha_dt: float, device: int = 0,
-                 runtime: str = "never"):
+                 runtime: str = "never", adjoint: bool = False):
+        """adjoint: create the handle with what backward() needs (VSMPC_CREATE_ADJOINT_RECORD)"""
         self.cfg = cfg
         self.batch = batch
-        self.mpc = BatchedVSMPC(cfg, device=device, max_batch=batch, runtime=runtime)   # runtime: see BatchedVSMPC
+        self.mpc = BatchedVSMPC(cfg, device=device, max_batch=batch, runtime=runtime, adjoint_record=adjoint)   # runtime: see BatchedVSMPC
         self.lib = self.mpc.lib
         pos = np.ascontiguousarray(traj_pos, dtype=np.float64)
         vel = np.ascontiguousarray(traj_vel, dtype=np.float64)
@@ -248,12 +249,44 @@ class ClosedLoopRollout:
         _lib.check(self.lib.vsmpc_rollout_set_jet_plant(self._r, None if jet_model is None else jet_model._h, _ptr(Q), _ptr(R)),
                    "vsmpc_rollout_set_jet_plant")
 
-    def run(self, ticks: int, log: bool = True, stream=None):
-        """Advances every instance by `ticks` MPC periods.  Returns the log [ticks, batch, ROLLOUT_LOG] or None."""
+    def run(self, ticks: int, log: bool = True, stream=None, tape: bool = False):
+        """Advances every instance by `ticks` MPC periods.  Returns the log [ticks, batch, ROLLOUT_LOG] or None.
+        tape: the taped run (vsmpc_rollout_run_taped): the same results bit for bit, and what backward() sweeps over."""
         out = np.empty((ticks, self.batch, L.ROLLOUT_LOG)) if log else None
         s = None if stream is None else ctypes.c_void_p(stream.cuda_stream)
-        _lib.check(self.lib.vsmpc_rollout_run(self._r, int(ticks), _ptr(out), s), "vsmpc_rollout_run")
+        entry = "vsmpc_rollout_run_taped" if tape else "vsmpc_rollout_run"
+        _lib.check(getattr(self.lib, entry)(self._r, int(ticks), _ptr(out), s), entry)
+        self._taped = int(ticks) if tape else 0
         return out
+
+    def backward(self, log_bar=None, state_bar=None) -> dict:
+        """vsmpc_rollout_backward over the last run(ticks, tape=True): the gradient of a loss on the flown trajectory, given
+        as log_bar [ticks, batch, ROLLOUT_LOG] = dL/d(log rows) (columns 14, 15 ignored) and / or state_bar [batch,
+        PLANT_STATE] = dL/d(final plant state).  Returns grad_state0 [batch, PLANT_STATE] (dL/d the plant state at the start
+        of that run, entries 0..39), grad_gains [batch, L.GRAD_SIZE] (field values in L.GRAD_* order, summed over the ticks;
+        per loop under its own row with set_tunables) and flags [batch] (OR over the ticks of L.ADJ_*).  Needs adjoint=True."""
+        ticks = getattr(self, "_taped", 0)
+        lb = None if log_bar is None else np.ascontiguousarray(log_bar, dtype=np.float64)
+        sb = None if state_bar is None else np.ascontiguousarray(state_bar, dtype=np.float64)
+        if lb is not None and lb.shape != (ticks, self.batch, L.ROLLOUT_LOG):
+            raise ValueError(f"log_bar must be [{ticks}, {self.batch}, {L.ROLLOUT_LOG}], the log of the taped run")
+        if sb is not None and sb.shape != (self.batch, L.PLANT_STATE):
+            raise ValueError(f"state_bar must be [{self.batch}, {L.PLANT_STATE}]")
+        out = {"grad_state0": np.empty((self.batch, L.PLANT_STATE)), "grad_gains": np.empty((self.batch, L.GRAD_SIZE)),
+               "flags": np.empty(self.batch, dtype=np.int32)}
+        _lib.check(self.lib.vsmpc_rollout_backward(self._r, _ptr(lb), _ptr(sb), _ptr(out["grad_state0"]), _ptr(out["grad_gains"]),
+                                                   _ptr(out["flags"]), None), "vsmpc_rollout_backward")
+        return out
+
+    def backward_device(self, d_log_bar, d_state_bar, d_grad_state0, d_grad_gains, d_flags, stream=None):
+        """vsmpc_rollout_backward_device: backward() on contiguous CUDA tensors (None: not given / not wanted); only enqueues,
+        on `stream` or torch's current stream"""
+        from .solver import _assert_f64_device, _dptr, _stream
+        _assert_f64_device(d_log_bar, d_state_bar, d_grad_state0, d_grad_gains)
+        ref_t = d_log_bar if d_log_bar is not None else d_state_bar
+        _lib.check(self.lib.vsmpc_rollout_backward_device(self._r, _dptr(d_log_bar), _dptr(d_state_bar), _dptr(d_grad_state0),
+                                                          _dptr(d_grad_gains), _dptr(d_flags), _stream(ref_t, stream)),
+                   "vsmpc_rollout_backward_device")
 
     def state(self) -> np.ndarray:
         out = np.empty((self.batch, L.PLANT_STATE))

@@ -1,0 +1,110 @@
+"""Time per tick of the rollout's backward sweep (vsmpc_rollout_backward_device) against the forward tick (vsmpc_rollout_run,
+graph replay), the taped forward tick (vsmpc_rollout_run_taped, direct launches and the tape's copies) and the record-adjoint
+launch alone (vsmpc_adjoint_record_batch_device on the records of one tick, the launch every tick of the sweep contains).
+
+    python tools/rollout_adjoint_bench.py [--out profiles/rollout_adjoint_bench.txt] [--rounds 7]
+
+Workloads: batch 256 hover and batch 4096 take-off at the paper horizon (17, 7, 12), tuned handle.  Host clock around calls
+that end in a synchronise; the four kinds ALTERNATE, `rounds` windows each after a warm-up window of all, and the report is
+the median and the min..max spread of each and the ratios of the medians -- all in one process, one box.  A record, not a
+gate."""
+from __future__ import annotations
+
+import argparse
+import importlib
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = "paper_gorbani_2025_humanoids_multi-rate-mpc-ironcub_amd"
+CASES = [("hover", 256, 50), ("takeoff", 4096, 25)]            # workload, batch, ticks per window (>= the graph's 25)
+
+
+def run_case(workload, batch, ticks, rounds):
+    import torch
+    layout = importlib.import_module(PKG + ".layout")
+    ro = importlib.import_module(PKG + ".rollout")
+    cfg = layout.paper_config()
+    st, pa = ro.make_plant(cfg, batch, workload=workload)
+    pos, vel, alpha, adt = ro.make_trajectory(cfg, workload, 60.0)
+    r = ro.ClosedLoopRollout(cfg, batch, pos, vel, alpha, adt, device=0, adjoint=True)
+    m = r.mpc
+    dev = torch.device("cuda:0")
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    rng = np.random.default_rng(0)
+    d_lb = torch.from_numpy(rng.standard_normal((ticks, batch, layout.ROLLOUT_LOG))).to(dev)
+    d_sb = torch.from_numpy(rng.standard_normal((batch, layout.PLANT_STATE))).to(dev)
+    d_g0, d_gg, d_fl = torch.empty((batch, layout.PLANT_STATE), **f64), torch.empty((batch, layout.GRAD_SIZE), **f64), torch.empty(batch, **i32)
+    d_xbar, d_fmbar = torch.zeros((batch, m.n_var), **f64), torch.from_numpy(rng.standard_normal((batch, 24))).to(dev)
+    d_st, d_gc, d_gin = torch.empty(batch, **i32), torch.empty((batch, layout.GRAD_SIZE), **f64), torch.empty((batch, m.n_in), **f64)
+    d_afl = torch.empty(batch, **i32)
+    r.reset(st, pa)
+    d_rec = torch.from_numpy(r.next_records()).to(dev)
+    s = torch.cuda.current_stream(dev)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / ticks         # us per tick
+
+    def record_alone():
+        for _ in range(ticks):
+            m.solve_adjoint_record_device(d_rec, None, d_xbar, d_fmbar, None, None, d_st, None, None, d_gc, None, d_afl, d_gin,
+                                          None, stream=s)
+
+    kinds = {
+        "forward": lambda: r.run(ticks, log=False),
+        "forward_taped": lambda: r.run(ticks, log=False, tape=True),
+        "backward": lambda: r.backward_device(d_lb, d_sb, d_g0, d_gg, d_fl, stream=s),      # (sweeps the tape in front of it)
+        "record_alone": record_alone,
+    }
+    for fn in kinds.values():                                    # warm-up window of all (builds the graph, grows the tape)
+        timed(fn)
+    r.reset(st, pa)
+    t = {k: [] for k in kinds}
+    for _ in range(rounds):
+        for k, fn in kinds.items():
+            t[k].append(timed(fn))
+    flags = d_fl.cpu().numpy()
+    med = {k: statistics.median(v) for k, v in t.items()}
+    lines = [f"paper {workload} batch {batch} ({m.kernel_name}), {rounds} alternating windows of {ticks} ticks; last sweep: "
+             f"{int((flags & layout.ADJ_UNSOLVED != 0).sum())} loops with an unsolved tick, "
+             f"{int((flags & layout.ADJ_DEGENERATE != 0).sum())} with a degenerate one, "
+             f"gradients finite: {bool(torch.isfinite(d_g0).all()) and bool(torch.isfinite(d_gg).all())}"]
+    for k in kinds:
+        lines.append(f"  {k:14s}  median {med[k]:10.2f} us/tick  ({med[k] / batch:.4f} us per loop and tick)  min {min(t[k]):10.2f}  "
+                     f"max {max(t[k]):10.2f}  spread {100.0 * (max(t[k]) - min(t[k])) / med[k]:.2f} %")
+    for k, base in (("forward_taped", "forward"), ("backward", "forward"), ("backward", "record_alone")):
+        ratios = [a / b for a, b in zip(t[k], t[base])]
+        lines.append(f"  {k} / {base} (medians) {med[k] / med[base]:.4f}   per round min {min(ratios):.4f} max {max(ratios):.4f}")
+    lines.append(f"  backward - record_alone (medians) {med['backward'] - med['record_alone']:.2f} us/tick: advance_adjoint_kernel and "
+                 f"the gaps between the two launches of a tick")
+    r.close()
+    return lines
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--rounds", type=int, default=7)
+    a = ap.parse_args()
+    sys.path.insert(0, ROOT)
+    import torch
+    lines = [f"python tools/rollout_adjoint_bench.py --rounds {a.rounds} on {torch.cuda.get_device_name(0)}"]
+    for workload, batch, ticks in CASES:
+        lines += run_case(workload, batch, ticks, a.rounds)
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
