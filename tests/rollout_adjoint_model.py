@@ -31,6 +31,19 @@ L = pm.L
 NS = 40                      # live entries of the plant state (the jet-plant slots behind them carry no gradient)
 GRAV = 9.81
 MUTATIONS = ("window_late", "release_off_by_one", "drop_dv_du", "drop_amom_qbar", "unsolved_as_solved")
+# what tests/rollout_adjoint_edge_cases.py is there to catch, one line of the sweep each (kept apart from MUTATIONS, which
+# test_rollout_adjoint_model.py requires the four loops of rollout_adjoint_cases.py to catch: they let most of these through)
+EDGE_MUTATIONS = (
+    "drot_sign",            # d R[1][0] / d pitch = -sy sp, second order at rpy = 0, with the wrong sign
+    "drop_winv_pitch",      # the pitch derivative of W^-1(rpy) is dropped
+    "inertia_half",         # I_G = R I_B R^T pulled back through dR I_B R^T alone, without R I_B dR^T
+    "alpha_per_tick",       # alpha-gravity sampled at the tick's start for every sub-step
+    "dist_per_tick",        # the disturbance window tested at the tick's start for every sub-step
+    "push_unclamped",       # the pushed column's trajectory sample is not clamped at the end of the track
+    "first_clamp_early",    # the `first` fill clamps one sample early
+    "h_1ms",                # the sub-step is 1 ms whatever period_mpc / substeps is
+    "limits_last_tick",     # grad_cfg's throttle limits are the last tick's, not the sum over the ticks
+    "shift_first_chunk")    # the window cotangent shifts back 12 entries within its first 64 entries only
 _JET = pm._JET
 
 
@@ -96,10 +109,17 @@ def solve_tick(cfg, rec):
     return fm, L.STATUS_SOLVED
 
 
-def forward(cfg, s0, p, traj, ticks, substeps=5, unsolved_ticks=()):
+def substeps_of(cfg):
+    """the plant's sub-steps per tick as vsmpc_rollout_create derives them: 1 ms each, at least 1 and at most 16 of them
+    (min(16, max(1, lround(period_mpc / 1 ms))); beyond 16 ms the sub-step is period_mpc / 16)"""
+    return min(16, max(1, int(math.floor(cfg.period_mpc / 1e-3 + 0.5))))
+
+
+def forward(cfg, s0, p, traj, ticks, substeps=None, unsolved_ticks=()):
     """One instance: (log [ticks, 16], final state, tape).  traj = (pos, vel, alpha, alpha_dt).  `unsolved_ticks`: ticks whose
     solve is reported as STATUS_MAX_ITER whatever it found, so that the move is not consumed (model tests only)."""
     pos, vel, alpha, alpha_dt = traj
+    substeps = substeps_of(cfg) if substeps is None else substeps
     model = tick_model.ReferenceTickModel(cfg, s0, p, pos, vel, alpha, fps_traj=int(round(1.0 / cfg.period_large)),
                                           fps_alpha=int(round(1.0 / alpha_dt)), ticks_before=int(p[L.PP_TICK0]),
                                           configured_elsewhere=True)
@@ -126,7 +146,7 @@ def loss(log, final, log_bar, state_bar):
 # ----------------------------------------------------------------------------------------------------------------------
 # the three transposes
 # ----------------------------------------------------------------------------------------------------------------------
-def drot(rpy):
+def drot(rpy, mutation=None):
     """R(rpy) of rollout_model.rot and its partials to roll, pitch, yaw"""
     r, p, y = rpy
     cr, sr, cp, sp, cy, sy = math.cos(r), math.sin(r), math.cos(p), math.sin(p), math.cos(y), math.sin(y)
@@ -139,6 +159,8 @@ def drot(rpy):
     dp = np.array([[-cy * sp, cy * cp * sr, cy * cp * cr],
                    [-sy * sp, sy * cp * sr, sy * cp * cr],
                    [-cp, -sp * sr, -sp * cr]])
+    if mutation == "drot_sign":
+        dp[1, 0] = sy * sp
     dy = np.array([[-sy * cp, -sy * sp * sr - cy * cr, -sy * sp * cr + cy * sr],
                    [cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
                    [0.0, 0.0, 0.0]])
@@ -150,9 +172,10 @@ def _dv_du(u):
     return am.dv_dthrottle(u)
 
 
-def plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next, substeps=5, mutation=None):
+def plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next, substeps=None, mutation=None):
     """Transpose of rollout_model.advance at (s, fm, status): sbar_next [40] = dL/d s_{t+1} -> (direct part of dL/d s_t [40],
     fmbar [24]).  The sub-steps are recomputed and kept, then run backwards."""
+    substeps = substeps_of(cfg) if substeps is None else substeps
     solved = status == L.STATUS_SOLVED or mutation == "unsolved_as_solved"
     s = np.array(s, dtype=float)
     if status == L.STATUS_SOLVED:                              # (the forward pass is never mutated)
@@ -166,7 +189,7 @@ def plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next,
     u = s[L.PS_U:L.PS_U + 4]
     vthr = np.array([_JET.compute_v(_JET.standardizeThrottle_u2T(v)) for v in u])
     co, (muT, sgT, _, _) = ref.JET_COEFF, ref.JET_NORM
-    h = cfg.period_mpc / substeps
+    h = 1e-3 if mutation == "h_1ms" else cfg.period_mpc / substeps
     xs, x = [], s[0:20].copy()
     for ss in range(substeps):                                 # the forward sub-steps, as rollout_model.advance takes them
         xs.append(x.copy())
@@ -176,9 +199,10 @@ def plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next,
     for ss in range(substeps - 1, -1, -1):
         x = xs[ss]
         t = (tk + ss / substeps) * cfg.period_mpc
-        alpha = pm.interp_clamped(alpha_track, t / alpha_dt)
-        dist = p[L.PP_DIST_T0] <= t < p[L.PP_DIST_T1]
-        R, dR = drot(x[6:9])
+        t_tick = tk * cfg.period_mpc
+        alpha = pm.interp_clamped(alpha_track, (t_tick if mutation == "alpha_per_tick" else t) / alpha_dt)
+        dist = p[L.PP_DIST_T0] <= (t_tick if mutation == "dist_per_tick" else t) < p[L.PP_DIST_T1]
+        R, dR = drot(x[6:9], mutation)
         om = IBi @ x[9:12]
         lp, ll, lr, la = lam[0:3], lam[3:6], lam[6:9], lam[9:12]
         hl, ha, T = x[3:6], x[9:12], x[12:16]
@@ -197,7 +221,8 @@ def plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next,
         for a in range(3):
             g[6 + a] = lp @ (dR[a] @ hl) / m + (dR[a] @ ll) @ fw
         g[6] += lr @ (dEr @ om)
-        g[7] += lr @ (dEp @ om)
+        if mutation != "drop_winv_pitch":
+            g[7] += lr @ (dEp @ om)
         g[12:16] = A[0:3].T @ ll + A[3:6].T @ la
         for j in range(4):
             Tb, Tdb = (x[12 + j] - muT) / sgT, x[16 + j] / sgT
@@ -269,7 +294,7 @@ def record_adjoint(cfg, s, p, tk, first, traj_vel, gin, sbar, wbar, mutation=Non
     IB = p[L.PP_INERTIA_B:L.PP_INERTIA_B + 9].reshape(3, 3)
     IBi = np.linalg.inv(IB)
     DJ = p[L.PP_DJ:L.PP_DJ + 192].reshape(8, 6, 4)
-    R, dR = drot(s[L.PS_RPY:L.PS_RPY + 3])
+    R, dR = drot(s[L.PS_RPY:L.PS_RPY + 3], mutation)
     w = wbar + gin[ref.IN_XREF:ref.IN_XREF + 12 * nref].reshape(nref, 12)
     x0b = gin[ref.IN_X0:ref.IN_X0 + 26]
     sbar[0:20] += x0b[0:20]                                    # X0: identity (the unwrapped RPY has derivative 1)
@@ -280,7 +305,8 @@ def record_adjoint(cfg, s, p, tk, first, traj_vel, gin, sbar, wbar, mutation=Non
     Gw = gin[ref.IN_WRB:ref.IN_WRB + 9].reshape(3, 3)
     Gi = gin[ref.IN_INERTIA:ref.IN_INERTIA + 9].reshape(3, 3)
     for a in range(3):
-        sbar[6 + a] += (Gw * dR[a]).sum() + (Gi * (dR[a] @ IB @ R.T + R @ IB @ dR[a].T)).sum()
+        partner = 0.0 if mutation == "inertia_half" else R @ IB @ dR[a].T
+        sbar[6 + a] += (Gw * dR[a]).sum() + (Gi * (dR[a] @ IB @ R.T + partner)).sum()
     sbar[6:9] += gin[ref.IN_RPY:ref.IN_RPY + 3]
     sbar[9:12] += IBi.T @ gin[ref.IN_OMEGA:ref.IN_OMEGA + 3]
     sbar[L.PS_Q:L.PS_Q + 8] += np.einsum("jl,l->j", DJ.reshape(8, 24), gin[ref.IN_AMOM:ref.IN_AMOM + 24]) \
@@ -295,17 +321,24 @@ def record_adjoint(cfg, s, p, tk, first, traj_vel, gin, sbar, wbar, mutation=Non
     n_traj = len(traj_vel)
     release = ((tk + 1) % ratio == ratio - 1) if mutation == "release_off_by_one" else (tk % ratio == ratio - 1)
     if release:
-        v = traj_vel[_sample(cfg, n_traj, 1 + (tk + 1) // ratio)]
+        idx = 1 + (tk + 1) // ratio
+        if mutation == "push_unclamped" and idx >= n_traj:     # reads behind the track: whatever lies there, zeros here
+            v = np.zeros(3)
+        else:
+            v = traj_vel[_sample(cfg, n_traj, idx)]
         pushed = nref - 2 if mutation == "window_late" and nref > 1 else nref - 1
         for a in range(3):
             sbar[6 + a] += (dR[a] @ w[pushed, 3:6]) @ (m * v)
         prev = np.zeros_like(w)
         prev[1:] = w[:-1]
+        if mutation == "shift_first_chunk":                    # entries 64 .. stay where they were
+            prev.reshape(-1)[64:] = w.reshape(-1)[64:]
         w = prev
     if first:                                                  # every column was frozen with the R of this tick
         ns0 = 1 + tk // ratio
         for j in range(nref):
-            v = traj_vel[_sample(cfg, n_traj, ns0 - (nref - 1 - j))]
+            v = traj_vel[_sample(cfg, n_traj - 1 if mutation == "first_clamp_early" and n_traj > 1 else n_traj,
+                                 ns0 - (nref - 1 - j))]
             for a in range(3):
                 sbar[6 + a] += (dR[a] @ w[j, 3:6]) @ (m * v)
         w = np.zeros_like(w)
@@ -315,14 +348,16 @@ def record_adjoint(cfg, s, p, tk, first, traj_vel, gin, sbar, wbar, mutation=Non
 # ----------------------------------------------------------------------------------------------------------------------
 # the sweep
 # ----------------------------------------------------------------------------------------------------------------------
-def backward(cfg, tape, p, traj, log_bar, state_bar, substeps=5, first=True, tick_base=0, mutation=None):
-    """One instance: grad_state0 [40], grad_cfg [32], flags, and the per-tick flags.  tape = forward()'s; log_bar [ticks, 16]
-    (columns 14, 15 ignored) or None, state_bar [>= 40] or None."""
+def backward(cfg, tape, p, traj, log_bar, state_bar, substeps=None, first=True, tick_base=0, mutation=None):
+    """One instance: grad_state0 [40], grad_cfg [32], flags, the per-tick flags and the per-tick states of the QP's throttles
+    (sensitivity_model.FREE / LOWER / UPPER / pinned; None for a tick that is not Solved) with the throttles themselves and
+    their limits.  tape = forward()'s; log_bar [ticks, 16] (columns 14, 15 ignored) or None, state_bar [>= 40] or None."""
+    substeps = substeps_of(cfg) if substeps is None else substeps
     _, vel, alpha, alpha_dt = traj
     ticks = len(tape)
     sbar = np.zeros(NS) if state_bar is None else np.array(state_bar[:NS], dtype=float)
     wbar = np.zeros((cfg.n_ref_cols, 12))
-    gcfg, flags, tick_flags = np.zeros(am.GRAD_SIZE), 0, []
+    gcfg, flags, tick_flags, tick_active, tick_v = np.zeros(am.GRAD_SIZE), 0, [], [], []
     xbar0 = np.zeros(cfg.n_var)
     for t in range(ticks - 1, -1, -1):
         s, rec, fm, status = tape[t]
@@ -335,22 +370,30 @@ def backward(cfg, tape, p, traj, log_bar, state_bar, substeps=5, first=True, tic
         if status == L.STATUS_SOLVED:
             adj = am.condensed_adjoint(cfg, rec, xbar0, fmbar)
             gin = arm.condensed_record_adjoint(cfg, rec, xbar0, fmbar)["grad_in"]
-            gcfg += adj["grad_cfg"]
+            gt = adj["grad_cfg"].copy()
+            if mutation == "limits_last_tick" and t != ticks - 1:
+                gt[29:31] = 0.0
+            gcfg += gt
             f = int(adj["flags"])
+            tick_active.append(adj["active"])
+            tick_v.append(adj["x"][cfg.off_throttle:])
         else:
             gin, f = np.zeros(cfg.n_in), am.UNSOLVED
+            tick_active.append(None)
+            tick_v.append(None)
         flags |= f
         tick_flags.append(f)
         wbar = record_adjoint(cfg, s, p, tick_base + t + int(p[L.PP_TICK0]), first and tick_base + t == 0, vel, gin, sbar, wbar,
                               mutation)
-    return {"grad_state0": sbar, "grad_cfg": gcfg, "flags": flags, "tick_flags": tick_flags[::-1]}
+    return {"grad_state0": sbar, "grad_cfg": gcfg, "flags": flags, "tick_flags": tick_flags[::-1],
+            "tick_active": tick_active[::-1], "tick_v": tick_v[::-1]}
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # central differences of the forward loop
 # ----------------------------------------------------------------------------------------------------------------------
-def central(cfg, s0, p, traj, ticks, log_bar, state_bar, d_state=None, d_gains=None, step=1e-4, substeps=5, unsolved_ticks=(),
-            richardson=True):
+def central(cfg, s0, p, traj, ticks, log_bar, state_bar, d_state=None, d_gains=None, step=1e-4, substeps=None,
+            unsolved_ticks=(), richardson=True):
     """Directional derivative of the loss of `forward` along (d_state [40], d_gains [32]) (either may be None): central
     differences with the step `step`, Richardson extrapolated with step / 2 (O(h^4))."""
     g0 = gains_of(cfg)
