@@ -5,6 +5,16 @@ using namespace vsmpc;
 
 namespace {
 
+// the launch record of the rollout's two kernels (in RolloutTick's order): its own rows, the handle's solve outputs as scratch
+RolloutTick tick_record(const vsmpc_rollout* r) {
+    const vsmpc_handle* h = r->h;
+    return {r->batch, r->substeps, r->d_state, r->d_params, r->d_tick, r->d_tpos, r->d_tvel, r->d_talpha, r->d_tstate, r->d_rec,
+            h->d_fm, h->d_status, h->d_iters, r->d_ctl};
+}
+
+// a failed allocation is VSMPC_ERR_ALLOC, any other HIP failure of `what` VSMPC_ERR_HIP
+int alloc_fail(hipError_t e, const char* what) { return e == hipErrorOutOfMemory ? VSMPC_ERR_ALLOC : hip_fail(e, what); }
+
 // Tree plant of a rollout: provider on the body-frame states (joints + this tick's move when `fm` is given), then the
 // kinematics terms of those records (I_B for the plant's integration; the Lambda terms are formed again after the advance,
 // with the thrusts it measured).  The handle's kinematics buffers are the rollout's scratch, like its solve buffers.
@@ -85,7 +95,7 @@ int vsmpc_rollout_create(vsmpc_handle* h, int batch, const double* traj_pos, con
     if (e == hipSuccess) e = hipStreamCreateWithFlags(r->own_stream.put(), hipStreamNonBlocking);
     if (e != hipSuccess) {
         vsmpc_rollout_destroy(r);
-        return e == hipErrorOutOfMemory ? VSMPC_ERR_ALLOC : hip_fail(e, "vsmpc_rollout_create");
+        return alloc_fail(e, "vsmpc_rollout_create");
     }
     *out = r;
     return VSMPC_OK;
@@ -110,8 +120,7 @@ int vsmpc_rollout_reset(vsmpc_rollout* r, const double* state, const double* par
     // record of tick 0; from here on every tick's advance kernel leaves the record of the following tick
     r->valid = 0;
     if (r->use_tree) HIP_TRY(enqueue_tree(r, nullptr, nullptr, nullptr));
-    HIP_TRY(launch_record(r->rd, r->batch, r->d_state, r->d_params, r->d_tick, r->d_tpos, r->d_tvel, r->d_talpha,
-                          r->d_tstate, r->d_rec, nullptr));
+    HIP_TRY(launch_record(r->rd, tick_record(r), nullptr));
     if (r->use_tree) HIP_TRY(enqueue_tree_lambda(r, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     r->valid = 1;
@@ -201,16 +210,25 @@ namespace {
 
 constexpr int GRAPH_TICKS = 25;  // ticks per captured graph (50 kernel nodes)
 
-// one closed-loop tick: two launches on `s` (solve, advance + next record), the stream order is the only
-// synchronisation the loop needs
-hipError_t enqueue_tick(vsmpc_rollout* r, hipStream_t s) {
+// One closed-loop tick: two launches on `s` (solve, advance + next record), the stream order is the only
+// synchronisation the loop needs.  With tape_row >= 0 the tape's rows of that tick of the run are copied out between the
+// launches (state and record in front of the solve, first move and status behind it); -1 is the plain tick, kernels only.
+hipError_t enqueue_tick(vsmpc_rollout* r, hipStream_t s, int tape_row) {
     vsmpc_handle* h = r->h;
-    hipError_t e = solve_launch(h, r->d_rec, r->batch, h->d_x, h->d_fm, h->d_status, h->d_iters, 0, s,
-                                r->use_tun ? r->d_tun : nullptr);
-    if (e == hipSuccess && r->use_tree) e = enqueue_tree(r, h->d_fm, h->d_status, s);   // A_mom, I_B of the joints after the move
+    vsmpc_rollout::Tape& tp = r->tape;
+    const bool taped = tape_row >= 0;
+    const size_t B = size_t(r->batch), o = taped ? size_t(tape_row) * B : 0;
+    auto keep = [&](void* dst, const void* src, size_t bytes) {
+        return taped ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+    };
+    hipError_t e = keep(tp.s + o * VSMPC_PLANT_STATE, r->d_state, B * VSMPC_PLANT_STATE * sizeof(double));
+    if (e == hipSuccess) e = keep(tp.rec + o * h->n_in, r->d_rec, B * h->n_in * sizeof(double));
     if (e == hipSuccess)
-        e = launch_advance(r->rd, r->batch, r->d_state, r->d_params, r->d_tick, h->d_fm, h->d_status, h->d_iters,
-                           r->d_talpha, r->d_ctl, r->substeps, r->d_tpos, r->d_tvel, r->d_tstate, r->d_rec, s);
+        e = solve_launch(h, r->d_rec, r->batch, h->d_x, h->d_fm, h->d_status, h->d_iters, 0, s, r->use_tun ? r->d_tun : nullptr);
+    if (e == hipSuccess) e = keep(tp.fm + o * VSMPC_FM_SIZE, h->d_fm, B * VSMPC_FM_SIZE * sizeof(double));
+    if (e == hipSuccess) e = keep(tp.status + o, h->d_status, B * sizeof(int));
+    if (e == hipSuccess && r->use_tree) e = enqueue_tree(r, h->d_fm, h->d_status, s);   // A_mom, I_B of the joints after the move
+    if (e == hipSuccess) e = launch_advance(r->rd, tick_record(r), s);
     if (e == hipSuccess && r->use_tree) e = enqueue_tree_lambda(r, s);
     return e;
 }
@@ -223,7 +241,7 @@ void build_tick_graph(vsmpc_rollout* r, hipStream_t s) {
     r->graph_small = small_batch_kernel(r->h, r->batch) ? 1 : 0;
     if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return; }
     hipError_t e = hipSuccess;
-    for (int t = 0; t < GRAPH_TICKS && e == hipSuccess; ++t) e = enqueue_tick(r, s);
+    for (int t = 0; t < GRAPH_TICKS && e == hipSuccess; ++t) e = enqueue_tick(r, s, -1);
     hipGraph_t graph = nullptr;
     const hipError_t e2 = hipStreamEndCapture(s, &graph);
     if (e == hipSuccess && e2 == hipSuccess && graph != nullptr &&
@@ -234,14 +252,13 @@ void build_tick_graph(vsmpc_rollout* r, hipStream_t s) {
     if (graph) (void)hipGraphDestroy(graph);
 }
 
-
 // what a run does in front of its ticks: the device log of `ticks` rows (grown when shorter) and the control block
 int begin_run(vsmpc_rollout* r, int ticks, double* log, hipStream_t s) {
     const size_t row = size_t(r->batch) * VSMPC_ROLLOUT_LOG;
     if (log != nullptr && r->log_ticks < ticks) {
         r->log_ticks = 0;
         hipError_t e = r->d_log.alloc(size_t(ticks) * row);   // (frees the shorter one first)
-        if (e != hipSuccess) return e == hipErrorOutOfMemory ? VSMPC_ERR_ALLOC : hip_fail(e, "vsmpc_rollout_run");
+        if (e != hipSuccess) return alloc_fail(e, "vsmpc_rollout_run");
         r->log_ticks = ticks;
     }
     const RolloutCtl ctl = {log ? r->d_log : nullptr, r->ticks_done, log ? ticks : 0};
@@ -293,24 +310,6 @@ hipError_t grow_tape(vsmpc_rollout* r, int ticks) {
     return e;
 }
 
-// enqueue_tick of the parametric plant with the tape's rows of tick `t` of this run copied out between its launches
-hipError_t enqueue_tick_taped(vsmpc_rollout* r, int t, hipStream_t s) {
-    vsmpc_handle* h = r->h;
-    vsmpc_rollout::Tape& tp = r->tape;
-    const size_t B = size_t(r->batch), o = size_t(t) * B;
-    auto keep = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s); };
-    hipError_t e = keep(tp.s + o * VSMPC_PLANT_STATE, r->d_state, B * VSMPC_PLANT_STATE * sizeof(double));
-    if (e == hipSuccess) e = keep(tp.rec + o * h->n_in, r->d_rec, B * h->n_in * sizeof(double));
-    if (e == hipSuccess)
-        e = solve_launch(h, r->d_rec, r->batch, h->d_x, h->d_fm, h->d_status, h->d_iters, 0, s, r->use_tun ? r->d_tun : nullptr);
-    if (e == hipSuccess) e = keep(tp.fm + o * VSMPC_FM_SIZE, h->d_fm, B * VSMPC_FM_SIZE * sizeof(double));
-    if (e == hipSuccess) e = keep(tp.status + o, h->d_status, B * sizeof(int));
-    if (e == hipSuccess)
-        e = launch_advance(r->rd, r->batch, r->d_state, r->d_params, r->d_tick, h->d_fm, h->d_status, h->d_iters,
-                           r->d_talpha, r->d_ctl, r->substeps, r->d_tpos, r->d_tvel, r->d_tstate, r->d_rec, s);
-    return e;
-}
-
 // The backward sweep over the tape, last tick to first, in stream order: tape.sbar holds dL/d(final state) on entry and
 // dL/d(state at the start of the taped run) on exit; tape.gcfg and tape.flags receive the sums over the ticks.  Launch k of
 // advance_adjoint_kernel is the record half of tick k behind the plant half of tick k - 1, with the record adjoint of tick
@@ -354,67 +353,73 @@ int enqueue_sweep(vsmpc_rollout* r, const double* d_log_bar, hipStream_t s) {
     return VSMPC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vsmpc_rollout_run(vsmpc_rollout* r, int ticks, double* log, void* stream) {
+// Both run entries.  `taped` keeps the tape of the run for vsmpc_rollout_backward, with direct launches (the captured graph has
+// no room for the copies between its kernels); the plain run replays the captured ticks where it can and leaves no tape.
+int run(vsmpc_rollout* r, int ticks, double* log, void* stream, bool taped) {
     if (r == nullptr || ticks < 0) return invalid_arg();
     if (!r->valid) return invalid_arg();   // never reset, or a previous run failed half-way: reset() first
+    if (taped) {                           // what the backward sweep has no transpose of
+        if (r->use_tree) return unsupported("vsmpc_rollout_run_taped: no adjoint of the kinematic-tree plant (vsmpc_rollout_set_tree)");
+        if (r->rd.jet_nn) return unsupported("vsmpc_rollout_run_taped: no adjoint of the jet plant option (vsmpc_rollout_set_jet_plant)");
+        if (r->rd.traj_rpyd != nullptr)
+            return unsupported("vsmpc_rollout_run_taped: no adjoint of an RPYDot track (vsmpc_rollout_set_attitude_tracks)");
+        r->tape.ticks = 0;
+    }
     if (ticks == 0) return VSMPC_OK;
     vsmpc_handle* h = r->h;
     ON_DEVICE(h->device);
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->own_stream.h;
+    if (taped)
+        if (const hipError_t e = grow_tape(r, ticks); e != hipSuccess)   // (the rollout itself is untouched: still runnable)
+            return alloc_fail(e, "vsmpc_rollout_run_taped");
     if (const int rc = begin_run(r, ticks, log, s); rc != VSMPC_OK) return rc;
     r->tape.ticks = 0;                  // the tape describes the run in front of this one
     r->valid = 0;                       // until the whole run has completed: a failure below leaves the counters ahead
     int t = 0;
-    // the captured launches are of the other condensing form, or of the other kernel for this batch size
-    if (r->graph_state != 0 && (r->graph_form != h->form || r->graph_small != (small_batch_kernel(h, r->batch) ? 1 : 0))) invalidate(r);
-    if (ticks >= GRAPH_TICKS && r->graph_state == 0) build_tick_graph(r, s);
-    if (r->graph_state == 1)
-        for (; ticks - t >= GRAPH_TICKS; t += GRAPH_TICKS) HIP_TRY(hipGraphLaunch(r->gexec, s));
-    for (; t < ticks; ++t) HIP_TRY(enqueue_tick(r, s));
-    return end_run(r, ticks, log, s);
-}
-
-int vsmpc_rollout_run_taped(vsmpc_rollout* r, int ticks, double* log, void* stream) {
-    if (r == nullptr || ticks < 0) return invalid_arg();
-    if (!r->valid) return invalid_arg();
-    // what the backward sweep has no transpose of
-    if (r->use_tree) return unsupported("vsmpc_rollout_run_taped: no adjoint of the kinematic-tree plant (vsmpc_rollout_set_tree)");
-    if (r->rd.jet_nn) return unsupported("vsmpc_rollout_run_taped: no adjoint of the jet plant option (vsmpc_rollout_set_jet_plant)");
-    if (r->rd.traj_rpyd != nullptr)
-        return unsupported("vsmpc_rollout_run_taped: no adjoint of an RPYDot track (vsmpc_rollout_set_attitude_tracks)");
-    vsmpc_handle* h = r->h;
-    ON_DEVICE(h->device);
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->own_stream.h;
-    r->tape.ticks = 0;
-    if (ticks == 0) return VSMPC_OK;
-    if (const hipError_t e = grow_tape(r, ticks); e != hipSuccess)   // (the rollout itself is untouched: still runnable)
-        return e == hipErrorOutOfMemory ? VSMPC_ERR_ALLOC : hip_fail(e, "vsmpc_rollout_run_taped");
-    if (const int rc = begin_run(r, ticks, log, s); rc != VSMPC_OK) return rc;
-    r->valid = 0;
-    // direct launches: the captured graph has no room for the copies between its kernels
-    for (int t = 0; t < ticks; ++t) HIP_TRY(enqueue_tick_taped(r, t, s));
+    if (!taped) {
+        // the captured launches are of the other condensing form, or of the other kernel for this batch size
+        if (r->graph_state != 0 && (r->graph_form != h->form || r->graph_small != (small_batch_kernel(h, r->batch) ? 1 : 0))) invalidate(r);
+        if (ticks >= GRAPH_TICKS && r->graph_state == 0) build_tick_graph(r, s);
+        if (r->graph_state == 1)
+            for (; ticks - t >= GRAPH_TICKS; t += GRAPH_TICKS) HIP_TRY(hipGraphLaunch(r->gexec, s));
+    }
+    for (; t < ticks; ++t) HIP_TRY(enqueue_tick(r, s, taped ? t : -1));
     if (const int rc = end_run(r, ticks, log, s); rc != VSMPC_OK) return rc;
-    r->tape.ticks = ticks;
-    r->tape.tick_base = r->ticks_done - ticks;
+    if (taped) {
+        r->tape.ticks = ticks;
+        r->tape.tick_base = r->ticks_done - ticks;
+    }
     return VSMPC_OK;
 }
 
+// what both backward entries refuse, in this order
+int backward_refusal(const vsmpc_rollout* r, const double* log_bar, const double* state_bar) {
+    if (r == nullptr || (log_bar == nullptr && state_bar == nullptr) || r->tape.ticks == 0) return invalid_arg();
+    if (!r->h->adjoint_record.on) return unsupported(BACKWARD_NEEDS_FLAG);
+    return VSMPC_OK;
+}
+// dL/d(final state) of the sweep: the caller's rows, from where `kind` says they live, or zeros
+hipError_t seed_sbar(vsmpc_rollout* r, const double* state_bar, hipMemcpyKind kind, hipStream_t s) {
+    const size_t bytes = size_t(r->batch) * VSMPC_PLANT_STATE * sizeof(double);
+    return state_bar != nullptr ? hipMemcpyAsync(r->tape.sbar, state_bar, bytes, kind, s) : hipMemsetAsync(r->tape.sbar, 0, bytes, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsmpc_rollout_run(vsmpc_rollout* r, int ticks, double* log, void* stream) { return run(r, ticks, log, stream, false); }
+
+int vsmpc_rollout_run_taped(vsmpc_rollout* r, int ticks, double* log, void* stream) { return run(r, ticks, log, stream, true); }
+
 int vsmpc_rollout_backward_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar, double* d_grad_state0,
                                   double* d_grad_cfg, int* d_flags, void* stream) {
-    if (r == nullptr || (d_log_bar == nullptr && d_state_bar == nullptr) || r->tape.ticks == 0) return invalid_arg();
-    if (!r->h->adjoint_record.on) return unsupported(BACKWARD_NEEDS_FLAG);
+    if (const int rc = backward_refusal(r, d_log_bar, d_state_bar); rc != VSMPC_OK) return rc;
     ON_DEVICE(r->h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);   // the caller's, the null stream too: its tensors are ordered on it
     const size_t B = size_t(r->batch);
     vsmpc_rollout::Tape& tp = r->tape;
-    if (d_state_bar != nullptr)
-        HIP_TRY(hipMemcpyAsync(tp.sbar, d_state_bar, B * VSMPC_PLANT_STATE * sizeof(double), hipMemcpyDeviceToDevice, s));
-    else
-        HIP_TRY(hipMemsetAsync(tp.sbar, 0, B * VSMPC_PLANT_STATE * sizeof(double), s));
+    HIP_TRY(seed_sbar(r, d_state_bar, hipMemcpyDeviceToDevice, s));
     if (const int rc = enqueue_sweep(r, d_log_bar, s); rc != VSMPC_OK) return rc;
     if (d_grad_state0 != nullptr)
         HIP_TRY(hipMemcpyAsync(d_grad_state0, tp.sbar, B * VSMPC_PLANT_STATE * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -426,15 +431,13 @@ int vsmpc_rollout_backward_device(vsmpc_rollout* r, const double* d_log_bar, con
 
 int vsmpc_rollout_backward(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0,
                            double* grad_cfg, int* flags, void* stream) {
-    if (r == nullptr || (log_bar == nullptr && state_bar == nullptr) || r->tape.ticks == 0) return invalid_arg();
-    if (!r->h->adjoint_record.on) return unsupported(BACKWARD_NEEDS_FLAG);
+    if (const int rc = backward_refusal(r, log_bar, state_bar); rc != VSMPC_OK) return rc;
     ON_DEVICE(r->h->device);
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->own_stream.h;
     const size_t B = size_t(r->batch);
     vsmpc_rollout::Tape& tp = r->tape;
     HIP_TRY(upload_rows(tp.log_bar.get(), log_bar, 0, size_t(tp.ticks), B * VSMPC_ROLLOUT_LOG, s));
-    HIP_TRY(upload_rows(tp.sbar.get(), state_bar, 0, B, VSMPC_PLANT_STATE, s));
-    if (state_bar == nullptr) HIP_TRY(hipMemsetAsync(tp.sbar, 0, B * VSMPC_PLANT_STATE * sizeof(double), s));
+    HIP_TRY(seed_sbar(r, state_bar, hipMemcpyHostToDevice, s));
     int rc = enqueue_sweep(r, log_bar ? tp.log_bar.get() : nullptr, s);
     hipError_t e = hipSuccess;
     if (rc == VSMPC_OK) e = download_rows(grad_state0, tp.sbar.get(), 0, B, VSMPC_PLANT_STATE, s);

@@ -196,13 +196,26 @@ struct RolloutCtl {   // device-resident per-run control block of the rollout
 // is given and the status is Solved: what the advance kernel is about to apply), thrusts as the controller sees them
 hipError_t launch_tree_state(const RolloutDev& rd, int batch, const double* state, const double* fm, const int* status,
                              double* rs, hipStream_t stream);
-hipError_t launch_record(const RolloutDev& rd, int batch, const double* state, const double* params, const int* tick,
-                         const double* traj_pos, const double* traj_vel, const double* traj_alpha, double* tstate,
-                         double* rec, hipStream_t stream);
-hipError_t launch_advance(const RolloutDev& rd, int batch, double* state, const double* params, int* tick, const double* fm,
-                          const int* status, const int* iters, const double* traj_alpha, const RolloutCtl* ctl, int substeps,
-                          const double* traj_pos, const double* traj_vel, double* tstate, double* rec_next,
-                          hipStream_t stream);
+// What one tick's launches work on, the same at every tick (all device pointers, [batch][..] rows).  record_kernel builds the
+// record of the tick the counters stand at; advance_kernel consumes the solve's outputs, flies the plant over one MPC period
+// and leaves the record of the following tick.
+struct RolloutTick {
+    int batch, substeps;
+    double* state;               // [VSMPC_PLANT_STATE]
+    const double* params;        // [VSMPC_PLANT_PARAMS]
+    int* tick;                   // ticks since the reset
+    const double* traj_pos;
+    const double* traj_vel;
+    const double* traj_alpha;
+    double* tstate;              // per-instance tick state [rd.n_ts]
+    double* rec;                 // the record [rd.n_in]
+    const double* fm;            // advance only: first move [VSMPC_FM_SIZE], status and iterations of the solve, control block
+    const int* status;
+    const int* iters;
+    const RolloutCtl* ctl;
+};
+hipError_t launch_record(const RolloutDev& rd, const RolloutTick& k, hipStream_t stream);
+hipError_t launch_advance(const RolloutDev& rd, const RolloutTick& k, hipStream_t stream);
 
 // One launch of the rollout's backward sweep (vsmpc_rollout_adjoint.hip): the record half of tick `tick_rec`, then the plant
 // half of tick `tick_plant` (ticks as the rollout counts them since its reset; -1: that half is absent).  All device pointers,

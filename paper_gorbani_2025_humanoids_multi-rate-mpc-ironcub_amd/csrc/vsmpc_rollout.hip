@@ -98,9 +98,9 @@ VS_DEV void assemble_record(const RolloutDev& rd, const double* __restrict__ s, 
         rpy_old[i] = meas;
     }
     __syncthreads();
-    // window column from trajectory sample `idx` with the CURRENT attitude and mass (costsVSMPC.cpp:103-113,127-146)
+    // window column from trajectory sample `idx` (window_fill_sample / window_push_sample) with the CURRENT attitude and
+    // mass (costsVSMPC.cpp:103-113,127-146)
     auto column_entry = [&](int idx, int i) -> double {
-        idx = idx < rd.n_traj ? idx : rd.n_traj - 1;
         if (i < 3) return p[VSMPC_PP_PINIT + i] + traj_pos[3 * idx + i];   // m_initialCoMPos + positionCoM
         if (i < 6) {                                                        // R^T m v_ref
             const int c = i - 3;
@@ -125,18 +125,14 @@ VS_DEV void assemble_record(const RolloutDev& rd, const double* __restrict__ s, 
         return acc;
     };
     if (first) {
-        // shifts made before update() number tk: the one of configure + one per earlier tick with k % ratio == ratio - 1;
-        // shift number s pushed trajectory sample min(s, n_traj - 1), the initial fill is sample 0
-        const int ns0 = 1 + tk / rd.ratio;
         for (int e = lane; e < nwin; e += RO_BLOCK) {
             const int j = e / 12, i = e - 12 * j;
-            const int sj = ns0 - (nref - 1 - j);
-            ts[e] = column_entry(sj > 0 ? sj : 0, i);
+            ts[e] = column_entry(window_fill_sample(rd, tk, j), i);
         }
         __syncthreads();
     }
-    if (tk % rd.ratio == rd.ratio - 1) {   // ReferenceTrackingCost::computeHessianAndGradient, m_counter == ratio - 1
-        const int ns = 1 + (tk + 1) / rd.ratio;
+    if (release_tick(rd, tk)) {   // ReferenceTrackingCost::computeHessianAndGradient, m_counter == ratio - 1
+        const int ns = window_push_sample(rd, tk);
         constexpr int KMAX = (12 * MAX_STAGES + RO_BLOCK - 1) / RO_BLOCK;
         double keep[KMAX];
 #pragma unroll
@@ -154,11 +150,10 @@ VS_DEV void assemble_record(const RolloutDev& rd, const double* __restrict__ s, 
         __syncthreads();
     }
     for (int e = lane; e < nwin; e += RO_BLOCK) r[VSMPC_IN_XREF + e] = ts[e];
-    // A_mom(q) = A_mom0 + sum_j DJ[j] (q_j - q_ref0_j); Lambda column j = DJ[j] T at the measured thrust
+    // A_mom(q); Lambda column j = DJ[j] T at the measured thrust
     // (the reference recomputes both from the kinematics each tick, systemDynamicsVSMPC.cpp:159-206,304,321-350)
     if (lane < 24) {
-        double acc = p[VSMPC_PP_AMOM0 + lane];
-        for (int j = 0; j < 8; ++j) acc += p[VSMPC_PP_DJ + 24 * j + lane] * (s[VSMPC_PS_Q + j] - p[VSMPC_PP_QREF0 + j]);
+        const double acc = amom_entry(p, s + VSMPC_PS_Q, lane);
         r[VSMPC_IN_AMOM + lane] = rd.tree ? amom[lane] : acc;
     }
     // thrusts and thrust rates as the controller sees them: the plant's own with the polynomial jet plant, the EKF
@@ -204,7 +199,7 @@ VS_DEV void assemble_record(const RolloutDev& rd, const double* __restrict__ s, 
     if (lane == 47) {
         r[VSMPC_IN_MASS] = m;
         r[VSMPC_IN_ALPHA] = alpha_of_tick(traj_alpha, rd.n_alpha, rd.alpha_up, tk);
-        r[VSMPC_IN_HOLD] = (tk % rd.ratio) != (rd.ratio - 1) ? 1.0 : 0.0;   // constraintsVSMPC.cpp:351,366-372
+        r[VSMPC_IN_HOLD] = release_tick(rd, tk) ? 0.0 : 1.0;   // constraintsVSMPC.cpp:351,366-372
     }
     __syncthreads();
     if (lane < 3) {                                  // QPInput::getPosCoMReference / getRPYReference = column 0 (costsVSMPC.cpp:155-156)
@@ -276,26 +271,16 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_kernel(RolloutDev rd, int ba
         const double t = (double(tick_before + int(p[VSMPC_PP_TICK0])) + double(ss) / double(substeps)) * rd.period_mpc;
         alpha_s[ss] = interp_clamped(traj_alpha, rd.n_alpha, t / rd.alpha_dt);
     }
-    if (st == VSMPC_STATUS_SOLVED) {  // variableSamplingMPC.cpp:91-108
-        if (lane < 8) s[VSMPC_PS_Q + lane] += f[VSMPC_FM_DQ + lane];
-        if (lane >= 8 && lane < 12) {
-            const int i = lane - 8;
-            s[VSMPC_PS_U + i] = f[VSMPC_FM_THROTTLE + i];
-            s[VSMPC_PS_TDES + i] = f[VSMPC_FM_THRUST + i];
-            s[VSMPC_PS_TDDES + i] = f[VSMPC_FM_THRUSTDOT + i];
-        }
-    }
+    if (st == VSMPC_STATUS_SOLVED) consume_move<true>(s, f, lane);
     __syncthreads();
     if (lane < 24) {  // A_mom(q): the joints only move at the tick boundary
-        double acc = p[VSMPC_PP_AMOM0 + lane];
-        for (int j = 0; j < 8; ++j) acc += p[VSMPC_PP_DJ + 24 * j + lane] * (s[VSMPC_PS_Q + j] - p[VSMPC_PP_QREF0 + j]);
+        const double acc = amom_entry(p, s + VSMPC_PS_Q, lane);
         Aq[lane] = rd.tree ? tree_amom : acc;
     } else if (lane == 24) {
         inv3(rd.tree ? tIB : p + VSMPC_PP_INERTIA_B, IBi);
     }
     __syncthreads();
-    // explicit Euler sub-steps, one state component per lane (20 lanes): the three sincos run side by side in lanes
-    // 0..2, the body rates in lanes 8..10, then every lane forms the derivative of its own component
+    // explicit Euler sub-steps, one state component per lane (20 lanes): substep_preamble, substep_rate
     {
         __shared__ double x[20], Rm[9], omv[3], sc[6], vthr[4];
         const int tk = tick_before + int(p[VSMPC_PP_TICK0]);
@@ -305,9 +290,9 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_kernel(RolloutDev rd, int ba
         __syncthreads();
         const double h = rd.period_mpc / double(substeps);
         for (int ss = 0; ss < substeps; ++ss) {
-            const double t = (double(tk) + double(ss) / double(substeps)) * rd.period_mpc;
+            const double t = substep_time(rd, tk, ss, substeps);
             const double alpha = alpha_s[ss];
-            const bool dist = t >= p[VSMPC_PP_DIST_T0] && t < p[VSMPC_PP_DIST_T1];
+            const bool dist = push_active(p, t);
             if (rd.jet_nn) {
                 // jet plant option, one plant step in the order of MujocoSim.step (ironcub_mujoco_simulator.py:128-133,
                 // 393-396): the NN advances every jet's thrust from its own previous output (hidden units over the lanes),
@@ -340,52 +325,12 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_kernel(RolloutDev rd, int ba
                 }
                 __syncthreads();
             }
-            if (lane < 3) {
-                double sn, cs;
-                sincos(x[6 + lane], &sn, &cs);
-                sc[2 * lane] = sn;
-                sc[2 * lane + 1] = cs;
-            } else if (lane >= 8 && lane < 11) {
-                const int i = lane - 8;
-                omv[i] = IBi[3 * i] * x[9] + IBi[3 * i + 1] * x[10] + IBi[3 * i + 2] * x[11];
-            }
+            substep_preamble(x, IBi, sc, omv, lane);
             __syncthreads();
-            const double sr = sc[0], cr = sc[1], sp = sc[2], cp = sc[3], sy = sc[4], cy = sc[5];
-            if (lane == 0) {
-                Rm[0] = cy * cp; Rm[1] = cy * sp * sr - sy * cr; Rm[2] = cy * sp * cr + sy * sr;
-                Rm[3] = sy * cp; Rm[4] = sy * sp * sr + cy * cr; Rm[5] = sy * sp * cr - cy * sr;
-                Rm[6] = -sp;     Rm[7] = cp * sr;                Rm[8] = cp * cr;
-            }
+            const SinCos a = sincos_of(sc);
+            if (lane == 0) rot_from_sincos(a, Rm);
             __syncthreads();
-            double d = 0.0;
-            if (lane < 3) {                                   // p' = R h_lin / m
-                d = (Rm[3 * lane] * x[3] + Rm[3 * lane + 1] * x[4] + Rm[3 * lane + 2] * x[5]) / m;
-            } else if (lane < 6 || (lane >= 9 && lane < 12)) { // momentum rates: -omega x h + A_mom(q) T (+ gravity, push)
-                const bool lin = lane < 6;
-                const int r = lin ? lane - 3 : lane - 9, h0 = lin ? 3 : 9;
-                const int r1 = (r + 1) % 3, r2 = (r + 2) % 3;
-                const double cross = omv[r1] * x[h0 + r2] - omv[r2] * x[h0 + r1];   // (omega x h)[r]
-                double f = -cross;
-                if (lin) f += alpha * m * (Rm[6 + r] * (-9.81));                    // alpha m R^T g, g = (0,0,-9.81)
-                for (int j = 0; j < 4; ++j) f += Aq[4 * (lin ? r : 3 + r) + j] * x[12 + j];
-                if (dist)
-                    f += lin ? Rm[r] * p[VSMPC_PP_DIST_F] + Rm[3 + r] * p[VSMPC_PP_DIST_F + 1] + Rm[6 + r] * p[VSMPC_PP_DIST_F + 2]
-                             : p[VSMPC_PP_DIST_TAU + r];
-                d = f;
-            } else if (lane < 9) {                            // rpy' = W^-1 omega (systemDynamicsVSMPC.cpp:140-147)
-                const double tp = sp / cp;
-                d = lane == 6 ? omv[0] + sr * tp * omv[1] + cr * tp * omv[2]
-                  : lane == 7 ? cr * omv[1] - sr * omv[2]
-                              : (sr * omv[1] + cr * omv[2]) / cp;
-            } else if (rd.jet_nn) {                           // thrusts follow the NN below, not an ODE
-                d = 0.0;
-            } else if (lane < 16) {                           // T' = Tdot
-                d = x[lane + 4];
-            } else if (lane < 20) {                           // T'' = sigma_T (f + g v(u))  (JetModel.cpp:29-64)
-                const int j = lane - 16;
-                const double Tb = Jet::stdT(x[12 + j]), Tdb = Jet::stdTd(x[16 + j]);
-                d = Jet::sgT * (Jet::f(Tb, Tdb) + Jet::g(Tb, Tdb) * vthr[j]);
-            }
+            const double d = substep_rate(x, Rm, omv, a, Aq, vthr, p, m, alpha, dist, rd.jet_nn, lane);
             __syncthreads();                                  // every lane has read x before anyone updates it
             if (lane < 20) x[lane] += h * d;
             __syncthreads();
@@ -447,20 +392,15 @@ hipError_t launch_tree_state(const RolloutDev& rd, int batch, const double* stat
     return hipGetLastError();
 }
 
-hipError_t launch_record(const RolloutDev& rd, int batch, const double* state, const double* params, const int* tick,
-                         const double* traj_pos, const double* traj_vel, const double* traj_alpha, double* tstate,
-                         double* rec, hipStream_t stream) {
-    hipLaunchKernelGGL(record_kernel, dim3(batch), dim3(RO_BLOCK), 0, stream, rd, batch, state, params, tick,
-                       traj_pos, traj_vel, traj_alpha, tstate, rec);
+hipError_t launch_record(const RolloutDev& rd, const RolloutTick& k, hipStream_t stream) {
+    hipLaunchKernelGGL(record_kernel, dim3(k.batch), dim3(RO_BLOCK), 0, stream, rd, k.batch, k.state, k.params, k.tick,
+                       k.traj_pos, k.traj_vel, k.traj_alpha, k.tstate, k.rec);
     return hipGetLastError();
 }
 
-hipError_t launch_advance(const RolloutDev& rd, int batch, double* state, const double* params, int* tick, const double* fm,
-                          const int* status, const int* iters, const double* traj_alpha, const RolloutCtl* ctl, int substeps,
-                          const double* traj_pos, const double* traj_vel, double* tstate, double* rec_next,
-                          hipStream_t stream) {
-    hipLaunchKernelGGL(advance_kernel, dim3(batch), dim3(RO_BLOCK), 0, stream, rd, batch, state, params, tick, fm,
-                       status, iters, traj_alpha, ctl, substeps, traj_pos, traj_vel, tstate, rec_next);
+hipError_t launch_advance(const RolloutDev& rd, const RolloutTick& k, hipStream_t stream) {
+    hipLaunchKernelGGL(advance_kernel, dim3(k.batch), dim3(RO_BLOCK), 0, stream, rd, k.batch, k.state, k.params, k.tick, k.fm,
+                       k.status, k.iters, k.traj_alpha, k.ctl, k.substeps, k.traj_pos, k.traj_vel, k.tstate, k.rec);
     return hipGetLastError();
 }
 

@@ -22,11 +22,10 @@
 
 namespace vsmpc {
 
-// R(rpy) as rot_from_rpy builds it, and its partials to roll, pitch, yaw: dR + 9 a, row-major
-VS_DEV void rot_partials(double sr, double cr, double sp, double cp, double sy, double cy, double* R, double* dR) {
-    R[0] = cy * cp; R[1] = cy * sp * sr - sy * cr; R[2] = cy * sp * cr + sy * sr;
-    R[3] = sy * cp; R[4] = sy * sp * sr + cy * cr; R[5] = sy * sp * cr - cy * sr;
-    R[6] = -sp;     R[7] = cp * sr;                R[8] = cp * cr;
+// R(rpy) of rot_from_sincos, and its partials to roll, pitch, yaw: dR + 9 a, row-major
+VS_DEV void rot_partials(const SinCos& a, double* R, double* dR) {
+    const double sr = a.sr, cr = a.cr, sp = a.sp, cp = a.cp, sy = a.sy, cy = a.cy;
+    rot_from_sincos(a, R);
     dR[0] = 0.0; dR[1] = cy * sp * cr + sy * sr; dR[2] = -cy * sp * sr + sy * cr;
     dR[3] = 0.0; dR[4] = sy * sp * cr - cy * sr; dR[5] = -sy * sp * sr - cy * cr;
     dR[6] = 0.0; dR[7] = cp * cr;                dR[8] = -cp * sr;
@@ -83,7 +82,7 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
         if (lane == 0) {
             double sr, cr, sp, cp, sy, cy;
             sincos(s[VSMPC_PS_RPY], &sr, &cr); sincos(s[VSMPC_PS_RPY + 1], &sp, &cp); sincos(s[VSMPC_PS_RPY + 2], &sy, &cy);
-            rot_partials(sr, cr, sp, cp, sy, cy, R, dR);
+            rot_partials({sr, cr, sp, cp, sy, cy}, R, dR);
         } else if (lane == 1) {
             inv3(p + VSMPC_PP_INERTIA_B, IBi);
         }
@@ -113,9 +112,8 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
                             t += (dRa[3 * i + u] * R[3 * j + v] + R[3 * i + u] * dRa[3 * j + v]) * IB[3 * u + v];
                     add += gi[VSMPC_IN_INERTIA + 3 * i + j] * t;
                 }
-            if (tk % rd.ratio == rd.ratio - 1) {   // the column this tick pushed, at this tick's R
-                int idx = 1 + (tk + 1) / rd.ratio;
-                idx = idx < rd.n_traj ? idx : rd.n_traj - 1;
+            if (release_tick(rd, tk)) {   // the column this tick pushed, at this tick's R
+                const int idx = window_push_sample(rd, tk);
                 add += hlin_to_rpy(dRa, wb + 12 * (nref - 1) + 3, a.traj_vel + 3 * idx, m);
             }
         } else if (lane >= 9 && lane < 12) {
@@ -141,7 +139,7 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
             add = gi[VSMPC_IN_TDDES + lane - 36];
         }
         __syncthreads();
-        if (tk % rd.ratio == rd.ratio - 1) {   // the FIFO shifted at this tick: the cotangent shifts back, column 0 was new to it
+        if (release_tick(rd, tk)) {   // the FIFO shifted at this tick: the cotangent shifts back, column 0 was new to it
             constexpr int KMAX = (12 * MAX_STAGES + RO_BLOCK - 1) / RO_BLOCK;
             double keep[KMAX];
 #pragma unroll
@@ -158,15 +156,11 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
             __syncthreads();
         }
         if (a.first) {   // this tick filled the window: every column was frozen with this tick's R
-            if (lane >= 6 && lane < 9) {
-                const int ns0 = 1 + tk / rd.ratio;
+            if (lane >= 6 && lane < 9)
                 for (int j = 0; j < nref; ++j) {
-                    int idx = ns0 - (nref - 1 - j);
-                    idx = idx > 0 ? idx : 0;
-                    idx = idx < rd.n_traj ? idx : rd.n_traj - 1;
+                    const int idx = window_fill_sample(rd, tk, j);
                     add += hlin_to_rpy(dR + 9 * (lane - 6), wb + 12 * j + 3, a.traj_vel + 3 * idx, m);
                 }
-            }
             __syncthreads();
             for (int e = lane; e < nwin; e += RO_BLOCK) wb[e] = 0.0;
         }
@@ -186,20 +180,12 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
         const bool solved = st == VSMPC_STATUS_SOLVED;
         const int tk = a.tick_plant + int(p[VSMPC_PP_TICK0]);
         const int substeps = a.substeps;
-        if (lane >= 32 && lane < 32 + substeps && lane < 48) {
-            const int ss = lane - 32;
-            const double t = (double(tk) + double(ss) / double(substeps)) * rd.period_mpc;
-            alpha_s[ss] = interp_clamped(a.traj_alpha, rd.n_alpha, t / rd.alpha_dt);
-        }
-        if (solved) {   // the move the forward tick consumed
-            if (lane < 8) s[VSMPC_PS_Q + lane] += f[VSMPC_FM_DQ + lane];
-            if (lane >= 8 && lane < 12) s[VSMPC_PS_U + lane - 8] = f[VSMPC_FM_THROTTLE + lane - 8];
-        }
+        if (lane >= 32 && lane < 32 + substeps && lane < 48)
+            alpha_s[lane - 32] = interp_clamped(a.traj_alpha, rd.n_alpha, substep_time(rd, tk, lane - 32, substeps) / rd.alpha_dt);
+        if (solved) consume_move<false>(s, f, lane);   // the move the forward tick consumed
         __syncthreads();
         if (lane < 24) {
-            double acc = p[VSMPC_PP_AMOM0 + lane];
-            for (int j = 0; j < 8; ++j) acc += DJ[24 * j + lane] * (s[VSMPC_PS_Q + j] - p[VSMPC_PP_QREF0 + j]);
-            Aq[lane] = acc;
+            Aq[lane] = amom_entry(p, s + VSMPC_PS_Q, lane);
         } else if (lane == 24) {
             inv3(p + VSMPC_PP_INERTIA_B, IBi);
         } else if (lane >= 28 && lane < 32) {
@@ -211,53 +197,15 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
         // forward: the sub-steps of advance_kernel, every one's 20-vector kept (xs + 20 ss is the state IN FRONT of sub-step ss)
         for (int ss = 0; ss + 1 < substeps; ++ss) {
             const double* x = xs + 20 * ss;
-            const double t = (double(tk) + double(ss) / double(substeps)) * rd.period_mpc;
+            const double t = substep_time(rd, tk, ss, substeps);
             const double alpha = alpha_s[ss];
-            const bool dist = t >= p[VSMPC_PP_DIST_T0] && t < p[VSMPC_PP_DIST_T1];
-            if (lane < 3) {
-                double sn, cs;
-                sincos(x[6 + lane], &sn, &cs);
-                sc[2 * lane] = sn;
-                sc[2 * lane + 1] = cs;
-            } else if (lane >= 8 && lane < 11) {
-                const int i = lane - 8;
-                omv[i] = IBi[3 * i] * x[9] + IBi[3 * i + 1] * x[10] + IBi[3 * i + 2] * x[11];
-            }
+            const bool dist = push_active(p, t);
+            substep_preamble(x, IBi, sc, omv, lane);
             __syncthreads();
-            const double sr = sc[0], cr = sc[1], sp = sc[2], cp = sc[3], sy = sc[4], cy = sc[5];
-            if (lane == 0) {
-                R[0] = cy * cp; R[1] = cy * sp * sr - sy * cr; R[2] = cy * sp * cr + sy * sr;
-                R[3] = sy * cp; R[4] = sy * sp * sr + cy * cr; R[5] = sy * sp * cr - cy * sr;
-                R[6] = -sp;     R[7] = cp * sr;                R[8] = cp * cr;
-            }
+            const SinCos w = sincos_of(sc);
+            if (lane == 0) rot_from_sincos(w, R);
             __syncthreads();
-            double d = 0.0;
-            if (lane < 3) {
-                d = (R[3 * lane] * x[3] + R[3 * lane + 1] * x[4] + R[3 * lane + 2] * x[5]) / m;
-            } else if (lane < 6 || (lane >= 9 && lane < 12)) {
-                const bool lin = lane < 6;
-                const int r = lin ? lane - 3 : lane - 9, h0 = lin ? 3 : 9;
-                const int r1 = (r + 1) % 3, r2 = (r + 2) % 3;
-                const double cross = omv[r1] * x[h0 + r2] - omv[r2] * x[h0 + r1];
-                double fo = -cross;
-                if (lin) fo += alpha * m * (R[6 + r] * (-9.81));
-                for (int j = 0; j < 4; ++j) fo += Aq[4 * (lin ? r : 3 + r) + j] * x[12 + j];
-                if (dist)
-                    fo += lin ? R[r] * p[VSMPC_PP_DIST_F] + R[3 + r] * p[VSMPC_PP_DIST_F + 1] + R[6 + r] * p[VSMPC_PP_DIST_F + 2]
-                              : p[VSMPC_PP_DIST_TAU + r];
-                d = fo;
-            } else if (lane < 9) {
-                const double tp = sp / cp;
-                d = lane == 6 ? omv[0] + sr * tp * omv[1] + cr * tp * omv[2]
-                  : lane == 7 ? cr * omv[1] - sr * omv[2]
-                              : (sr * omv[1] + cr * omv[2]) / cp;
-            } else if (lane < 16) {
-                d = x[lane + 4];
-            } else if (lane < 20) {
-                const int j = lane - 16;
-                const double Tb = Jet::stdT(x[12 + j]), Tdb = Jet::stdTd(x[16 + j]);
-                d = Jet::sgT * (Jet::f(Tb, Tdb) + Jet::g(Tb, Tdb) * vthr[j]);
-            }
+            const double d = substep_rate(x, R, omv, w, Aq, vthr, p, m, alpha, dist, false, lane);
             if (lane < 20) xs[20 * (ss + 1) + lane] = x[lane] + h * d;
             __syncthreads();
         }
@@ -267,23 +215,15 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
         __syncthreads();
         for (int ss = substeps - 1; ss >= 0; --ss) {
             const double* x = xs + 20 * ss;
-            const double t = (double(tk) + double(ss) / double(substeps)) * rd.period_mpc;
+            const double t = substep_time(rd, tk, ss, substeps);
             const double alpha = alpha_s[ss];
-            const bool dist = t >= p[VSMPC_PP_DIST_T0] && t < p[VSMPC_PP_DIST_T1];
-            if (lane < 3) {
-                double sn, cs;
-                sincos(x[6 + lane], &sn, &cs);
-                sc[2 * lane] = sn;
-                sc[2 * lane + 1] = cs;
-            } else if (lane >= 8 && lane < 11) {
-                const int i = lane - 8;
-                omv[i] = IBi[3 * i] * x[9] + IBi[3 * i + 1] * x[10] + IBi[3 * i + 2] * x[11];
-            }
+            const bool dist = push_active(p, t);
+            substep_preamble(x, IBi, sc, omv, lane);
             __syncthreads();
-            const double sr = sc[0], cr = sc[1], sp = sc[2], cp = sc[3], sy = sc[4], cy = sc[5];
-            const double tp = sp / cp;
+            const SinCos w = sincos_of(sc);
+            const double sr = w.sr, cr = w.cr, sp = w.sp, cp = w.cp, tp = sp / cp;
             if (lane == 0) {
-                rot_partials(sr, cr, sp, cp, sy, cy, R, dR);
+                rot_partials(w, R, dR);
             } else if (lane >= 1 && lane < 4) {
                 // cotangent of omega: -omega x h in both momenta, and rpy' = W^-1(rpy) omega
                 const int i = lane - 1, i1 = (i + 1) % 3, i2 = (i + 2) % 3;

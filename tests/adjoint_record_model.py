@@ -54,14 +54,22 @@ def dead(cfg):
     return [ref.IN_RPY + 2] + (list(range(last, last + 12)) if cfg.n_ref_cols > 1 else [])
 
 
+def worst_field(got, want, fields, bar=1e-6, floor=1e-12):
+    """the project's bar form on (name, offset, length) fields of a gradient: the worst |err| / (bar |field|_inf + floor
+    max |want|) and the field it was found in"""
+    gall = np.abs(want).max()
+    worst, where = 0.0, None
+    for name, off, n in fields:
+        f = want[off:off + n]
+        e = float(np.abs(got[off:off + n] - f).max() / (bar * np.abs(f).max() + floor * gall))
+        if e > worst or where is None:
+            worst, where = max(worst, e), name if e >= worst else where
+    return worst, where
+
+
 def field_errors(cfg, got_in, want_in, bar=1e-6, floor=1e-12):
-    """worst |err| / (bar |field|_inf + floor max |grad_in|) over the fields of the record (the project's bar form)"""
-    gall = np.abs(want_in).max()
-    worst = 0.0
-    for _, off, n in fields(cfg):
-        f = want_in[off:off + n]
-        worst = max(worst, float(np.abs(got_in[off:off + n] - f).max() / (bar * np.abs(f).max() + floor * gall)))
-    return worst
+    """worst_field over the fields of the record"""
+    return worst_field(got_in, want_in, fields(cfg), bar, floor)[0]
 
 
 # --------------------------------------------------------------------------------------------------------------------

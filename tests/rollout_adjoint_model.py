@@ -52,17 +52,7 @@ STATE_FIELDS = (("P", 0, 3), ("HLIN", 3, 3), ("RPY", 6, 3), ("HANG", 9, 3), ("T"
                 ("TDES", 32, 4), ("TDDES", 36, 4))
 
 
-def field_errors(got, want, fields, bar=1e-6, floor=1e-12):
-    """adjoint_record_model.field_errors' rule on the fields of a plant-state or a gains gradient: the worst
-    |err| / (bar |field|_inf + floor max |want|) and the field it was found in"""
-    gall = np.abs(want).max()
-    worst, where = 0.0, None
-    for name, off, n in fields:
-        f = want[off:off + n]
-        e = float(np.abs(got[off:off + n] - f).max() / (bar * np.abs(f).max() + floor * gall))
-        if e > worst or where is None:
-            worst, where = max(worst, e), name if e >= worst else where
-    return worst, where
+field_errors = arm.worst_field   # (got, want, fields, bar, floor) on the fields of a plant-state or a gains gradient
 
 
 def with_gains(cfg, row):
@@ -150,9 +140,6 @@ def drot(rpy, mutation=None):
     """R(rpy) of rollout_model.rot and its partials to roll, pitch, yaw"""
     r, p, y = rpy
     cr, sr, cp, sp, cy, sy = math.cos(r), math.sin(r), math.cos(p), math.sin(p), math.cos(y), math.sin(y)
-    R = np.array([[cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
-                  [sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
-                  [-sp, cp * sr, cp * cr]])
     dr = np.array([[0.0, cy * sp * cr + sy * sr, -cy * sp * sr + sy * cr],
                    [0.0, sy * sp * cr - cy * sr, -sy * sp * sr - cy * cr],
                    [0.0, cp * cr, -cp * sr]])
@@ -164,7 +151,7 @@ def drot(rpy, mutation=None):
     dy = np.array([[-sy * cp, -sy * sp * sr - cy * cr, -sy * sp * cr + cy * sr],
                    [cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
                    [0.0, 0.0, 0.0]])
-    return R, (dr, dp, dy)
+    return pm.rot(rpy), (dr, dp, dy)
 
 
 def _dv_du(u):
@@ -193,7 +180,7 @@ def plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next,
     xs, x = [], s[0:20].copy()
     for ss in range(substeps):                                 # the forward sub-steps, as rollout_model.advance takes them
         xs.append(x.copy())
-        x = _substep(cfg, x, p, tk, ss, substeps, A, IBi, vthr, alpha_track, alpha_dt)
+        x = pm.substep(cfg, x, p, tk, ss, substeps, A, IB, vthr, alpha_track, alpha_dt)
     lam = np.array(sbar_next[0:20], dtype=float)
     Abar, vbar = np.zeros((6, 4)), np.zeros(4)
     for ss in range(substeps - 1, -1, -1):
@@ -251,34 +238,6 @@ def plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next,
         out[L.PS_TDES:L.PS_TDES + 4] = sbar_next[L.PS_TDES:L.PS_TDES + 4]
         out[L.PS_TDDES:L.PS_TDDES + 4] = sbar_next[L.PS_TDDES:L.PS_TDDES + 4]
     return out, fmbar
-
-
-def _substep(cfg, x, p, tk, ss, substeps, A, IBi, vthr, alpha_track, alpha_dt):
-    """one explicit Euler sub-step of rollout_model.advance (parametric plant, polynomial jets)"""
-    m = p[L.PP_MASS]
-    h = cfg.period_mpc / substeps
-    t = (tk + ss / substeps) * cfg.period_mpc
-    alpha = pm.interp_clamped(alpha_track, t / alpha_dt)
-    R = pm.rot(x[6:9])
-    om = IBi @ x[9:12]
-    d = np.zeros(20)
-    d[0:3] = R @ x[3:6] / m
-    d[3:6] = -np.cross(om, x[3:6]) + A[0:3] @ x[12:16] + alpha * m * (R.T @ np.array([0.0, 0.0, -GRAV]))
-    d[9:12] = -np.cross(om, x[9:12]) + A[3:6] @ x[12:16]
-    if p[L.PP_DIST_T0] <= t < p[L.PP_DIST_T1]:
-        d[3:6] += R.T @ p[L.PP_DIST_F:L.PP_DIST_F + 3]
-        d[9:12] += p[L.PP_DIST_TAU:L.PP_DIST_TAU + 3]
-    sr, cr, sp, cp = math.sin(x[6]), math.cos(x[6]), math.sin(x[7]), math.cos(x[7])
-    tp = sp / cp
-    d[6] = om[0] + sr * tp * om[1] + cr * tp * om[2]
-    d[7] = cr * om[1] - sr * om[2]
-    d[8] = (sr * om[1] + cr * om[2]) / cp
-    sg = _JET.getThrustStandardDeviation_u2T()
-    for i in range(4):
-        Tb, Tdb = _JET.standardizeThrust_u2T(x[12 + i]), _JET.standardizeThrustDot_u2T(x[16 + i])
-        d[12 + i] = x[16 + i]
-        d[16 + i] = sg * (_JET.compute_f(Tb, Tdb) + _JET.compute_g(Tb, Tdb) * vthr[i])
-    return x + h * d
 
 
 def _sample(cfg, n_traj, idx):

@@ -119,6 +119,38 @@ def measured(s, jet=None):
     return m
 
 
+def substep(cfg, x, p, tk, ss, substeps, A, IB, vthr, traj_alpha, alpha_dt, jet_nn=False):
+    """x = (p, h_lin, rpy, h_ang, T, Tdot) after explicit Euler sub-step ss of tick tk (PP_TICK0 included).  A = A_mom(q), IB,
+    vthr = v(u) are constant over the tick; with jet_nn the thrusts are held.  The one copy: `advance` flies it,
+    rollout_adjoint_model.plant_adjoint recomputes its linearisation points with it."""
+    m = p[L.PP_MASS]
+    h = cfg.period_mpc / substeps
+    t = (tk + ss / substeps) * cfg.period_mpc
+    alpha = interp_clamped(traj_alpha, t / alpha_dt)
+    R = rot(x[6:9])
+    om = np.linalg.solve(IB, x[9:12])
+    d = np.zeros(20)
+    d[0:3] = R @ x[3:6] / m
+    d[3:6] = -np.cross(om, x[3:6]) + A[0:3] @ x[12:16] + alpha * m * (R.T @ np.array([0.0, 0.0, -9.81]))
+    d[9:12] = -np.cross(om, x[9:12]) + A[3:6] @ x[12:16]
+    if p[L.PP_DIST_T0] <= t < p[L.PP_DIST_T1]:
+        d[3:6] += R.T @ p[L.PP_DIST_F:L.PP_DIST_F + 3]
+        d[9:12] += p[L.PP_DIST_TAU:L.PP_DIST_TAU + 3]
+    sr, cr, sp, cp = math.sin(x[6]), math.cos(x[6]), math.sin(x[7]), math.cos(x[7])
+    tp = sp / cp
+    d[6] = om[0] + sr * tp * om[1] + cr * tp * om[2]
+    d[7] = cr * om[1] - sr * om[2]
+    d[8] = (sr * om[1] + cr * om[2]) / cp
+    sg = _JET.getThrustStandardDeviation_u2T()
+    for i in range(4):
+        Tb, Tdb = _JET.standardizeThrust_u2T(x[12 + i]), _JET.standardizeThrustDot_u2T(x[16 + i])
+        d[12 + i] = x[16 + i]
+        d[16 + i] = sg * (_JET.compute_f(Tb, Tdb) + _JET.compute_g(Tb, Tdb) * vthr[i])
+    if jet_nn:
+        d[12:20] = 0.0
+    return x + h * d
+
+
 def advance(cfg, s, p, tick, fm, status, traj_alpha, alpha_dt, substeps=5, jet=None):
     """Returns the plant state after one tick (first move applied only if status == 1).  `jet` = (JetLSTM, Q, R) of
     oracle/jet_ref.py selects the jet plant option, in the order of MujocoSim.step (ironcub_mujoco_simulator.py:128-133,
@@ -131,17 +163,12 @@ def advance(cfg, s, p, tick, fm, status, traj_alpha, alpha_dt, substeps=5, jet=N
         s[L.PS_TDES:L.PS_TDES + 4] = fm[L.FM_THRUST:L.FM_THRUST + 4]
         s[L.PS_TDDES:L.PS_TDDES + 4] = fm[L.FM_THRUSTDOT:L.FM_THRUSTDOT + 4]
     tk = tick + int(p[L.PP_TICK0])
-    m = p[L.PP_MASS]
     IB = inertia_body(s, p)            # (the joints only move at the tick boundary: constant over the sub-steps)
     A, _ = amom_of_q(s, p)
     vthr = np.array([_JET.compute_v(_JET.standardizeThrottle_u2T(u)) for u in s[L.PS_U:L.PS_U + 4]])
-    sg = _JET.getThrustStandardDeviation_u2T()
     h = cfg.period_mpc / substeps
     x = s[0:20].copy()
     for ss in range(substeps):
-        t = (tk + ss / substeps) * cfg.period_mpc
-        alpha = interp_clamped(traj_alpha, t / alpha_dt)
-        dist = p[L.PP_DIST_T0] <= t < p[L.PP_DIST_T1]
         if jet is not None:
             import jet_ref
             lstm, Q, Rm = jet
@@ -155,28 +182,6 @@ def advance(cfg, s, p, tick, fm, status, traj_alpha, alpha_dt, substeps=5, jet=N
             s[L.PS_TNN:L.PS_TNN + 4] = Tn                       # the NN's own feedback state
             x[12:16] = s[L.PS_EST:L.PS_EST + 8:2]               # set_thrust(self._estimated_thrust)
             x[16:20] = s[L.PS_EST + 1:L.PS_EST + 8:2]
-        R = rot(x[6:9])
-        om = np.linalg.solve(IB, x[9:12])
-        d = np.zeros(20)
-        d[0:3] = R @ x[3:6] / m
-        fl = -np.cross(om, x[3:6]) + A[0:3] @ x[12:16] + alpha * m * (R.T @ np.array([0.0, 0.0, -9.81]))
-        fa = -np.cross(om, x[9:12]) + A[3:6] @ x[12:16]
-        if dist:
-            fl = fl + R.T @ p[L.PP_DIST_F:L.PP_DIST_F + 3]
-            fa = fa + p[L.PP_DIST_TAU:L.PP_DIST_TAU + 3]
-        d[3:6], d[9:12] = fl, fa
-        sr, cr, sp, cp = math.sin(x[6]), math.cos(x[6]), math.sin(x[7]), math.cos(x[7])
-        tp = sp / cp
-        d[6] = om[0] + sr * tp * om[1] + cr * tp * om[2]
-        d[7] = cr * om[1] - sr * om[2]
-        d[8] = (sr * om[1] + cr * om[2]) / cp
-        for i in range(4):
-            Tb = _JET.standardizeThrust_u2T(x[12 + i])
-            Tdb = _JET.standardizeThrustDot_u2T(x[16 + i])
-            d[12 + i] = x[16 + i]
-            d[16 + i] = sg * (_JET.compute_f(Tb, Tdb) + _JET.compute_g(Tb, Tdb) * vthr[i])
-        if jet is not None:
-            d[12:20] = 0.0
-        x = x + h * d
+        x = substep(cfg, x, p, tk, ss, substeps, A, IB, vthr, traj_alpha, alpha_dt, jet is not None)
     s[0:20] = x
     return s

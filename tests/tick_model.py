@@ -23,6 +23,8 @@ import math
 
 import numpy as np
 
+from rollout_model import rot   # R(rpy) of the plant: one copy, the plant model's
+
 PKG = "paper_gorbani_2025_humanoids_multi-rate-mpc-ironcub_amd"
 L = importlib.import_module(PKG + ".layout")
 
@@ -65,14 +67,6 @@ class TrajectoryManager:
 
     def getCurrentValue(self, key):                            # :160-167
         return self.trajectories_map[key].values[self.trajectoryIndex]
-
-
-def rot(rpy):
-    r, p, y = rpy
-    cr, sr, cp, sp, cy, sy = math.cos(r), math.sin(r), math.cos(p), math.sin(p), math.cos(y), math.sin(y)
-    return np.array([[cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
-                     [sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
-                     [-sp, cp * sr, cp * cr]])
 
 
 def as_rpy(angle_continuous):
