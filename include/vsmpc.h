@@ -631,8 +631,9 @@ int vsmpc_rollout_get_records(vsmpc_rollout* r, double* records);
  * Every output may be NULL.  A tick whose taped status is not Solved did not consume its move: the cotangent of the move is
  * zero, the latched entries (joints, throttle, thrust references) pass straight through, VSMPC_ADJ_UNSOLVED is set.  The
  * sum over the ticks has an order fixed by the tick count alone: repeated and permuted batches are bit-identical.  Gradients
- * with respect to the plant parameters and the trajectories are not returned; the tick grid, the hold pattern, the
- * disturbance window and the alpha track are structural.  Needs a handle created with VSMPC_CREATE_ADJOINT_RECORD
+ * with respect to the plant parameters and the trajectories (the alpha track among them) are returned by
+ * vsmpc_rollout_backward_full, below; the tick grid, the hold pattern and the disturbance window are structural.  Needs a
+ * handle created with VSMPC_CREATE_ADJOINT_RECORD
  * (otherwise VSMPC_ERR_UNSUPPORTED_CONFIG, and vsmpc_strerror names the flag); it uses that entry's workspace, so it must
  * be ordered against the handle's other adjoint calls.
  */
@@ -643,6 +644,39 @@ int vsmpc_rollout_backward(vsmpc_rollout* r, const double* log_bar, const double
 /* Same, all pointers are DEVICE pointers and the call only enqueues work on `stream`. */
 int vsmpc_rollout_backward_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar, double* d_grad_state0,
                                   double* d_grad_cfg, int* d_flags, void* stream);
+
+/*
+ * The same sweep, with the gradients to the plant parameters and to the reference trajectories beside it ("Adjoint
+ * of the rollout: parameters and tracks"; executable model: tests/rollout_param_adjoint_model.py):
+ *   grad_params[batch][VSMPC_PLANT_PARAMS]     dL/d(every plant parameter) of the loop, in the order of VSMPC_PP_*: mass, I_B,
+ *                                              A_mom0, DJ, q_ref0, PINIT, RPYINIT, the push force and torque.  DIST_T0, DIST_T1
+ *                                              and TICK0 are structural: +0.0
+ *   grad_traj[batch][6 n_traj + n_alpha]       dL/d(traj_pos [n_traj][3] | traj_vel [n_traj][3] | traj_alpha [n_alpha]), in that
+ *                                              order (vsmpc_rollout_traj_grad_size doubles).  The tracks are shared by all
+ *                                              loops: one row per loop, the caller sums.  A sample that no window column of
+ *                                              the run holds, or that no tick and no sub-step reads, is +0.0
+ * Every output may be NULL; with grad_params == grad_traj == NULL the call runs exactly what vsmpc_rollout_backward runs, and
+ * grad_state0, grad_cfg and flags are those of vsmpc_rollout_backward bit for bit either way.  The sums have fixed orders (no
+ * atomics): repeated and permuted batches are bit-identical here too.  The derivative is taken with the tick state at the
+ * start of the taped run -- the reference window and the unwrap counters -- held fixed: when the taped run begins at a reset,
+ * that window is built from the tracks, PINIT, RPYINIT and the mass, and is differentiated; when it begins later, the window
+ * cotangent left at its first tick is dropped, as vsmpc_rollout_backward drops it.  A tick that was not Solved contributes
+ * nothing through its solve, and still through its plant half and the window.  The first call that asks for either output
+ * allocates batch x (VSMPC_PLANT_PARAMS + 6 n_traj + n_alpha) doubles, kept until vsmpc_rollout_destroy; a failure returns
+ * VSMPC_ERR_ALLOC and leaves the rollout and its tape usable.  Refusals as vsmpc_rollout_backward's; a rollout with a tree, the
+ * jet plant option or an RPYDot track is refused by name (VSMPC_ERR_UNSUPPORTED_CONFIG).
+ */
+int vsmpc_rollout_backward_full(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0,
+                                double* grad_cfg, double* grad_params, double* grad_traj, int* flags, void* stream);
+int vsmpc_rollout_backward_full_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar, double* d_grad_state0,
+                                       double* d_grad_cfg, double* d_grad_params, double* d_grad_traj, int* d_flags, void* stream);
+/* 6 n_traj + n_alpha: doubles in one row of grad_traj */
+int vsmpc_rollout_traj_grad_size(const vsmpc_rollout* r);
+/* New values for the rollout's tracks, of the lengths given at vsmpc_rollout_create (host; NULL keeps a track): a loop that
+ * optimises the trajectory need not re-create the rollout.  Written into the device buffers the rollout already holds, which
+ * the captured tick graph reads too: it is not rebuilt.  Invalidates the tape and requires vsmpc_rollout_reset before the next
+ * run, like vsmpc_rollout_set_attitude_tracks. */
+int vsmpc_rollout_set_trajectories(vsmpc_rollout* r, const double* traj_pos, const double* traj_vel, const double* traj_alpha);
 
 /* Pinned host memory for the caller's in/x/first_move/status buffers (thin wrappers of hipHostMalloc / hipHostFree,
  * so that a C caller need not link the HIP runtime).  With pinned OUTPUT buffers vsmpc_solve_batch lets the kernel write

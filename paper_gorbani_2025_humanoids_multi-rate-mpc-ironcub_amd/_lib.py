@@ -53,6 +53,11 @@ SIGNATURES = {
     "vsmpc_rollout_run_taped": [vp, c_int, dp, vp],
     # r, log_bar, state_bar, grad_state0, grad_cfg, flags, stream
     "vsmpc_rollout_backward": [vp, dp, dp, dp, dp, vp, vp], "vsmpc_rollout_backward_device": [vp, dp, dp, dp, dp, vp, vp],
+    # r, log_bar, state_bar, grad_state0, grad_cfg, grad_params, grad_traj, flags, stream
+    "vsmpc_rollout_backward_full": [vp, dp, dp, dp, dp, dp, dp, vp, vp],
+    "vsmpc_rollout_backward_full_device": [vp, dp, dp, dp, dp, dp, dp, vp, vp],
+    "vsmpc_rollout_traj_grad_size": [vp],
+    "vsmpc_rollout_set_trajectories": [vp, dp, dp, dp],
     "vsmpc_alloc_host": ([ctypes.c_size_t], vp),
     "vsmpc_free_host": ([vp], None),
     "vsmpc_set_kernel_form": [vp, c_int], "vsmpc_set_small_batch_kernel": [vp, c_int], "vsmpc_small_batch_kernel_for": [vp, c_int],

@@ -310,11 +310,24 @@ hipError_t grow_tape(vsmpc_rollout* r, int ticks) {
     return e;
 }
 
+size_t traj_grad_size(const vsmpc_rollout* r) { return size_t(6) * size_t(r->rd.n_traj) + size_t(r->rd.n_alpha); }
+
+// The two rows per instance of vsmpc_rollout_backward_full, on first request.  A failure leaves neither, and the tape as it was.
+hipError_t grow_full(vsmpc_rollout* r) {
+    vsmpc_rollout::Tape& tp = r->tape;
+    if (tp.gtraj != nullptr) return hipSuccess;
+    hipError_t e = tp.gpar.alloc(size_t(r->batch) * VSMPC_PLANT_PARAMS);
+    if (e == hipSuccess) e = tp.gtraj.alloc(size_t(r->batch) * traj_grad_size(r));
+    if (e != hipSuccess) { tp.gpar.reset(); tp.gtraj.reset(); }
+    return e;
+}
+
 // The backward sweep over the tape, last tick to first, in stream order: tape.sbar holds dL/d(final state) on entry and
 // dL/d(state at the start of the taped run) on exit; tape.gcfg and tape.flags receive the sums over the ticks.  Launch k of
 // advance_adjoint_kernel is the record half of tick k behind the plant half of tick k - 1, with the record adjoint of tick
 // k - 1 (the `_device` body of vsmpc_adjoint_record_batch: xbar = 0, fmbar = the plant half's) between launches k and k - 1.
-int enqueue_sweep(vsmpc_rollout* r, const double* d_log_bar, hipStream_t s) {
+// `full`: tape.gpar and tape.gtraj (grow_full) receive the sums over the ticks too, through the kernel's second instantiation.
+int enqueue_sweep(vsmpc_rollout* r, const double* d_log_bar, hipStream_t s, bool full = false) {
     vsmpc_handle* h = r->h;
     vsmpc_rollout::Tape& tp = r->tape;
     const size_t B = size_t(r->batch);
@@ -323,6 +336,12 @@ int enqueue_sweep(vsmpc_rollout* r, const double* d_log_bar, hipStream_t s) {
     HIP_TRY(hipMemsetAsync(tp.gcfg, 0, B * VSMPC_GRAD_SIZE * sizeof(double), s));
     HIP_TRY(hipMemsetAsync(tp.flags, 0, B * sizeof(int), s));
     RolloutAdj a = {};
+    if (full) {
+        HIP_TRY(hipMemsetAsync(tp.gpar, 0, B * VSMPC_PLANT_PARAMS * sizeof(double), s));
+        HIP_TRY(hipMemsetAsync(tp.gtraj, 0, B * traj_grad_size(r) * sizeof(double), s));
+        a.gpar = tp.gpar;
+        a.gtraj = tp.gtraj;
+    }
     a.batch = r->batch;
     a.substeps = r->substeps;
     a.params = r->d_params;
@@ -404,6 +423,66 @@ hipError_t seed_sbar(vsmpc_rollout* r, const double* state_bar, hipMemcpyKind ki
     return state_bar != nullptr ? hipMemcpyAsync(r->tape.sbar, state_bar, bytes, kind, s) : hipMemsetAsync(r->tape.sbar, 0, bytes, s);
 }
 
+// what the `_full` entries refuse in front of that, by name: a rollout of these kinds has no tape either, but the caller asked
+// for derivatives of a plant that has none
+int full_refusal(const vsmpc_rollout* r) {
+    if (r == nullptr) return invalid_arg();
+    if (r->use_tree) return unsupported("vsmpc_rollout_backward_full: no adjoint of the kinematic-tree plant (vsmpc_rollout_set_tree)");
+    if (r->rd.jet_nn) return unsupported("vsmpc_rollout_backward_full: no adjoint of the jet plant option (vsmpc_rollout_set_jet_plant)");
+    if (r->rd.traj_rpyd != nullptr)
+        return unsupported("vsmpc_rollout_backward_full: no adjoint of an RPYDot track (vsmpc_rollout_set_attitude_tracks)");
+    return VSMPC_OK;
+}
+
+// Both device entries (gpar == gtraj == nullptr: the plain one) and both host entries, `what` the entry's name.
+int backward_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar, double* d_grad_state0, double* d_grad_cfg,
+                    double* d_gpar, double* d_gtraj, int* d_flags, void* stream, const char* what) {
+    if (const int rc = backward_refusal(r, d_log_bar, d_state_bar); rc != VSMPC_OK) return rc;
+    ON_DEVICE(r->h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);   // the caller's, the null stream too: its tensors are ordered on it
+    const size_t B = size_t(r->batch);
+    vsmpc_rollout::Tape& tp = r->tape;
+    const bool full = d_gpar != nullptr || d_gtraj != nullptr;
+    if (full)
+        if (const hipError_t e = grow_full(r); e != hipSuccess) return alloc_fail(e, what);
+    HIP_TRY(seed_sbar(r, d_state_bar, hipMemcpyDeviceToDevice, s));
+    if (const int rc = enqueue_sweep(r, d_log_bar, s, full); rc != VSMPC_OK) return rc;
+    auto out = [&](void* dst, const void* src, size_t bytes) {
+        return dst != nullptr ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+    };
+    HIP_TRY(out(d_grad_state0, tp.sbar, B * VSMPC_PLANT_STATE * sizeof(double)));
+    HIP_TRY(out(d_grad_cfg, tp.gcfg, B * VSMPC_GRAD_SIZE * sizeof(double)));
+    HIP_TRY(out(d_flags, tp.flags, B * sizeof(int)));
+    HIP_TRY(out(d_gpar, tp.gpar, B * VSMPC_PLANT_PARAMS * sizeof(double)));
+    HIP_TRY(out(d_gtraj, tp.gtraj, B * traj_grad_size(r) * sizeof(double)));
+    return VSMPC_OK;
+}
+
+int backward_host(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0, double* grad_cfg,
+                  double* gpar, double* gtraj, int* flags, void* stream, const char* what) {
+    if (const int rc = backward_refusal(r, log_bar, state_bar); rc != VSMPC_OK) return rc;
+    ON_DEVICE(r->h->device);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->own_stream.h;
+    const size_t B = size_t(r->batch);
+    vsmpc_rollout::Tape& tp = r->tape;
+    const bool full = gpar != nullptr || gtraj != nullptr;
+    if (full)
+        if (const hipError_t e = grow_full(r); e != hipSuccess) return alloc_fail(e, what);
+    HIP_TRY(upload_rows(tp.log_bar.get(), log_bar, 0, size_t(tp.ticks), B * VSMPC_ROLLOUT_LOG, s));
+    HIP_TRY(seed_sbar(r, state_bar, hipMemcpyHostToDevice, s));
+    int rc = enqueue_sweep(r, log_bar ? tp.log_bar.get() : nullptr, s, full);
+    hipError_t e = hipSuccess;
+    if (rc == VSMPC_OK) e = download_rows(grad_state0, tp.sbar.get(), 0, B, VSMPC_PLANT_STATE, s);
+    if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(grad_cfg, tp.gcfg.get(), 0, B, VSMPC_GRAD_SIZE, s);
+    if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(flags, tp.flags.get(), 0, B, 1, s);
+    if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(gpar, tp.gpar.get(), 0, B, VSMPC_PLANT_PARAMS, s);
+    if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(gtraj, tp.gtraj.get(), 0, B, traj_grad_size(r), s);
+    const hipError_t e2 = hipStreamSynchronize(s);   // nothing returns while copies from the caller's buffers are queued
+    if (rc != VSMPC_OK) return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, what);
+    return VSMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -414,38 +493,42 @@ int vsmpc_rollout_run_taped(vsmpc_rollout* r, int ticks, double* log, void* stre
 
 int vsmpc_rollout_backward_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar, double* d_grad_state0,
                                   double* d_grad_cfg, int* d_flags, void* stream) {
-    if (const int rc = backward_refusal(r, d_log_bar, d_state_bar); rc != VSMPC_OK) return rc;
-    ON_DEVICE(r->h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);   // the caller's, the null stream too: its tensors are ordered on it
-    const size_t B = size_t(r->batch);
-    vsmpc_rollout::Tape& tp = r->tape;
-    HIP_TRY(seed_sbar(r, d_state_bar, hipMemcpyDeviceToDevice, s));
-    if (const int rc = enqueue_sweep(r, d_log_bar, s); rc != VSMPC_OK) return rc;
-    if (d_grad_state0 != nullptr)
-        HIP_TRY(hipMemcpyAsync(d_grad_state0, tp.sbar, B * VSMPC_PLANT_STATE * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (d_grad_cfg != nullptr)
-        HIP_TRY(hipMemcpyAsync(d_grad_cfg, tp.gcfg, B * VSMPC_GRAD_SIZE * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (d_flags != nullptr) HIP_TRY(hipMemcpyAsync(d_flags, tp.flags, B * sizeof(int), hipMemcpyDeviceToDevice, s));
-    return VSMPC_OK;
+    return backward_device(r, d_log_bar, d_state_bar, d_grad_state0, d_grad_cfg, nullptr, nullptr, d_flags, stream,
+                           "vsmpc_rollout_backward_device");
 }
 
 int vsmpc_rollout_backward(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0,
                            double* grad_cfg, int* flags, void* stream) {
-    if (const int rc = backward_refusal(r, log_bar, state_bar); rc != VSMPC_OK) return rc;
+    return backward_host(r, log_bar, state_bar, grad_state0, grad_cfg, nullptr, nullptr, flags, stream, "vsmpc_rollout_backward");
+}
+
+int vsmpc_rollout_backward_full_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar, double* d_grad_state0,
+                                       double* d_grad_cfg, double* d_grad_params, double* d_grad_traj, int* d_flags, void* stream) {
+    if (const int rc = full_refusal(r); rc != VSMPC_OK) return rc;
+    return backward_device(r, d_log_bar, d_state_bar, d_grad_state0, d_grad_cfg, d_grad_params, d_grad_traj, d_flags, stream,
+                           "vsmpc_rollout_backward_full_device");
+}
+
+int vsmpc_rollout_backward_full(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0,
+                                double* grad_cfg, double* grad_params, double* grad_traj, int* flags, void* stream) {
+    if (const int rc = full_refusal(r); rc != VSMPC_OK) return rc;
+    return backward_host(r, log_bar, state_bar, grad_state0, grad_cfg, grad_params, grad_traj, flags, stream,
+                         "vsmpc_rollout_backward_full");
+}
+
+int vsmpc_rollout_traj_grad_size(const vsmpc_rollout* r) { return r == nullptr ? invalid_arg() : int(traj_grad_size(r)); }
+
+int vsmpc_rollout_set_trajectories(vsmpc_rollout* r, const double* traj_pos, const double* traj_vel, const double* traj_alpha) {
+    if (r == nullptr) return invalid_arg();
     ON_DEVICE(r->h->device);
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->own_stream.h;
-    const size_t B = size_t(r->batch);
-    vsmpc_rollout::Tape& tp = r->tape;
-    HIP_TRY(upload_rows(tp.log_bar.get(), log_bar, 0, size_t(tp.ticks), B * VSMPC_ROLLOUT_LOG, s));
-    HIP_TRY(seed_sbar(r, state_bar, hipMemcpyHostToDevice, s));
-    int rc = enqueue_sweep(r, log_bar ? tp.log_bar.get() : nullptr, s);
-    hipError_t e = hipSuccess;
-    if (rc == VSMPC_OK) e = download_rows(grad_state0, tp.sbar.get(), 0, B, VSMPC_PLANT_STATE, s);
-    if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(grad_cfg, tp.gcfg.get(), 0, B, VSMPC_GRAD_SIZE, s);
-    if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(flags, tp.flags.get(), 0, B, 1, s);
-    const hipError_t e2 = hipStreamSynchronize(s);   // nothing returns while copies from the caller's buffers are queued
-    if (rc != VSMPC_OK) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, "vsmpc_rollout_backward");
+    // the record of the next tick and the tape were built from the old tracks; the captured ticks read the same buffers
+    r->valid = 0;
+    r->tape.ticks = 0;
+    HIP_TRY(hipDeviceSynchronize());   // a sweep a `_device` entry enqueued may still read them
+    const size_t nt = size_t(r->rd.n_traj) * 3 * sizeof(double);
+    if (traj_pos != nullptr) HIP_TRY(hipMemcpy(r->d_tpos, traj_pos, nt, hipMemcpyHostToDevice));
+    if (traj_vel != nullptr) HIP_TRY(hipMemcpy(r->d_tvel, traj_vel, nt, hipMemcpyHostToDevice));
+    if (traj_alpha != nullptr) HIP_TRY(hipMemcpy(r->d_talpha, traj_alpha, size_t(r->rd.n_alpha) * sizeof(double), hipMemcpyHostToDevice));
     return VSMPC_OK;
 }
 

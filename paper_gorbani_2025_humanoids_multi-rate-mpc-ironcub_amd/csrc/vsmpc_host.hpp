@@ -189,6 +189,9 @@ struct vsmpc_rollout {
         vsmpc::DevBuf<double> sbar, wbar, fmbar, xbar, gin, gcfg_t, gcfg, log_bar;
         vsmpc::DevBuf<int> flags_t, flags, bstatus;
         int log_bar_ticks = 0;              // rows of ticks the host entry's log_bar staging holds
+        // vsmpc_rollout_backward_full: dL/d(plant parameters) [batch][VSMPC_PLANT_PARAMS] and dL/d(tracks) [batch][6 n_traj +
+        // n_alpha], allocated by the first call that asks for either (gtraj last: its presence says that both are there)
+        vsmpc::DevBuf<double> gpar, gtraj;
     } tape;
 };
 

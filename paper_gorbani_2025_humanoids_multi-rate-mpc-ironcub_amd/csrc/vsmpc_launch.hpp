@@ -240,6 +240,11 @@ struct RolloutAdj {
     double* fmbar;               // out: cotangent of tick_plant's first move [VSMPC_FM_SIZE]
     double* gcfg;                // accumulated over the ticks [VSMPC_GRAD_SIZE]
     int* flags;
+    // vsmpc_rollout_backward_full: both or neither.  Given, the launch runs the kernel's second instantiation, which also
+    // accumulates over the ticks dL/d(plant parameters) [VSMPC_PLANT_PARAMS] and dL/d(traj_pos | traj_vel | traj_alpha)
+    // [6 n_traj + n_alpha], one row per instance
+    double* gpar;
+    double* gtraj;
 };
 hipError_t launch_advance_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream);
 

@@ -14,8 +14,18 @@
 //                   the direct part of dL/ds_{t-1} and the cotangent of the first move; on a tick that was not Solved the
 //                   move was not consumed: its cotangent is zero and the latched entries pass straight through.
 //
-// Mirror of tests/rollout_adjoint_model.py (plant_adjoint, record_adjoint), which is checked against central differences
-// of the forward loop model.  Parametric plant with the polynomial jet model only (the entry refuses the others).
+//   parameters and tracks (the PT instantiation, vsmpc_rollout_backward_full): the last step of the chain rule at both halves.
+//                   Record half: the record's entries that are plant parameters or are built from them (mass, I_G and omega
+//                   through I_B, A_mom and Lambda through A_mom0 / DJ / q_ref0, the posture error, RPYINIT), alpha of the tick
+//                   to its two track samples, and every window column at the moment its cotangent is complete -- the pushed
+//                   column in front of the shift, every column at the `first` fill -- to PINIT, RPYINIT, the mass and the
+//                   column's trajectory sample (position directly, velocity m R w).  Plant half, every sub-step: the mass
+//                   (p' = R h_lin / m, alpha m R^T g), I_B^-1 through omega, the push where push_active holds, alpha of the
+//                   sub-step to its two samples; behind the sub-steps A_mom0, DJ and q_ref0 from the cotangent of A_mom(q).
+//
+// Mirror of tests/rollout_adjoint_model.py (plant_adjoint, record_adjoint) and tests/rollout_param_adjoint_model.py, which are
+// checked against central differences of the forward loop model.  Parametric plant with the polynomial jet model only (the
+// entry refuses the others).
 #include "vsmpc_device.hpp"
 #include "vsmpc_launch.hpp"
 #include "vsmpc_rollout_device.hpp"
@@ -44,16 +54,96 @@ VS_DEV double hlin_to_rpy(const double* __restrict__ dRa, const double* __restri
     return acc;
 }
 
+// w . (R^T v): what a window column's h_lin entry R^T m v_ref, with cotangent w, hands to the mass
+VS_DEV double hlin_to_mass(const double* __restrict__ R, const double* __restrict__ w, const double* __restrict__ v) {
+    double acc = 0.0;
+    for (int c = 0; c < 3; ++c) acc += w[c] * (R[c] * v[0] + R[3 + c] * v[1] + R[6 + c] * v[2]);
+    return acc;
+}
+// (R w)[r] of a row-major R
+VS_DEV double rot_row(const double* __restrict__ R, const double* __restrict__ w, int r) {
+    return R[3 * r] * w[0] + R[3 * r + 1] * w[1] + R[3 * r + 2] * w[2];
+}
+
+// ---- the track rows of the PT instantiation --------------------------------------------------------------------------------
+// One launch touches few samples of grad_traj: those of the window columns whose cotangent becomes complete in its record half
+// (slots 0 .. n_ref - 1: the columns of the `first` fill; slot n_ref: the column a release tick pushed) and those the two
+// alpha-gravity look-ups read (elements 0, 1: alpha_of_tick of the record half; 2 .. 4: the three samples the sub-steps of the
+// plant half can reach, since one tick never spans more than one sample interval).  Clamped ends put several slots on one
+// sample: the first of them owns it.  The owner loads the sample's running sum in front of the first barrier and, at the end,
+// adds the slots of that sample in slot order and stores it -- one lane, a fixed order, no atomics.
+VS_DEV int slot_sample(const RolloutDev& rd, int tk, bool first, int ws) {   // -1: the slot is not live in this launch
+    if (ws < rd.n_ref) return first ? window_fill_sample(rd, tk, ws) : -1;
+    return release_tick(rd, tk) ? window_push_sample(rd, tk) : -1;
+}
+VS_DEV bool slot_owner(const RolloutDev& rd, int tk, bool first, int ws, int idx) {
+    for (int w2 = 0; w2 < ws; ++w2)
+        if (slot_sample(rd, tk, first, w2) == idx) return false;
+    return true;
+}
+constexpr int ALPHA_ELEMS = 5;
+// tkr, tkp: the launch's record and plant ticks with PP_TICK0 added, or -1; ai0: the lower sample of the plant tick's first sub-step
+VS_DEV int alpha_elem_sample(const RolloutDev& rd, int tkr, int tkp, int ai0, int e) {
+    if (e < 2) {
+        if (tkr < 0) return -1;
+        const Lerp l = alpha_tick_lerp(rd.n_alpha, rd.alpha_up, tkr);
+        return e == 0 ? l.i0 : l.i1;
+    }
+    if (tkp < 0) return -1;
+    const int i = ai0 + e - 2;
+    return i < rd.n_alpha ? i : rd.n_alpha - 1;
+}
+VS_DEV bool alpha_elem_owner(const RolloutDev& rd, int tkr, int tkp, int ai0, int e, int idx) {
+    for (int e2 = 0; e2 < e; ++e2)
+        if (alpha_elem_sample(rd, tkr, tkp, ai0, e2) == idx) return false;
+    return true;
+}
+// where component c (0..2 position, 3..5 velocity) of trajectory sample idx lives in a row of grad_traj
+VS_DEV size_t traj_entry(const RolloutDev& rd, int idx, int c) { return size_t(c < 3 ? 0 : 3 * rd.n_traj) + size_t(3 * idx + (c < 3 ? c : c - 3)); }
+
 // One wavefront per instance, as advance_kernel.  Every global load is requested in front of the first barrier.
+// PT (vsmpc_rollout_backward_full) also accumulates dL/d(plant parameters) and dL/d(tracks) of the instance: the parameter row
+// lives in LDS for the launch, the touched track samples as described above.  Without PT nothing of that is compiled in.
+template <bool PT>
 __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd, RolloutAdj a) {
     __shared__ double s[VSMPC_PLANT_STATE], p[VSMPC_PLANT_PARAMS + 1], f[VSMPC_FM_SIZE], sb[VSMPC_PLANT_STATE];
     __shared__ double gi[VSMPC_IN_XREF + 12 * MAX_STAGES], wb[12 * MAX_STAGES];
     __shared__ double R[9], dR[27], IBi[9], Aq[24], Ab[24], vb[4], vthr[4], alpha_s[16];
     __shared__ double xs[16 * 20], lam[20], sc[6], omv[3], omb[3];
+    // PT: cotangent of the parameters; of the window slots' trajectory samples (6 per slot); of the alpha elements
+    __shared__ double gp[PT ? VSMPC_PLANT_PARAMS + 1 : 1], tc[PT ? 6 * (MAX_STAGES + 1) : 1], ac[PT ? ALPHA_ELEMS + 1 : 1];
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= a.batch) return;
     const bool rec = a.tick_rec >= 0, plant = a.tick_plant >= 0;
     const int nref = rd.n_ref, nwin = 12 * rd.n_ref;
+    constexpr int KT = (6 * (MAX_STAGES + 1) + RO_BLOCK - 1) / RO_BLOCK;
+    double tpre[KT], apre = 0.0;   // PT: the running sums of the samples this lane owns
+    int tkr = -1, tkp = -1, ai0 = 0;
+    if constexpr (PT) {
+        stage_in<VSMPC_PLANT_PARAMS>(a.gpar + size_t(b) * VSMPC_PLANT_PARAMS, gp, lane);
+        // which samples the launch touches hangs on the instance's own PP_TICK0: one dependent round trip, still in front of
+        // the first barrier
+        const int tick0 = int(a.params[size_t(b) * VSMPC_PLANT_PARAMS + VSMPC_PP_TICK0]);
+        const double* gt = a.gtraj + size_t(b) * size_t(6 * rd.n_traj + rd.n_alpha);
+        if (rec) tkr = a.tick_rec + tick0;
+        if (plant) {
+            tkp = a.tick_plant + tick0;
+            ai0 = interp_lerp(rd.n_alpha, substep_time(rd, tkp, 0, a.substeps) / rd.alpha_dt).i0;
+        }
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            const int e = lane + k * RO_BLOCK, ws = e / 6, c = e - 6 * ws;
+            tpre[k] = 0.0;
+            if (rec && ws <= nref) {
+                const int idx = slot_sample(rd, tkr, a.first, ws);
+                if (idx >= 0 && slot_owner(rd, tkr, a.first, ws, idx)) tpre[k] = gt[traj_entry(rd, idx, c)];
+            }
+        }
+        if (lane < ALPHA_ELEMS) {
+            const int idx = alpha_elem_sample(rd, tkr, tkp, ai0, lane);
+            if (idx >= 0 && alpha_elem_owner(rd, tkr, tkp, ai0, lane, idx)) apre = gt[6 * rd.n_traj + idx];
+        }
+    }
     stage_in<VSMPC_PLANT_STATE>(a.sbar + size_t(b) * VSMPC_PLANT_STATE, sb, lane);
     stage_in<VSMPC_PLANT_PARAMS>(a.params + size_t(b) * VSMPC_PLANT_PARAMS, p, lane);
     for (int e = lane; e < nwin; e += RO_BLOCK) wb[e] = a.wbar[size_t(b) * nwin + e];
@@ -138,6 +228,50 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
         } else if (lane >= 36 && lane < 40) {
             add = gi[VSMPC_IN_TDDES + lane - 36];
         }
+        if constexpr (PT) {
+            // The record's entries that are parameters or are built from them, at the taped state; and the column this tick
+            // pushed, whose cotangent is complete here, in front of the shift: its position, attitude and h_lin entries
+            const bool rel = release_tick(rd, tk);
+            const double* wp = wb + 12 * (nref - 1);
+            const double* vp = a.traj_vel + 3 * (rel ? window_push_sample(rd, tk) : 0);
+            for (int e = lane; e < VSMPC_PP_DIST_F; e += RO_BLOCK) {
+                double g = 0.0;
+                if (e == VSMPC_PP_MASS) {
+                    g = gi[VSMPC_IN_MASS];
+                    if (rel) g += hlin_to_mass(R, wp + 3, vp);
+                } else if (e < VSMPC_PP_AMOM0) {                 // I_G = R I_B R^T, and omega = I_B^-1 h_ang
+                    const int u = (e - VSMPC_PP_INERTIA_B) / 3, v = (e - VSMPC_PP_INERTIA_B) % 3;
+                    for (int i = 0; i < 3; ++i)
+                        for (int j = 0; j < 3; ++j) g += R[3 * i + u] * gi[VSMPC_IN_INERTIA + 3 * i + j] * R[3 * j + v];
+                    const double om = IBi[3 * v] * s[VSMPC_PS_HANG] + IBi[3 * v + 1] * s[VSMPC_PS_HANG + 1] + IBi[3 * v + 2] * s[VSMPC_PS_HANG + 2];
+                    g -= (IBi[u] * gi[VSMPC_IN_OMEGA] + IBi[3 + u] * gi[VSMPC_IN_OMEGA + 1] + IBi[6 + u] * gi[VSMPC_IN_OMEGA + 2]) * om;
+                } else if (e < VSMPC_PP_DJ) {
+                    g = gi[VSMPC_IN_AMOM + e - VSMPC_PP_AMOM0];
+                } else if (e < VSMPC_PP_QREF0) {                 // A_mom(q), and Lambda column j = DJ[j] T
+                    const int d = e - VSMPC_PP_DJ, j = d / 24, l = d - 24 * j, row = l >> 2, c = l & 3;
+                    g = gi[VSMPC_IN_AMOM + l] * (s[VSMPC_PS_Q + j] - p[VSMPC_PP_QREF0 + j])
+                      + (row < 3 ? gi[VSMPC_IN_LLIN + 8 * row + j] : gi[VSMPC_IN_LANG + 8 * (row - 3) + j]) * s[VSMPC_PS_T + c];
+                } else if (e < VSMPC_PP_PINIT) {                 // the posture error, and A_mom(q)
+                    const int j = e - VSMPC_PP_QREF0;
+                    for (int l = 0; l < 24; ++l) g += DJ[24 * j + l] * gi[VSMPC_IN_AMOM + l];
+                    g = -gi[VSMPC_IN_QERR + j] - g;
+                } else if (e < VSMPC_PP_RPYINIT) {
+                    if (rel) g = wp[e - VSMPC_PP_PINIT];
+                } else {
+                    g = gi[VSMPC_IN_RPYINIT + e - VSMPC_PP_RPYINIT];
+                    if (rel) g += wp[6 + e - VSMPC_PP_RPYINIT];
+                }
+                gp[e] += g;
+            }
+            if (lane >= 40 && lane < 46) {                       // the pushed column's trajectory sample
+                const int c = lane - 40;
+                tc[6 * nref + c] = !rel ? 0.0 : c < 3 ? wp[c] : m * rot_row(R, wp + 3, c - 3);
+            } else if (lane == 46) {
+                const Lerp l = alpha_tick_lerp(rd.n_alpha, rd.alpha_up, tk);
+                ac[0] = gi[VSMPC_IN_ALPHA] * (1.0 - l.f);
+                ac[1] = gi[VSMPC_IN_ALPHA] * l.f;
+            }
+        }
         __syncthreads();
         if (release_tick(rd, tk)) {   // the FIFO shifted at this tick: the cotangent shifts back, column 0 was new to it
             constexpr int KMAX = (12 * MAX_STAGES + RO_BLOCK - 1) / RO_BLOCK;
@@ -161,6 +295,22 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
                     const int idx = window_fill_sample(rd, tk, j);
                     add += hlin_to_rpy(dR + 9 * (lane - 6), wb + 12 * j + 3, a.traj_vel + 3 * idx, m);
                 }
+            if constexpr (PT) {   // every column's cotangent is complete: its sample, and PINIT, RPYINIT and the mass, column by column
+                for (int e = lane; e < 6 * nref; e += RO_BLOCK) {
+                    const int j = e / 6, c = e - 6 * j;
+                    tc[e] = c < 3 ? wb[12 * j + c] : m * rot_row(R, wb + 12 * j + 3, c - 3);
+                }
+                if (lane >= 32 && lane < 39) {
+                    const int k = lane - 32;
+                    double acc = 0.0;
+                    for (int j = 0; j < nref; ++j) {
+                        const double* cw = wb + 12 * j;
+                        acc += k < 3 ? cw[k] : k < 6 ? cw[6 + k - 3]
+                                     : hlin_to_mass(R, cw + 3, a.traj_vel + 3 * window_fill_sample(rd, tk, j));
+                    }
+                    gp[k < 3 ? VSMPC_PP_PINIT + k : k < 6 ? VSMPC_PP_RPYINIT + k - 3 : VSMPC_PP_MASS] += acc;
+                }
+            }
             __syncthreads();
             for (int e = lane; e < nwin; e += RO_BLOCK) wb[e] = 0.0;
         }
@@ -212,6 +362,7 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
         // backward: lam = dL/d(the 20-vector behind sub-step ss); lanes 32..55 collect the cotangent of A_mom(q), 56..59 of v(u)
         if (lane < 20) lam[lane] = sb[lane];
         double abar = 0.0;
+        double pacc = 0.0, al0 = 0.0, al1 = 0.0, al2 = 0.0;   // PT: this lane's parameter entry; lane 20: the three alpha elements
         __syncthreads();
         for (int ss = substeps - 1; ss >= 0; --ss) {
             const double* x = xs + 20 * ss;
@@ -270,6 +421,26 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
                 const int j = lane - 56;
                 abar += h * lam[16 + j] * Jet::sgT * Jet::g(Jet::stdT(x[12 + j]), Jet::stdTd(x[16 + j]));
             }
+            if constexpr (PT) {   // the parameters of this sub-step, in the lanes the state leaves idle
+                if (lane == 20) {                      // mass: alpha m R^T g and p' = R h_lin / m; alpha: its two samples
+                    const double rg = -9.81 * (R[6] * lam[3] + R[7] * lam[4] + R[8] * lam[5]);
+                    const double rh = lam[0] * rot_row(R, x + 3, 0) + lam[1] * rot_row(R, x + 3, 1) + lam[2] * rot_row(R, x + 3, 2);
+                    pacc += h * (alpha * rg - rh / (m * m));
+                    const Lerp l = interp_lerp(rd.n_alpha, t / rd.alpha_dt);
+                    const double ga = h * m * rg, g0 = ga * (1.0 - l.f), g1 = ga * l.f;
+                    const int k0 = l.i0 - ai0, k1 = l.i1 - ai0;
+                    al0 += (k0 == 0 ? g0 : 0.0) + (k1 == 0 ? g1 : 0.0);
+                    al1 += (k0 == 1 ? g0 : 0.0) + (k1 == 1 ? g1 : 0.0);
+                    al2 += (k0 >= 2 ? g0 : 0.0) + (k1 >= 2 ? g1 : 0.0);
+                } else if (lane >= 21 && lane < 30) {  // I_B through omega = I_B^-1 h_ang: -(I_B^-T omega_bar) omega^T
+                    const int u = (lane - 21) / 3, v = (lane - 21) % 3;
+                    pacc -= h * (IBi[u] * omb[0] + IBi[3 + u] * omb[1] + IBi[6 + u] * omb[2]) * omv[v];
+                } else if (dist && (lane == 30 || lane == 31 || lane == 60)) {   // the push force enters as R^T F
+                    pacc += h * rot_row(R, lam + 3, lane == 60 ? 2 : lane - 30);
+                } else if (dist && lane >= 61) {       // and the torque directly
+                    pacc += h * lam[9 + lane - 61];
+                }
+            }
             __syncthreads();
             if (lane < 20) lam[lane] += h * g;
             __syncthreads();
@@ -277,6 +448,28 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
         if (lane >= 32 && lane < 56) Ab[lane - 32] = abar;
         if (lane >= 56 && lane < 60) vb[lane - 56] = abar;
         __syncthreads();
+        if constexpr (PT) {
+            if (lane == 20) {
+                gp[VSMPC_PP_MASS] += pacc;
+                ac[2] = al0; ac[3] = al1; ac[4] = al2;
+            } else if (lane >= 21 && lane < 30) {
+                gp[VSMPC_PP_INERTIA_B + lane - 21] += pacc;
+            } else if (lane == 30 || lane == 31 || lane == 60) {
+                gp[VSMPC_PP_DIST_F + (lane == 60 ? 2 : lane - 30)] += pacc;
+            } else if (lane >= 61) {
+                gp[VSMPC_PP_DIST_TAU + lane - 61] += pacc;
+            } else if (lane >= 40 && lane < 48) {      // q_ref0 through A_mom(q)
+                const int j = lane - 40;
+                double t = 0.0;
+                for (int l = 0; l < 24; ++l) t += DJ[24 * j + l] * Ab[l];
+                gp[VSMPC_PP_QREF0 + j] -= t;
+            }
+            // A_mom0 and DJ[j] (behind it in the row) from the cotangent of A_mom(q), q the joints after the move
+            for (int e = lane; e < 24 + 192; e += RO_BLOCK) {
+                const int j = e / 24 - 1, l = e - 24 * (j + 1);
+                gp[VSMPC_PP_AMOM0 + e] += j < 0 ? Ab[l] : Ab[l] * (s[VSMPC_PS_Q + j] - p[VSMPC_PP_QREF0 + j]);
+            }
+        }
         double fmb = 0.0;
         if (lane < 20) {
             out0 = lam[lane];
@@ -307,10 +500,40 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
     a.sbar[size_t(b) * VSMPC_PLANT_STATE + lane] = out0;
     if (lane + RO_BLOCK < VSMPC_PLANT_STATE) a.sbar[size_t(b) * VSMPC_PLANT_STATE + lane + RO_BLOCK] = 0.0;
     for (int e = lane; e < nwin; e += RO_BLOCK) a.wbar[size_t(b) * nwin + e] = wb[e];
+    if constexpr (PT) {
+        __syncthreads();
+        for (int e = lane; e < VSMPC_PLANT_PARAMS; e += RO_BLOCK) a.gpar[size_t(b) * VSMPC_PLANT_PARAMS + e] = gp[e];
+        double* gt = a.gtraj + size_t(b) * size_t(6 * rd.n_traj + rd.n_alpha);
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            const int e = lane + k * RO_BLOCK, ws = e / 6, c = e - 6 * ws;
+            if (rec && ws <= nref) {
+                const int idx = slot_sample(rd, tkr, a.first, ws);
+                if (idx >= 0 && slot_owner(rd, tkr, a.first, ws, idx)) {
+                    double sum = tpre[k];
+                    for (int w2 = ws; w2 <= nref; ++w2)
+                        if (slot_sample(rd, tkr, a.first, w2) == idx) sum += tc[6 * w2 + c];
+                    gt[traj_entry(rd, idx, c)] = sum;
+                }
+            }
+        }
+        if (lane < ALPHA_ELEMS) {
+            const int idx = alpha_elem_sample(rd, tkr, tkp, ai0, lane);
+            if (idx >= 0 && alpha_elem_owner(rd, tkr, tkp, ai0, lane, idx)) {
+                double sum = apre;
+                for (int e2 = lane; e2 < ALPHA_ELEMS; ++e2)
+                    if (alpha_elem_sample(rd, tkr, tkp, ai0, e2) == idx) sum += ac[e2];
+                gt[6 * rd.n_traj + idx] = sum;
+            }
+        }
+    }
 }
 
 hipError_t launch_advance_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream) {
-    hipLaunchKernelGGL(advance_adjoint_kernel, dim3(a.batch), dim3(RO_BLOCK), 0, stream, rd, a);
+    if (a.gpar != nullptr && a.gtraj != nullptr)
+        hipLaunchKernelGGL(advance_adjoint_kernel<true>, dim3(a.batch), dim3(RO_BLOCK), 0, stream, rd, a);
+    else
+        hipLaunchKernelGGL(advance_adjoint_kernel<false>, dim3(a.batch), dim3(RO_BLOCK), 0, stream, rd, a);
     return hipGetLastError();
 }
 

@@ -2,7 +2,8 @@
 // advance_adjoint_kernel), one copy of each formula that has to agree between the loop and its transpose: the rotation of the
 // plant's RPY convention (SinCos, rot_from_sincos), the consumed move, A_mom(q), the explicit Euler sub-step (its time and
 // push window; substep_preamble, substep_rate) and which trajectory sample a window column holds;
-// beside them the 3x3 inverse, clamped linear up-sampling and the global -> LDS staging of one instance's rows.  The plant state
+// beside them the 3x3 inverse, clamped linear up-sampling, the two samples it and the alpha-gravity cursor read (Lerp, for the
+// transposes) and the global -> LDS staging of one instance's rows.  The plant state
 // and parameter layouts are VSMPC_PS_* / VSMPC_PP_* of include/vsmpc.h; the per-instance tick state is described beside
 // tick_state_doubles in vsmpc_rollout.hip.
 #pragma once
@@ -46,6 +47,27 @@ VS_DEV double interp_clamped(const double* __restrict__ tr, int n, double pos) {
     const int i = int(pos);
     const double f = pos - double(i);
     return tr[i] + f * (tr[i + 1] - tr[i]);
+}
+
+// Which two samples a linearly up-sampled track value reads, for the transposes: v = tr[i0] + f (tr[i1] - tr[i0]), so a cotangent
+// g of v hands (1 - f) g to sample i0 and f g to sample i1 (a clamped end: i0 == i1, f = 0)
+struct Lerp { int i0, i1; double f; };
+VS_DEV Lerp interp_lerp(int n, double pos) {   // of interp_clamped: keep the two together
+    if (pos <= 0.0) return {0, 0, 0.0};
+    if (pos >= double(n - 1)) return {n - 1, n - 1, 0.0};
+    const int i = int(pos);
+    return {i, i + 1, pos - double(i)};
+}
+
+// of alpha_of_tick (vsmpc_rollout.hip, where the semantics are described; the forward kernels keep their own copy of the
+// index arithmetic so that their code does not move): tick tk reads sample tk + 1 of the track up-sampled by `up`
+VS_DEV Lerp alpha_tick_lerp(int n, int up, int tk) {
+    const int last = up == 1 ? n - 1 : up * (n - 1) - 1;
+    int idx = tk + 1;
+    idx = idx < last ? idx : last;
+    idx = idx > 0 ? idx : 0;
+    const int i = idx / up, j = idx - up * i;
+    return {i, i + 1 < n ? i + 1 : n - 1, double(j) / double(up)};
 }
 
 // One wavefront per instance.  The plant state and parameters are staged through LDS with coalesced loads, the record

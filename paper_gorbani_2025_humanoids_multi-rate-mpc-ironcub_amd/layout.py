@@ -124,6 +124,18 @@ PP_MASS, PP_INERTIA_B, PP_AMOM0, PP_DJ, PP_QREF0, PP_PINIT, PP_RPYINIT = 0, 1, 1
 PP_DIST_F, PP_DIST_TAU, PP_DIST_T0, PP_DIST_T1, PP_TICK0 = 240, 243, 246, 247, 248
 PLANT_PARAMS = 249
 ROLLOUT_LOG = 16
+# (field, offset, length) of the plant parameters vsmpc_rollout_backward_full differentiates; DIST_T0, DIST_T1 and TICK0 are
+# structural and get zero
+PARAM_GRAD_FIELDS = (("MASS", PP_MASS, 1), ("INERTIA_B", PP_INERTIA_B, 9), ("AMOM0", PP_AMOM0, 24), ("DJ", PP_DJ, 192),
+                     ("QREF0", PP_QREF0, 8), ("PINIT", PP_PINIT, 3), ("RPYINIT", PP_RPYINIT, 3), ("DIST_F", PP_DIST_F, 3),
+                     ("DIST_TAU", PP_DIST_TAU, 3))
+
+
+def traj_grad_blocks(n_traj: int, n_alpha: int) -> dict:
+    """name -> (offset, length, shape) of the three blocks of one row of grad_traj (vsmpc_rollout_backward_full):
+    traj_pos | traj_vel | traj_alpha, 6 n_traj + n_alpha doubles"""
+    return {"pos": (0, 3 * n_traj, (n_traj, 3)), "vel": (3 * n_traj, 3 * n_traj, (n_traj, 3)),
+            "alpha": (6 * n_traj, n_alpha, (n_alpha,))}
 
 # per-instance status (mirrors the OsqpEigen::Status values the reference distinguishes,
 # IMPCProblem.cpp:285-294, variableSamplingMPC.cpp:91)

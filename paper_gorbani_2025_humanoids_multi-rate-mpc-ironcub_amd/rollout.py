@@ -180,6 +180,7 @@ class ClosedLoopRollout:
         if pos.shape != vel.shape or pos.ndim != 2 or pos.shape[1] != 3:
             raise ValueError("traj_pos / traj_vel must be [n, 3]")
         self.n_traj = pos.shape[0]
+        self.n_alpha = alpha.shape[0]
         self._r = ctypes.c_void_p()
         _lib.check(self.lib.vsmpc_rollout_create(self.mpc._h, batch, _ptr(pos), _ptr(vel), pos.shape[0], _ptr(alpha),
                                                  alpha.shape[0], float(alpha_dt), ctypes.byref(self._r)),
@@ -259,12 +260,35 @@ class ClosedLoopRollout:
         self._taped = int(ticks) if tape else 0
         return out
 
-    def backward(self, log_bar=None, state_bar=None) -> dict:
+    def set_trajectories(self, traj_pos=None, traj_vel=None, traj_alpha=None):
+        """New values for the tracks, of the shapes given at construction (vsmpc_rollout_set_trajectories); None keeps a
+        track.  The tape is gone afterwards; call reset() before the next run."""
+        pos = None if traj_pos is None else np.ascontiguousarray(traj_pos, dtype=np.float64)
+        vel = None if traj_vel is None else np.ascontiguousarray(traj_vel, dtype=np.float64)
+        alpha = None if traj_alpha is None else np.ascontiguousarray(traj_alpha, dtype=np.float64)
+        for t in (pos, vel):
+            if t is not None and t.shape != (self.n_traj, 3):
+                raise ValueError(f"traj_pos / traj_vel must be [{self.n_traj}, 3]")
+        if alpha is not None and alpha.shape != (self.n_alpha,):
+            raise ValueError(f"traj_alpha must be [{self.n_alpha}]")
+        self._taped = 0
+        _lib.check(self.lib.vsmpc_rollout_set_trajectories(self._r, _ptr(pos), _ptr(vel), _ptr(alpha)),
+                   "vsmpc_rollout_set_trajectories")
+
+    @property
+    def traj_grad_size(self) -> int:
+        """doubles in one row of grad_traj: 6 n_traj + n_alpha (L.traj_grad_blocks names its three blocks)"""
+        return int(self.lib.vsmpc_rollout_traj_grad_size(self._r))
+
+    def backward(self, log_bar=None, state_bar=None, params: bool = False, traj: bool = False) -> dict:
         """vsmpc_rollout_backward over the last run(ticks, tape=True): the gradient of a loss on the flown trajectory, given
         as log_bar [ticks, batch, ROLLOUT_LOG] = dL/d(log rows) (columns 14, 15 ignored) and / or state_bar [batch,
         PLANT_STATE] = dL/d(final plant state).  Returns grad_state0 [batch, PLANT_STATE] (dL/d the plant state at the start
         of that run, entries 0..39), grad_gains [batch, L.GRAD_SIZE] (field values in L.GRAD_* order, summed over the ticks;
-        per loop under its own row with set_tunables) and flags [batch] (OR over the ticks of L.ADJ_*).  Needs adjoint=True."""
+        per loop under its own row with set_tunables) and flags [batch] (OR over the ticks of L.ADJ_*).  Needs adjoint=True.
+        params / traj (vsmpc_rollout_backward_full): also grad_params [batch, PLANT_PARAMS] (L.PP_* order; the structural
+        entries are zero) and / or grad_traj_pos, grad_traj_vel [batch, n_traj, 3] and grad_traj_alpha [batch, n_alpha], each
+        per loop: the tracks are shared, their gradient is the sum over the loops."""
         ticks = getattr(self, "_taped", 0)
         lb = None if log_bar is None else np.ascontiguousarray(log_bar, dtype=np.float64)
         sb = None if state_bar is None else np.ascontiguousarray(state_bar, dtype=np.float64)
@@ -274,19 +298,43 @@ class ClosedLoopRollout:
             raise ValueError(f"state_bar must be [{self.batch}, {L.PLANT_STATE}]")
         out = {"grad_state0": np.empty((self.batch, L.PLANT_STATE)), "grad_gains": np.empty((self.batch, L.GRAD_SIZE)),
                "flags": np.empty(self.batch, dtype=np.int32)}
-        _lib.check(self.lib.vsmpc_rollout_backward(self._r, _ptr(lb), _ptr(sb), _ptr(out["grad_state0"]), _ptr(out["grad_gains"]),
-                                                   _ptr(out["flags"]), None), "vsmpc_rollout_backward")
+        if not params and not traj:
+            _lib.check(self.lib.vsmpc_rollout_backward(self._r, _ptr(lb), _ptr(sb), _ptr(out["grad_state0"]),
+                                                       _ptr(out["grad_gains"]), _ptr(out["flags"]), None), "vsmpc_rollout_backward")
+            return out
+        gp = np.empty((self.batch, L.PLANT_PARAMS)) if params else None
+        gt = np.empty((self.batch, self.traj_grad_size)) if traj else None
+        _lib.check(self.lib.vsmpc_rollout_backward_full(self._r, _ptr(lb), _ptr(sb), _ptr(out["grad_state0"]),
+                                                        _ptr(out["grad_gains"]), _ptr(gp), _ptr(gt), _ptr(out["flags"]), None),
+                   "vsmpc_rollout_backward_full")
+        if params:
+            out["grad_params"] = gp
+        if traj:
+            for name, (off, n, shape) in L.traj_grad_blocks(self.n_traj, self.n_alpha).items():
+                out["grad_traj_" + name] = gt[:, off:off + n].reshape((self.batch,) + shape).copy()
         return out
 
-    def backward_device(self, d_log_bar, d_state_bar, d_grad_state0, d_grad_gains, d_flags, stream=None):
+    def backward_device(self, d_log_bar, d_state_bar, d_grad_state0, d_grad_gains, d_flags, stream=None, d_grad_params=None,
+                        d_grad_traj=None):
         """vsmpc_rollout_backward_device: backward() on contiguous CUDA tensors (None: not given / not wanted); only enqueues,
-        on `stream` or torch's current stream"""
+        on `stream` or torch's current stream.  d_grad_params [batch, PLANT_PARAMS] and / or d_grad_traj [batch,
+        traj_grad_size] given: vsmpc_rollout_backward_full_device."""
         from .solver import _assert_f64_device, _dptr, _stream
-        _assert_f64_device(d_log_bar, d_state_bar, d_grad_state0, d_grad_gains)
+        _assert_f64_device(d_log_bar, d_state_bar, d_grad_state0, d_grad_gains, d_grad_params, d_grad_traj)
         ref_t = d_log_bar if d_log_bar is not None else d_state_bar
-        _lib.check(self.lib.vsmpc_rollout_backward_device(self._r, _dptr(d_log_bar), _dptr(d_state_bar), _dptr(d_grad_state0),
-                                                          _dptr(d_grad_gains), _dptr(d_flags), _stream(ref_t, stream)),
-                   "vsmpc_rollout_backward_device")
+        if d_grad_params is None and d_grad_traj is None:
+            _lib.check(self.lib.vsmpc_rollout_backward_device(self._r, _dptr(d_log_bar), _dptr(d_state_bar), _dptr(d_grad_state0),
+                                                              _dptr(d_grad_gains), _dptr(d_flags), _stream(ref_t, stream)),
+                       "vsmpc_rollout_backward_device")
+            return
+        if d_grad_params is not None and tuple(d_grad_params.shape) != (self.batch, L.PLANT_PARAMS):
+            raise ValueError(f"d_grad_params must be [{self.batch}, {L.PLANT_PARAMS}]")
+        if d_grad_traj is not None and tuple(d_grad_traj.shape) != (self.batch, self.traj_grad_size):
+            raise ValueError(f"d_grad_traj must be [{self.batch}, {self.traj_grad_size}] (6 n_traj + n_alpha)")
+        _lib.check(self.lib.vsmpc_rollout_backward_full_device(self._r, _dptr(d_log_bar), _dptr(d_state_bar), _dptr(d_grad_state0),
+                                                               _dptr(d_grad_gains), _dptr(d_grad_params), _dptr(d_grad_traj),
+                                                               _dptr(d_flags), _stream(ref_t, stream)),
+                   "vsmpc_rollout_backward_full_device")
 
     def state(self) -> np.ndarray:
         out = np.empty((self.batch, L.PLANT_STATE))

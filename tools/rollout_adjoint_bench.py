@@ -1,11 +1,13 @@
 """Time per tick of the rollout's backward sweep (vsmpc_rollout_backward_device) against the forward tick (vsmpc_rollout_run,
 graph replay), the taped forward tick (vsmpc_rollout_run_taped, direct launches and the tape's copies) and the record-adjoint
-launch alone (vsmpc_adjoint_record_batch_device on the records of one tick, the launch every tick of the sweep contains).
+launch alone (vsmpc_adjoint_record_batch_device on the records of one tick, the launch every tick of the sweep contains), and
+of the sweep that also returns the parameter and track gradients (vsmpc_rollout_backward_full_device: the same launches, the
+second instantiation of advance_adjoint_kernel).
 
     python tools/rollout_adjoint_bench.py [--out profiles/rollout_adjoint_bench.txt] [--rounds 7]
 
 Workloads: batch 256 hover and batch 4096 take-off at the paper horizon (17, 7, 12), tuned handle.  Host clock around calls
-that end in a synchronise; the four kinds ALTERNATE, `rounds` windows each after a warm-up window of all, and the report is
+that end in a synchronise; the five kinds ALTERNATE, `rounds` windows each after a warm-up window of all, and the report is
 the median and the min..max spread of each and the ratios of the medians -- all in one process, one box.  A record, not a
 gate."""
 from __future__ import annotations
@@ -42,6 +44,7 @@ def run_case(workload, batch, ticks, rounds):
     d_xbar, d_fmbar = torch.zeros((batch, m.n_var), **f64), torch.from_numpy(rng.standard_normal((batch, 24))).to(dev)
     d_st, d_gc, d_gin = torch.empty(batch, **i32), torch.empty((batch, layout.GRAD_SIZE), **f64), torch.empty((batch, m.n_in), **f64)
     d_afl = torch.empty(batch, **i32)
+    d_gp, d_gt = torch.empty((batch, layout.PLANT_PARAMS), **f64), torch.empty((batch, 6 * len(pos) + len(alpha)), **f64)
     r.reset(st, pa)
     d_rec = torch.from_numpy(r.next_records()).to(dev)
     s = torch.cuda.current_stream(dev)
@@ -63,6 +66,7 @@ def run_case(workload, batch, ticks, rounds):
         "forward_taped": lambda: r.run(ticks, log=False, tape=True),
         "backward": lambda: r.backward_device(d_lb, d_sb, d_g0, d_gg, d_fl, stream=s),      # (sweeps the tape in front of it)
         "record_alone": record_alone,
+        "backward_full": lambda: r.backward_device(d_lb, d_sb, d_g0, d_gg, d_fl, stream=s, d_grad_params=d_gp, d_grad_traj=d_gt),
     }
     for fn in kinds.values():                                    # warm-up window of all (builds the graph, grows the tape)
         timed(fn)
@@ -80,9 +84,13 @@ def run_case(workload, batch, ticks, rounds):
     for k in kinds:
         lines.append(f"  {k:14s}  median {med[k]:10.2f} us/tick  ({med[k] / batch:.4f} us per loop and tick)  min {min(t[k]):10.2f}  "
                      f"max {max(t[k]):10.2f}  spread {100.0 * (max(t[k]) - min(t[k])) / med[k]:.2f} %")
-    for k, base in (("forward_taped", "forward"), ("backward", "forward"), ("backward", "record_alone")):
+    for k, base in (("forward_taped", "forward"), ("backward", "forward"), ("backward", "record_alone"),
+                    ("backward_full", "backward"), ("backward_full", "record_alone")):
         ratios = [a / b for a, b in zip(t[k], t[base])]
         lines.append(f"  {k} / {base} (medians) {med[k] / med[base]:.4f}   per round min {min(ratios):.4f} max {max(ratios):.4f}")
+    lines.append(f"  backward_full - backward (medians) {med['backward_full'] - med['backward']:.2f} us/tick: the parameter and track shares "
+                 f"(one dependent load, {8 * (layout.PLANT_PARAMS)} B row read and written per instance and launch); gradients finite: "
+                 f"{bool(torch.isfinite(d_gp).all()) and bool(torch.isfinite(d_gt).all())}")
     lines.append(f"  backward - record_alone (medians) {med['backward'] - med['record_alone']:.2f} us/tick: advance_adjoint_kernel and "
                  f"the gaps between the two launches of a tick")
     r.close()
