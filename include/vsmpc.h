@@ -485,6 +485,32 @@ typedef struct {
 int vsmpc_provider_batch(vsmpc_handle* h, const vsmpc_tree* tree, const double* state, int batch, double* kin,
                          double* robot, double* records);
 
+/* What the kinematic-tree plant of a rollout (vsmpc_rollout_set_tree) hands a tick, as one smooth map of the plant's joints
+ * and thrusts, and its Jacobian:
+ *     (q[8], T[4]) -> terms = A_mom,body | Lambda_lin,B | Lambda_ang,B | I_B,   jac = d terms / d(q | T),
+ * with the base at the origin, identity attitude and zero velocities -- the pose the rollout evaluates the provider and the
+ * kinematics kernel at, so that `terms` is what vsmpc_provider_batch (AMOMB) followed by vsmpc_kinematics_batch returns
+ * there (I_G = I_B at that pose).  One kernel (tree_jacobian_kernel) carries the twelve directions in forward mode; Lambda
+ * is linear in T, so its thrust columns are Lambda at unit thrusts and every other row of those columns is zero.  Lambda_ang
+ * takes its columns through the handle's joint selector (vsmpc_set_kinematics_options); with jointsLambdaOption "constant"
+ * set the call is refused (VSMPC_ERR_UNSUPPORTED_CONFIG), as the provider's record patch is.  The tree's own geometry
+ * (masses, origins, axes) is held fixed: there are no derivatives to it. */
+#define VSMPC_TT_AMOM 0    /* 24 A_mom,body 6x4 row-major */
+#define VSMPC_TT_LLIN 24   /* 24 Lambda_lin,B 3x8 */
+#define VSMPC_TT_LANG 48   /* 24 Lambda_ang,B 3x8 */
+#define VSMPC_TT_IB 72     /*  9 I_B */
+#define VSMPC_TT_SIZE 81
+#define VSMPC_TT_NDIR 12   /* 8 joints | 4 thrusts */
+/* q[batch][8], thrust[batch][4] -> terms[batch][VSMPC_TT_SIZE] and jac[batch][VSMPC_TT_SIZE][VSMPC_TT_NDIR] (either may be
+ * NULL: not wanted).  Any batch (the call stages it in device memory of its own, freed before it returns).  NULL handle, tree,
+ * q or thrust, a batch <= 0 or an invalid tree (parents must precede children, indices in range): VSMPC_ERR_INVALID_ARG, the
+ * NULL and batch checks before any device call. */
+int vsmpc_tree_jacobian_batch(vsmpc_handle* h, const vsmpc_tree* tree, const double* q, const double* thrust, int batch,
+                              double* terms, double* jac);
+/* The same on device pointers: only enqueues on `stream` (the null stream too), allocates nothing, does not synchronise. */
+int vsmpc_tree_jacobian_batch_device(vsmpc_handle* h, const vsmpc_tree* tree, const double* d_q, const double* d_thrust, int batch,
+                                     double* d_terms, double* d_jac, void* stream);
+
 /* Debug/parity: the reference-ordered dense QP of ONE instance, assembled on the host from the
  * DEVICE linearisation exactly as IMPCProblem::update stacks it (IMPCProblem.cpp:150-194):
  * H[nVar*nVar], g[nVar], Ac[nCon*nVar] (row-major), lo[nCon], hi[nCon]. */
@@ -582,6 +608,18 @@ int vsmpc_rollout_set_attitude_tracks(vsmpc_rollout* r, const double* traj_rpy, 
  * (tree->robot_joint[j] = 3 + j for the default selector).  NULL switches back to the parametric plant.  Call before
  * vsmpc_rollout_reset; a tick is then six launches instead of two (still replayed from a captured graph). */
 int vsmpc_rollout_set_tree(vsmpc_rollout* r, const vsmpc_tree* tree);
+/* The same with flags; vsmpc_rollout_set_tree is this call with flags 0.  Unknown bits: VSMPC_ERR_INVALID_ARG.
+ *   VSMPC_TREE_ADJOINT   the rollout then accepts vsmpc_rollout_run_taped, vsmpc_rollout_backward[_device] and
+ *                        vsmpc_rollout_backward_full[_device] on the tree plant (below, "Adjoint of the rollout").  The call
+ *                        allocates the rows the sweep reads per launch -- the terms of vsmpc_tree_jacobian_batch and their
+ *                        Jacobian, batch x VSMPC_TT_SIZE x (1 + VSMPC_TT_NDIR) doubles, kept until vsmpc_rollout_destroy; a
+ *                        failure returns VSMPC_ERR_ALLOC and leaves the rollout as it was.  Refused when the handle has
+ *                        jointsLambdaOption "constant" set at the time of this call (VSMPC_ERR_UNSUPPORTED_CONFIG), as the
+ *                        provider's record patch is; the check is made here only: the rollout's tree plant, forward and
+ *                        backward, never reads that option (it always forms the current Lambda terms).
+ * Without the flag a rollout with a tree keeps refusing the taped run and the sweep. */
+#define VSMPC_TREE_ADJOINT 1u
+int vsmpc_rollout_set_tree_ex(vsmpc_rollout* r, const vsmpc_tree* tree, unsigned flags);
 /* Per-instance tunables of the rollout's solves: tunables[batch][VSMPC_TUNE_SIZE] (host, rows of vsmpc_pack_tunables)
  * are copied to a device buffer the rollout owns, and every tick's solve launch -- those inside the captured graph too --
  * is then of the per-instance-tunables kind.  NULL restores the handle's shared configuration.  Call before
@@ -606,8 +644,18 @@ int vsmpc_rollout_get_records(vsmpc_rollout* r, double* records);
  * of staging for vsmpc_rollout_backward's log_bar), beside a few rows per instance for the sweep.  An allocation failure
  * returns VSMPC_ERR_ALLOC and leaves the rollout runnable, without a tape.  A later vsmpc_rollout_reset, _set_tree,
  * _set_tunables, _set_attitude_tracks, _set_jet_plant or untaped vsmpc_rollout_run invalidates the tape.
- * Supported: the parametric plant with the polynomial jet model.  A rollout with a tree (vsmpc_rollout_set_tree), with the jet
- * plant option or with an RPYDot track is refused: VSMPC_ERR_UNSUPPORTED_CONFIG, and vsmpc_strerror names the option.
+ * Supported: the parametric plant, and the kinematic-tree plant when the tree was set with VSMPC_TREE_ADJOINT
+ * (vsmpc_rollout_set_tree_ex), both with the polynomial jet model.  A rollout with a tree set without that flag
+ * (vsmpc_rollout_set_tree), with the jet plant option or with an RPYDot track -- alone or beside such a tree -- is refused:
+ * VSMPC_ERR_UNSUPPORTED_CONFIG, and vsmpc_strerror names the option.
+ * On the tree plant the sweep sees the tree through tau = terms(q, T) of vsmpc_tree_jacobian_batch at the state between two
+ * ticks: one launch of tree_jacobian_kernel per launch of advance_adjoint_kernel gives tau and d tau / d(q | T), and the tree
+ * instantiations of the latter contract the cotangents of A_mom, Lambda and I_B with it ("Adjoint of the rollout:
+ * kinematic-tree plant"; executable model: tests/rollout_tree_adjoint_model.py).  The joint selector of
+ * vsmpc_set_kinematics_options is kept by value with the tape: changing it between the taped run and the sweep changes
+ * nothing.  In vsmpc_rollout_backward_full's grad_params the blocks the tree plant does not read -- INERTIA_B, AMOM0, DJ --
+ * are +0.0; everything else is as on the parametric plant.  The tree's own geometry (masses, origins, axes) is held fixed:
+ * gradients to it are not computed.
  *
  * vsmpc_rollout_backward sweeps the tape from the last tick to the first, in stream order.  Per tick: the transpose of the plant
  * advance (advance_adjoint_kernel: the sub-steps are recomputed from the tape and run backwards) turns dL/d(state after the
@@ -663,8 +711,8 @@ int vsmpc_rollout_backward_device(vsmpc_rollout* r, const double* d_log_bar, con
  * cotangent left at its first tick is dropped, as vsmpc_rollout_backward drops it.  A tick that was not Solved contributes
  * nothing through its solve, and still through its plant half and the window.  The first call that asks for either output
  * allocates batch x (VSMPC_PLANT_PARAMS + 6 n_traj + n_alpha) doubles, kept until vsmpc_rollout_destroy; a failure returns
- * VSMPC_ERR_ALLOC and leaves the rollout and its tape usable.  Refusals as vsmpc_rollout_backward's; a rollout with a tree, the
- * jet plant option or an RPYDot track is refused by name (VSMPC_ERR_UNSUPPORTED_CONFIG).
+ * VSMPC_ERR_ALLOC and leaves the rollout and its tape usable.  Refusals as vsmpc_rollout_backward's; a rollout with a tree set
+ * without VSMPC_TREE_ADJOINT, the jet plant option or an RPYDot track is refused by name (VSMPC_ERR_UNSUPPORTED_CONFIG).
  */
 int vsmpc_rollout_backward_full(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0,
                                 double* grad_cfg, double* grad_params, double* grad_traj, int* flags, void* stream);

@@ -64,8 +64,11 @@ SIGNATURES = {
     "vsmpc_small_batch_lds_bytes": ([c_int, c_int, c_int], ctypes.c_size_t),
     "vsmpc_set_kinematics_options": [vp, ip, c_int],
     "vsmpc_provider_batch": [vp, vp, dp, c_int, dp, dp, dp],
+    # h, tree, q, thrust, batch, terms, jac (, stream)
+    "vsmpc_tree_jacobian_batch": [vp, vp, dp, dp, c_int, dp, dp], "vsmpc_tree_jacobian_batch_device": [vp, vp, dp, dp, c_int, dp, dp, vp],
     "vsmpc_rollout_set_attitude_tracks": [vp, dp, dp],
     "vsmpc_rollout_set_tree": [vp, vp],
+    "vsmpc_rollout_set_tree_ex": [vp, vp, ctypes.c_uint],
     "vsmpc_tick": [vp, dp, dp, c_int, dp, dp, vp, vp, vp],
     "vsmpc_rollout_set_jet_plant": [vp, vp, dp, dp],
     "vsmpc_strerror": ([c_int], ctypes.c_char_p),

@@ -207,6 +207,9 @@ def rollout(ro, state0, gains, params, ticks: int, info: dict | None = None, tra
     """(log [ticks, B, 14], final_state [B, 40]) of `ticks` closed-loop ticks from `state0`, differentiable with respect to
     `state0` and `gains`, to `params` when it is a tensor that requires grad ([B, PLANT_PARAMS]), and to the tracks when
     traj = (pos [n_traj, 3], vel [n_traj, 3], alpha [n_alpha]) is given as tensors that require grad (any of the three may be
-    None: that track of the rollout stays as it is) (RolloutFunction)"""
+    None: that track of the rollout stays as it is) (RolloutFunction).
+    Plants: the parametric plant, and the kinematic-tree plant when the rollout's tree was set with set_tree(tree, adjoint=True)
+    -- `params` then gets +0.0 in the blocks that plant does not read (INERTIA_B, AMOM0, DJ); the tree's own geometry is not
+    differentiated.  The jet plant option, an RPYDot track and a tree set without adjoint=True are refused by the taped run."""
     pos, vel, alpha = (None, None, None) if traj is None else traj
     return RolloutFunction.apply(ro, state0, gains, params, ticks, info, pos, vel, alpha)

@@ -13,11 +13,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libvsmpc.so")
 SOLVE = "vsmpc_kernels.hip"     # the per-horizon unit: production / diagnostic / per-instance-tunables instantiations
-SOURCES = [SOLVE, "vsmpc_dispatch.hip", "vsmpc_rollout.hip", "vsmpc_rollout_adjoint.hip", "vsmpc_capi.hip", "vsmpc_capi_solve.hip", "vsmpc_capi_debug.hip",
-           "vsmpc_capi_rollout.hip", "vsmpc_jet.hip", "vsmpc_provider.hip", "vsmpc_runtime.hip", "vsmpc_certify.hip"]
+SOURCES = [SOLVE, "vsmpc_dispatch.hip", "vsmpc_rollout.hip", "vsmpc_rollout_adjoint.hip", "vsmpc_rollout_tree_adjoint.hip", "vsmpc_capi.hip", "vsmpc_capi_solve.hip", "vsmpc_capi_debug.hip",
+           "vsmpc_capi_rollout.hip", "vsmpc_jet.hip", "vsmpc_provider.hip", "vsmpc_tree_jacobian.hip", "vsmpc_runtime.hip", "vsmpc_certify.hip"]
 HEADERS = ["vsmpc_device.hpp", "vsmpc_launch.hpp", "vsmpc_host.hpp", "vsmpc_p0.hpp", "vsmpc_smem.hpp", "vsmpc_p1_syrk.hpp", "vsmpc_p1_struct.hpp",
            "vsmpc_p3.hpp", "vsmpc_p4.hpp", "vsmpc_p5.hpp", "vsmpc_panel_asm.inc",
-           "vsmpc_structure.hpp", "vsmpc_rt_core.hpp", "vsmpc_rt_sens.hpp", "vsmpc_rt_adjoint.hpp", "vsmpc_rt_adjoint_record.hpp", "vsmpc_solve_body.inc", "vsmpc_jet_device.hpp", "vsmpc_rollout_device.hpp", "vsmpc_horizons.def", os.path.join("..", "..", "include", "vsmpc.h"),
+           "vsmpc_structure.hpp", "vsmpc_rt_core.hpp", "vsmpc_rt_sens.hpp", "vsmpc_rt_adjoint.hpp", "vsmpc_rt_adjoint_record.hpp", "vsmpc_solve_body.inc", "vsmpc_jet_device.hpp", "vsmpc_rollout_device.hpp", "vsmpc_rollout_adjoint_body.inc", "vsmpc_horizons.def", os.path.join("..", "..", "include", "vsmpc.h"),
            os.path.join("..", "..", "include", "vsmpc_jet.h")]
 
 

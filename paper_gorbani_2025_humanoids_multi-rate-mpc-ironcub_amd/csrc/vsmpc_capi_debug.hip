@@ -1,5 +1,6 @@
 // C-ABI of include/vsmpc.h, the entries beside the hot path: linearisation and dense-QP debug assembly, the condensed
-// matrices and phase stamps of the solve kernel, kinematics terms and the kinematics provider, event timing.
+// matrices and phase stamps of the solve kernel, kinematics terms, the kinematics provider and the Jacobian of the tree plant's
+// terms, event timing.
 #include "vsmpc_host.hpp"
 
 using namespace vsmpc;
@@ -194,6 +195,41 @@ int vsmpc_provider_batch(vsmpc_handle* h, const vsmpc_tree* tree, const double* 
         HIP_TRY(hipMemcpy(robot, d_robot, size_t(batch) * VSMPC_RO_SIZE * sizeof(double), hipMemcpyDeviceToHost));
     if (records != nullptr)
         HIP_TRY(hipMemcpy(records, h->d_in, size_t(batch) * h->n_in * sizeof(double), hipMemcpyDeviceToHost));
+    return VSMPC_OK;
+}
+
+int vsmpc_tree_jacobian_batch_device(vsmpc_handle* h, const vsmpc_tree* tree, const double* d_q, const double* d_thrust, int batch,
+                                     double* d_terms, double* d_jac, void* stream) {
+    if (h == nullptr || tree == nullptr || d_q == nullptr || d_thrust == nullptr || batch <= 0) return invalid_arg();
+    if (h->kin.constant_lambda) return unsupported();   // the provider delivers the current Jacobians (vsmpc_provider_batch)
+    if (!tree_valid(*tree)) return invalid_arg();
+    if (d_terms == nullptr && d_jac == nullptr) return VSMPC_OK;
+    ON_DEVICE(h->device);
+    HIP_TRY(launch_tree_jacobian(*tree, h->kin, d_q, VSMPC_TREE_NJ, d_thrust, VSMPC_N_THRUSTS, batch, d_terms, d_jac,
+                                 static_cast<hipStream_t>(stream)));
+    return VSMPC_OK;
+}
+
+int vsmpc_tree_jacobian_batch(vsmpc_handle* h, const vsmpc_tree* tree, const double* q, const double* thrust, int batch,
+                              double* terms, double* jac) {
+    if (h == nullptr || tree == nullptr || q == nullptr || thrust == nullptr || batch <= 0) return invalid_arg();
+    if (h->kin.constant_lambda) return unsupported();
+    if (!tree_valid(*tree)) return invalid_arg();
+    if (terms == nullptr && jac == nullptr) return VSMPC_OK;
+    ON_DEVICE(h->device);
+    const size_t B = size_t(batch), nj = size_t(VSMPC_TT_SIZE) * VSMPC_TT_NDIR;
+    DevBuf<double> d_q, d_t, d_terms, d_jac;   // a stand-alone entry of any batch: its own staging, freed on return
+    hipError_t e = d_q.alloc(B * VSMPC_TREE_NJ);
+    if (e == hipSuccess) e = d_t.alloc(B * VSMPC_N_THRUSTS);
+    if (e == hipSuccess && terms != nullptr) e = d_terms.alloc(B * VSMPC_TT_SIZE);
+    if (e == hipSuccess && jac != nullptr) e = d_jac.alloc(B * nj);
+    if (e != hipSuccess) return e == hipErrorOutOfMemory ? VSMPC_ERR_ALLOC : hip_fail(e, "vsmpc_tree_jacobian_batch");
+    HIP_TRY(hipMemcpy(d_q, q, B * VSMPC_TREE_NJ * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_t, thrust, B * VSMPC_N_THRUSTS * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(launch_tree_jacobian(*tree, h->kin, d_q, VSMPC_TREE_NJ, d_t, VSMPC_N_THRUSTS, batch, d_terms, d_jac, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    if (terms != nullptr) HIP_TRY(hipMemcpy(terms, d_terms, B * VSMPC_TT_SIZE * sizeof(double), hipMemcpyDeviceToHost));
+    if (jac != nullptr) HIP_TRY(hipMemcpy(jac, d_jac, B * nj * sizeof(double), hipMemcpyDeviceToHost));
     return VSMPC_OK;
 }
 

@@ -148,15 +148,33 @@ int vsmpc_rollout_set_attitude_tracks(vsmpc_rollout* r, const double* traj_rpy, 
     return VSMPC_OK;
 }
 
-int vsmpc_rollout_set_tree(vsmpc_rollout* r, const vsmpc_tree* tree) {
-    if (r == nullptr) return invalid_arg();
+int vsmpc_rollout_set_tree(vsmpc_rollout* r, const vsmpc_tree* tree) { return vsmpc_rollout_set_tree_ex(r, tree, 0u); }
+
+int vsmpc_rollout_set_tree_ex(vsmpc_rollout* r, const vsmpc_tree* tree, unsigned flags) {
+    if (r == nullptr || (flags & ~VSMPC_TREE_ADJOINT) != 0u) return invalid_arg();
     ON_DEVICE(r->h->device);
+    const bool adjoint = tree != nullptr && (flags & VSMPC_TREE_ADJOINT) != 0u;
+    const size_t B = size_t(r->batch);
+    if (adjoint) {   // first, what the flag can fail on: a refused call leaves the rollout as it was
+        if (r->h->kin.constant_lambda) return unsupported();
+        if (!tree_valid(*tree)) return invalid_arg();
+        // every buffer of the tree plant, the forward run's two among them, in front of anything that changes the rollout
+        hipError_t e = hipSuccess;
+        if (r->d_rs == nullptr) e = r->d_rs.alloc(B * VSMPC_RS_SIZE);
+        if (e == hipSuccess && r->d_ro == nullptr) e = r->d_ro.alloc(B * VSMPC_RO_SIZE);
+        if (e == hipSuccess && r->d_tj == nullptr) {   // (d_tj last of the two: its presence says that both are there)
+            e = r->d_tt.alloc(B * VSMPC_TT_SIZE);
+            if (e == hipSuccess) e = r->d_tj.alloc(B * VSMPC_TT_SIZE * VSMPC_TT_NDIR);
+            if (e != hipSuccess) r->d_tt.reset();
+        }
+        if (e != hipSuccess) return alloc_fail(e, "vsmpc_rollout_set_tree_ex");
+    }
     invalidate(r);   // the captured ticks have other launches
     r->use_tree = 0;
     r->rd.tree = 0;
+    r->tree_adjoint = 0;
     if (tree == nullptr) return VSMPC_OK;
     if (!tree_valid(*tree)) return invalid_arg();
-    const size_t B = size_t(r->batch);
     if (r->d_rs == nullptr) HIP_TRY(r->d_rs.alloc(B * VSMPC_RS_SIZE));
     if (r->d_ro == nullptr) HIP_TRY(r->d_ro.alloc(B * VSMPC_RO_SIZE));
     r->tree = *tree;
@@ -165,6 +183,7 @@ int vsmpc_rollout_set_tree(vsmpc_rollout* r, const vsmpc_tree* tree) {
     r->rd.tree_ro = r->d_ro;
     r->rd.tree_kout = r->h->d_kout;
     r->rd.tree_kin = r->h->d_kin;
+    r->tree_adjoint = adjoint ? 1 : 0;
     return VSMPC_OK;
 }
 
@@ -350,6 +369,15 @@ int enqueue_sweep(vsmpc_rollout* r, const double* d_log_bar, hipStream_t s, bool
     a.gin = tp.gin; a.gcfg_t = tp.gcfg_t; a.flags_t = tp.flags_t;
     a.sbar = tp.sbar; a.wbar = tp.wbar; a.fmbar = tp.fmbar; a.gcfg = tp.gcfg; a.flags = tp.flags;
     for (int k = T; k >= 0; --k) {
+        if (r->use_tree) {
+            // tau and its Jacobian at the state between ticks k - 1 and k: the tape's row k, behind the last tick the state the
+            // run left (an untaped run, a reset and the set_* calls all drop the tape), under the taped run's joint selector
+            const double* sk = k < T ? tp.s + size_t(k) * B * VSMPC_PLANT_STATE : r->d_state.get();
+            HIP_TRY(launch_tree_jacobian(r->tree, tp.kin, sk + VSMPC_PS_Q, VSMPC_PLANT_STATE, sk + VSMPC_PS_T, VSMPC_PLANT_STATE,
+                                         r->batch, r->d_tt, r->d_tj, s));
+            a.tree_terms = r->d_tt;
+            a.tree_jac = r->d_tj;
+        }
         if (k < T) {
             const int rc = vsmpc_adjoint_record_batch_device(h, tp.rec + size_t(k) * B * h->n_in, r->use_tun ? r->d_tun.get() : nullptr,
                                                              tp.xbar, tp.fmbar, r->batch, nullptr, nullptr, tp.bstatus, nullptr,
@@ -378,7 +406,8 @@ int run(vsmpc_rollout* r, int ticks, double* log, void* stream, bool taped) {
     if (r == nullptr || ticks < 0) return invalid_arg();
     if (!r->valid) return invalid_arg();   // never reset, or a previous run failed half-way: reset() first
     if (taped) {                           // what the backward sweep has no transpose of
-        if (r->use_tree) return unsupported("vsmpc_rollout_run_taped: no adjoint of the kinematic-tree plant (vsmpc_rollout_set_tree)");
+        if (r->use_tree && !r->tree_adjoint)
+            return unsupported("vsmpc_rollout_run_taped: no adjoint of the kinematic-tree plant (vsmpc_rollout_set_tree)");
         if (r->rd.jet_nn) return unsupported("vsmpc_rollout_run_taped: no adjoint of the jet plant option (vsmpc_rollout_set_jet_plant)");
         if (r->rd.traj_rpyd != nullptr)
             return unsupported("vsmpc_rollout_run_taped: no adjoint of an RPYDot track (vsmpc_rollout_set_attitude_tracks)");
@@ -407,6 +436,8 @@ int run(vsmpc_rollout* r, int ticks, double* log, void* stream, bool taped) {
     if (taped) {
         r->tape.ticks = ticks;
         r->tape.tick_base = r->ticks_done - ticks;
+        r->tape.kin = h->kin;
+        r->tape.kin.constant_lambda = 0;   // as enqueue_tree flies it
     }
     return VSMPC_OK;
 }
@@ -427,7 +458,8 @@ hipError_t seed_sbar(vsmpc_rollout* r, const double* state_bar, hipMemcpyKind ki
 // for derivatives of a plant that has none
 int full_refusal(const vsmpc_rollout* r) {
     if (r == nullptr) return invalid_arg();
-    if (r->use_tree) return unsupported("vsmpc_rollout_backward_full: no adjoint of the kinematic-tree plant (vsmpc_rollout_set_tree)");
+    if (r->use_tree && !r->tree_adjoint)
+        return unsupported("vsmpc_rollout_backward_full: no adjoint of the kinematic-tree plant (vsmpc_rollout_set_tree)");
     if (r->rd.jet_nn) return unsupported("vsmpc_rollout_backward_full: no adjoint of the jet plant option (vsmpc_rollout_set_jet_plant)");
     if (r->rd.traj_rpyd != nullptr)
         return unsupported("vsmpc_rollout_backward_full: no adjoint of an RPYDot track (vsmpc_rollout_set_attitude_tracks)");

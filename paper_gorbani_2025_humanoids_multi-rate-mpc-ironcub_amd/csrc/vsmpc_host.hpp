@@ -174,6 +174,10 @@ struct vsmpc_rollout {
     vsmpc_tree tree;
     vsmpc::DevBuf<double> d_rs;   // provider states [batch][VSMPC_RS_SIZE]
     vsmpc::DevBuf<double> d_ro;   // Robot-level outputs of the provider [batch][VSMPC_RO_SIZE]
+    // VSMPC_TREE_ADJOINT (vsmpc_rollout_set_tree_ex): the sweep's rows of one launch, terms [batch][VSMPC_TT_SIZE] and their
+    // Jacobian [batch][VSMPC_TT_SIZE][VSMPC_TT_NDIR] (allocated by the first call with the flag)
+    int tree_adjoint;
+    vsmpc::DevBuf<double> d_tt, d_tj;
     // per-instance tunables (vsmpc_rollout_set_tunables)
     int use_tun;
     vsmpc::DevBuf<double> d_tun;  // rows [batch][VSMPC_TUNE_SIZE]
@@ -182,6 +186,7 @@ struct vsmpc_rollout {
         int ticks = 0;        // ticks on the tape; 0: none (never taped, or invalidated by reset / set_* / an untaped run)
         int cap = 0;          // ticks the four buffers below hold
         int tick_base = 0;    // the rollout's tick counter at the start of the taped run
+        vsmpc::KinOpts kin = {};   // tree plant: the handle's kinematics options (joint selector) the taped run flew with
         vsmpc::DevBuf<double> s, rec, fm;   // [cap][batch][VSMPC_PLANT_STATE | n_in | VSMPC_FM_SIZE]
         vsmpc::DevBuf<int> status;          // [cap][batch]
         // per-instance rows of the sweep: cotangents of the plant state, the window and the first move; the record adjoint's

@@ -163,6 +163,13 @@ hipError_t launch_provider(const vsmpc_tree& tree, const double* d_state, int ba
 hipError_t launch_kinematics_patch(const double* d_kin, int batch, double* d_records, int n_in, const KinOpts& opts,
                                    hipStream_t stream);
 
+// tree_jacobian_kernel (vsmpc_tree_jacobian.hip): terms [batch][VSMPC_TT_SIZE] and / or their Jacobian [batch][VSMPC_TT_SIZE]
+// [VSMPC_TT_NDIR] (either may be nullptr) of the tree at the joints d_q + b q_stride [8] and thrusts d_thrust + b t_stride [4]
+// of instance b (rows of their own, or a row of plant states), base at the origin with identity attitude; opts.sel picks
+// Lambda_ang's columns (opts.constant_lambda is the caller's to refuse)
+hipError_t launch_tree_jacobian(const vsmpc_tree& tree, const KinOpts& opts, const double* d_q, int q_stride, const double* d_thrust,
+                                int t_stride, int batch, double* d_terms, double* d_jac, hipStream_t stream);
+
 // closed-loop rollout (vsmpc_rollout.hip)
 struct RolloutDev {
     int n_in, n_ref, ratio, n_traj, n_alpha;
@@ -245,7 +252,14 @@ struct RolloutAdj {
     // [6 n_traj + n_alpha], one row per instance
     double* gpar;
     double* gtraj;
+    // kinematic-tree plant (vsmpc_rollout_set_tree_ex with VSMPC_TREE_ADJOINT): both or neither.  Given, the launch runs the
+    // kernel's tree instantiations on tau = terms(q, T) [VSMPC_TT_SIZE] of the state in front of tick_rec (= behind
+    // tick_plant) and its Jacobian [VSMPC_TT_SIZE][VSMPC_TT_NDIR] (launch_tree_jacobian on that state)
+    const double* tree_terms;
+    const double* tree_jac;
 };
 hipError_t launch_advance_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream);
+// the tree instantiations (vsmpc_rollout_tree_adjoint.hip): what launch_advance_adjoint launches when a.tree_terms is given
+hipError_t launch_advance_tree_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream);
 
 }  // namespace vsmpc

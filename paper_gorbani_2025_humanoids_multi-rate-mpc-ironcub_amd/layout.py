@@ -50,6 +50,15 @@ KIN_R = 694
 KIN_SIZE = 697
 KIN_OUT = 57
 
+# terms of the kinematic-tree plant and the directions of their Jacobian (vsmpc_tree_jacobian_batch, VSMPC_TT_*)
+TT_AMOM = 0
+TT_LLIN = 24
+TT_LANG = 48
+TT_IB = 72
+TT_SIZE = 81
+TT_NDIR = 12
+TREE_ADJOINT = 0x1   # vsmpc_rollout_set_tree_ex flag (VSMPC_TREE_ADJOINT)
+
 # first-move block (24 doubles): dq(8) v0(4) throttle%(4) T1(4) Tdot1(4)
 FM_DQ = 0
 FM_V0 = 8

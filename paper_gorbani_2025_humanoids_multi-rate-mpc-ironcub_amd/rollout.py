@@ -216,14 +216,19 @@ class ClosedLoopRollout:
                 raise ValueError(f"attitude tracks must be [{self.n_traj}, 3]")
         _lib.check(self.lib.vsmpc_rollout_set_attitude_tracks(self._r, _ptr(a), _ptr(b)), "vsmpc_rollout_set_attitude_tracks")
 
-    def set_tree(self, tree: dict | None):
+    def set_tree(self, tree: dict | None, adjoint: bool = False):
         """Kinematic-tree plant (vsmpc_rollout_set_tree): `tree` = a robot_tree dictionary (None = the parametric plant).
         The plant's A_mom(q), I_B(q) and the MPC's Lambda terms then all come from the kinematics provider on the plant's
-        own joints.  Call reset() afterwards; params[:, PP_MASS] must be the tree's total mass."""
+        own joints.  Call reset() afterwards; params[:, PP_MASS] must be the tree's total mass.
+        adjoint: vsmpc_rollout_set_tree_ex with VSMPC_TREE_ADJOINT -- run(tape=True) and backward() then work on the tree
+        plant (the rollout allocates the rows of the tree's terms and their Jacobian); without it they are refused."""
         from . import robot_tree as RT
         self._ctree = None if tree is None else RT.to_c(tree)    # (kept alive; the library copies it anyway)
-        _lib.check(self.lib.vsmpc_rollout_set_tree(self._r, None if tree is None else ctypes.byref(self._ctree)),
-                   "vsmpc_rollout_set_tree")
+        ctree = None if tree is None else ctypes.byref(self._ctree)
+        if adjoint:
+            _lib.check(self.lib.vsmpc_rollout_set_tree_ex(self._r, ctree, L.TREE_ADJOINT), "vsmpc_rollout_set_tree_ex")
+        else:
+            _lib.check(self.lib.vsmpc_rollout_set_tree(self._r, ctree), "vsmpc_rollout_set_tree")
 
     def set_tunables(self, configs=None, tunables=None):
         """Per-instance weights and throttle box for the loops' solves (vsmpc_rollout_set_tunables): `configs` = one

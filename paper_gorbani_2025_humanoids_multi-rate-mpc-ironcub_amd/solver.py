@@ -424,6 +424,38 @@ class BatchedVSMPC:
                                                  _ptr(records)), "vsmpc_provider_batch")
         return kin, robot
 
+    def tree_jacobian(self, tree: dict, q: np.ndarray, thrust: np.ndarray, terms: bool = True, jac: bool = True):
+        """vsmpc_tree_jacobian_batch: what the kinematic-tree plant of a rollout hands a tick at joints q [B, 8] and thrusts
+        [B, 4] (base at the origin, identity attitude) -- terms [B, 81] = A_mom,body | Lambda_lin,B | Lambda_ang,B | I_B
+        (layout.TT_*) -- and their Jacobian jac [B, 81, 12] to (q | thrust).  Returns (terms, jac); either is None when not
+        asked for.  Lambda_ang takes its columns through set_kinematics_options' selector."""
+        from . import robot_tree as RT
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        thrust = np.ascontiguousarray(thrust, dtype=np.float64)
+        if q.ndim != 2 or q.shape[1] != RT.NJ or thrust.shape != (q.shape[0], RT.NJETS):
+            raise ValueError(f"q must be [batch, {RT.NJ}] and thrust [batch, {RT.NJETS}]")
+        n = q.shape[0]
+        o_terms = np.empty((n, L.TT_SIZE)) if terms else None
+        o_jac = np.empty((n, L.TT_SIZE, L.TT_NDIR)) if jac else None
+        ctree = RT.to_c(tree)
+        _lib.check(self.lib.vsmpc_tree_jacobian_batch(self._h, ctypes.byref(ctree), _ptr(q), _ptr(thrust), n, _ptr(o_terms),
+                                                      _ptr(o_jac)), "vsmpc_tree_jacobian_batch")
+        return o_terms, o_jac
+
+    def tree_jacobian_device(self, tree: dict, d_q, d_thrust, d_terms=None, d_jac=None, stream=None):
+        """vsmpc_tree_jacobian_batch_device on float64 CUDA tensors: d_q [B, 8], d_thrust [B, 4] -> d_terms [B, 81] and / or
+        d_jac [B, 81, 12] (None: not wanted).  Only enqueues on `stream` (default: torch's current stream)."""
+        from . import robot_tree as RT
+        _assert_f64_device(d_q, d_thrust, d_terms, d_jac)
+        n = d_q.shape[0]
+        assert d_q.shape == (n, RT.NJ) and d_thrust.shape == (n, RT.NJETS)
+        assert d_terms is None or d_terms.numel() == n * L.TT_SIZE
+        assert d_jac is None or d_jac.numel() == n * L.TT_SIZE * L.TT_NDIR
+        ctree = RT.to_c(tree)
+        _lib.check(self.lib.vsmpc_tree_jacobian_batch_device(self._h, ctypes.byref(ctree), _dptr(d_q), _dptr(d_thrust), n,
+                                                             _dptr(d_terms), _dptr(d_jac), _stream(d_q, stream)),
+                   "vsmpc_tree_jacobian_batch_device")
+
     def set_kinematics_options(self, joint_selector=None, constant_lambda: bool = False):
         """vsmpc_set_kinematics_options: robot joint indices of the controlled joints (Lambda_ang columns; the
         reference selects them by name) and jointsLambdaOption 'constant'."""

@@ -4,7 +4,12 @@ launch alone (vsmpc_adjoint_record_batch_device on the records of one tick, the 
 of the sweep that also returns the parameter and track gradients (vsmpc_rollout_backward_full_device: the same launches, the
 second instantiation of advance_adjoint_kernel).
 
-    python tools/rollout_adjoint_bench.py [--out profiles/rollout_adjoint_bench.txt] [--rounds 7]
+    python tools/rollout_adjoint_bench.py [--out profiles/rollout_adjoint_bench.txt] [--rounds 7] [--tree]
+
+--tree: instead, a backward tick on the kinematic-tree plant (set_tree(tree, adjoint=True)) against a backward tick on the
+parametric plant of the same build -- two rollouts of the same workloads in one process, their sweeps alternating -- with
+the Jacobian launch every launch of the tree sweep contains (vsmpc_tree_jacobian_batch_device on a row of plant states) alone
+beside them.
 
 Workloads: batch 256 hover and batch 4096 take-off at the paper horizon (17, 7, 12), tuned handle.  Host clock around calls
 that end in a synchronise; the five kinds ALTERNATE, `rounds` windows each after a warm-up window of all, and the report is
@@ -97,16 +102,93 @@ def run_case(workload, batch, ticks, rounds):
     return lines
 
 
+def run_tree_case(workload, batch, ticks, rounds):
+    """a backward tick on the tree plant against one on the parametric plant, and the Jacobian launch alone"""
+    import torch
+    layout = importlib.import_module(PKG + ".layout")
+    ro = importlib.import_module(PKG + ".rollout")
+    tree = importlib.import_module(PKG + ".robot_tree").default_tree()
+    cfg = layout.paper_config()
+    pos, vel, alpha, adt = ro.make_trajectory(cfg, workload, 60.0)
+    dev = torch.device("cuda:0")
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    rng = np.random.default_rng(0)
+    d_lb = torch.from_numpy(rng.standard_normal((ticks, batch, layout.ROLLOUT_LOG))).to(dev)
+    d_sb = torch.from_numpy(rng.standard_normal((batch, layout.PLANT_STATE))).to(dev)
+    d_g0, d_gg, d_fl = torch.empty((batch, layout.PLANT_STATE), **f64), torch.empty((batch, layout.GRAD_SIZE), **f64), torch.empty(batch, **i32)
+    d_gp, d_gt = torch.empty((batch, layout.PLANT_PARAMS), **f64), torch.empty((batch, 6 * len(pos) + len(alpha)), **f64)
+    s = torch.cuda.current_stream(dev)
+    rolls = {}
+    for plant in ("parametric", "tree"):
+        r = ro.ClosedLoopRollout(cfg, batch, pos, vel, alpha, adt, device=0, adjoint=True)
+        if plant == "tree":
+            r.set_tree(tree, adjoint=True)
+            st, pa = ro.make_plant_tree(cfg, batch, tree, workload=workload)
+        else:
+            st, pa = ro.make_plant(cfg, batch, workload=workload)
+        r.reset(st, pa)
+        r.run(ticks, log=False, tape=True)
+        rolls[plant] = r
+    d_q = torch.from_numpy(rolls["tree"].state()[:, layout.PS_Q:layout.PS_Q + 8].copy()).to(dev)
+    d_T = torch.from_numpy(rolls["tree"].state()[:, layout.PS_T:layout.PS_T + 4].copy()).to(dev)
+    d_tt, d_tj = torch.empty((batch, layout.TT_SIZE), **f64), torch.empty((batch, layout.TT_SIZE, layout.TT_NDIR), **f64)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / ticks         # us per tick
+
+    def jacobian_alone():
+        for _ in range(ticks):
+            rolls["tree"].mpc.tree_jacobian_device(tree, d_q, d_T, d_tt, d_tj, stream=s)
+
+    kinds = {}
+    for plant, r in rolls.items():
+        kinds["backward_" + plant] = lambda r=r: r.backward_device(d_lb, d_sb, d_g0, d_gg, d_fl, stream=s)
+        kinds["backward_full_" + plant] = lambda r=r: r.backward_device(d_lb, d_sb, d_g0, d_gg, d_fl, stream=s, d_grad_params=d_gp,
+                                                                          d_grad_traj=d_gt)
+    kinds["jacobian_alone"] = jacobian_alone
+    for fn in kinds.values():
+        timed(fn)
+    t = {k: [] for k in kinds}
+    flags = {}
+    for _ in range(rounds):
+        for k, fn in kinds.items():
+            t[k].append(timed(fn))
+            if k.startswith("backward_full_"):
+                flags[k[len("backward_full_"):]] = (d_fl.cpu().numpy(), bool(torch.isfinite(d_g0).all()) and bool(torch.isfinite(d_gp).all()))
+    med = {k: statistics.median(v) for k, v in t.items()}
+    lines = [f"paper {workload} batch {batch} ({rolls['tree'].mpc.kernel_name}), {rounds} alternating windows of {ticks} ticks; last sweeps: "
+             + "; ".join(f"{plant}: {int((fl & layout.ADJ_UNSOLVED != 0).sum())} loops with an unsolved tick, "
+                         f"{int((fl & layout.ADJ_DEGENERATE != 0).sum())} with a degenerate one, gradients finite: {fin}"
+                         for plant, (fl, fin) in flags.items())]
+    for k in kinds:
+        unit = "us/launch" if k == "jacobian_alone" else "us/tick"
+        lines.append(f"  {k:24s}  median {med[k]:10.2f} {unit}  min {min(t[k]):10.2f}  max {max(t[k]):10.2f}  "
+                     f"spread {100.0 * (max(t[k]) - min(t[k])) / med[k]:.2f} %")
+    for k in ("backward", "backward_full"):
+        a, b = k + "_tree", k + "_parametric"
+        ratios = [x / y for x, y in zip(t[a], t[b])]
+        lines.append(f"  {a} / {b} (medians) {med[a] / med[b]:.4f}   per round min {min(ratios):.4f} max {max(ratios):.4f};   "
+                     f"difference {med[a] - med[b]:.2f} us/tick, of which the Jacobian launch alone is {med['jacobian_alone']:.2f}")
+    for r in rolls.values():
+        r.close()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--tree", action="store_true", help="the tree plant's backward tick against the parametric plant's")
     a = ap.parse_args()
     sys.path.insert(0, ROOT)
     import torch
-    lines = [f"python tools/rollout_adjoint_bench.py --rounds {a.rounds} on {torch.cuda.get_device_name(0)}"]
+    lines = [f"python tools/rollout_adjoint_bench.py --rounds {a.rounds}{' --tree' if a.tree else ''} on {torch.cuda.get_device_name(0)}"]
     for workload, batch, ticks in CASES:
-        lines += run_case(workload, batch, ticks, a.rounds)
+        lines += (run_tree_case if a.tree else run_case)(workload, batch, ticks, a.rounds)
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if a.out:
