@@ -23,18 +23,22 @@
 //                   (p' = R h_lin / m, alpha m R^T g), I_B^-1 through omega, the push where push_active holds, alpha of the
 //                   sub-step to its two samples; behind the sub-steps A_mom0, DJ and q_ref0 from the cotangent of A_mom(q).
 //
+// Layout: the device code is csrc/vsmpc_rollout_adjoint_device.hpp -- advance_adjoint_body<PT, TREE>, a driver over one function
+// per phase (stage-in; record half: set-up, pull-back to the state, to the parameters, FIFO shift, `first` fill; plant half:
+// set-up, forward sub-steps, backward sub-steps, what follows them; write-out), each with its contract above it.  This unit
+// holds the parametric plant's kernel template and the launcher; vsmpc_rollout_tree_adjoint.hip holds the tree plant's.
+//
 // Mirror of tests/rollout_adjoint_model.py (plant_adjoint, record_adjoint) and tests/rollout_param_adjoint_model.py, which are
 // checked against central differences of the forward loop model; the tree instantiations mirror
 // tests/rollout_tree_adjoint_model.py.  Polynomial jet model only (the entry refuses the jet plant option).
-#include "vsmpc_device.hpp"
-#include "vsmpc_launch.hpp"
-#include "vsmpc_rollout_device.hpp"
+#include "vsmpc_rollout_adjoint_device.hpp"
 
 namespace vsmpc {
 
-#define VS_ADJ_KERNEL advance_adjoint_kernel
-#define VS_ADJ_TREE false
-#include "vsmpc_rollout_adjoint_body.inc"
+template <bool PT>
+__global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd, RolloutAdj a) {
+    advance_adjoint_body<PT, false>(rd, a);
+}
 
 hipError_t launch_advance_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream) {
     if (a.tree_terms != nullptr && a.tree_jac != nullptr) return launch_advance_tree_adjoint(rd, a, stream);

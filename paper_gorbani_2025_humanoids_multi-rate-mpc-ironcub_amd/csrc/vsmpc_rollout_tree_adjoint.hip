@@ -1,16 +1,16 @@
 // The kinematic-tree plant's instantiations of the rollout's backward sweep (vsmpc_rollout_set_tree_ex with
-// VSMPC_TREE_ADJOINT): the body of advance_adjoint_kernel (vsmpc_rollout_adjoint_body.inc, where the differences are
-// described) compiled with TREE on, in a unit of its own so that the parametric plant's kernels stay what they were.
+// VSMPC_TREE_ADJOINT): advance_adjoint_body (vsmpc_rollout_adjoint_device.hpp, where the phases and the differences are
+// described) with TREE on, its kernel template and launcher in a unit of their own so that the parametric plant's kernels
+// stay what they were.
 // Mirror of tests/rollout_tree_adjoint_model.py.
-#include "vsmpc_device.hpp"
-#include "vsmpc_launch.hpp"
-#include "vsmpc_rollout_device.hpp"
+#include "vsmpc_rollout_adjoint_device.hpp"
 
 namespace vsmpc {
 
-#define VS_ADJ_KERNEL advance_tree_adjoint_kernel
-#define VS_ADJ_TREE true
-#include "vsmpc_rollout_adjoint_body.inc"
+template <bool PT>
+__global__ __launch_bounds__(RO_BLOCK) void advance_tree_adjoint_kernel(RolloutDev rd, RolloutAdj a) {
+    advance_adjoint_body<PT, true>(rd, a);
+}
 
 hipError_t launch_advance_tree_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream) {
     if (a.gpar != nullptr && a.gtraj != nullptr)

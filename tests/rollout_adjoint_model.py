@@ -159,9 +159,13 @@ def _dv_du(u):
     return am.dv_dthrottle(u)
 
 
-def plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next, substeps=None, mutation=None):
+def plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next, substeps=None, mutation=None, trace=None):
     """Transpose of rollout_model.advance at (s, fm, status): sbar_next [40] = dL/d s_{t+1} -> (direct part of dL/d s_t [40],
-    fmbar [24]).  The sub-steps are recomputed and kept, then run backwards."""
+    fmbar [24]).  The sub-steps are recomputed and kept, then run backwards.  This is the only copy of that recursion: `trace`
+    (a dict, or None) receives what a caller builds further shares of the sub-steps from (rollout_param_adjoint_model) --
+    "steps": one (x, lam, R, dR, om, ombar, alpha, dist, t) per sub-step, in the order the recursion takes them (the last
+    sub-step first), lam the cotangent behind the sub-step; "h", "Abar" [6, 4], and "q", "DJ": the joints after the move and
+    d A_mom / dq there."""
     substeps = substeps_of(cfg) if substeps is None else substeps
     solved = status == L.STATUS_SOLVED or mutation == "unsolved_as_solved"
     s = np.array(s, dtype=float)
@@ -182,7 +186,7 @@ def plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next,
         xs.append(x.copy())
         x = pm.substep(cfg, x, p, tk, ss, substeps, A, IB, vthr, alpha_track, alpha_dt)
     lam = np.array(sbar_next[0:20], dtype=float)
-    Abar, vbar = np.zeros((6, 4)), np.zeros(4)
+    Abar, vbar, steps = np.zeros((6, 4)), np.zeros(4), []
     for ss in range(substeps - 1, -1, -1):
         x = xs[ss]
         t = (tk + ss / substeps) * cfg.period_mpc
@@ -199,6 +203,7 @@ def plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next,
         dEr = np.array([[0.0, cr * tp, -sr * tp], [0.0, -sr, -cr], [0.0, cr / cp, -sr / cp]])
         dEp = np.array([[0.0, sr / cp ** 2, cr / cp ** 2], [0.0, 0.0, 0.0], [0.0, sr * tp / cp, cr * tp / cp]])
         ombar = np.cross(ll, hl) + np.cross(la, ha) + E.T @ lr
+        steps.append((x, lam, R, dR, om, ombar, alpha, dist, t))
         fw = alpha * m * np.array([0.0, 0.0, -GRAV])           # world-frame force that enters through R^T
         if dist:
             fw = fw + p[L.PP_DIST_F:L.PP_DIST_F + 3]
@@ -221,6 +226,8 @@ def plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next,
         Abar[0:3] += h * np.outer(ll, T)
         Abar[3:6] += h * np.outer(la, T)
         lam = lam + h * g
+    if trace is not None:
+        trace.update(steps=steps, h=h, Abar=Abar, q=s[L.PS_Q:L.PS_Q + 8], DJ=DJ)
     qbar = np.array(sbar_next[L.PS_Q:L.PS_Q + 8], dtype=float)
     if mutation != "drop_amom_qbar":
         qbar += np.einsum("jrc,rc->j", DJ, Abar)

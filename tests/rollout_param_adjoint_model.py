@@ -5,19 +5,20 @@ vsmpc_rollout_backward_full (the PT instantiation of advance_adjoint_kernel in c
 
   backward     rollout_adjoint_model.backward's sweep with the last step of the chain rule added at both halves of a tick:
                record_param_adjoint at the taped state (the record's entries that are parameters or are built from them, the
-               window columns at the moment their cotangent is complete, alpha of the tick), plant_param_adjoint at every
-               sub-step (mass, I_B^-1, the jet map, the push, alpha of the sub-step).  Written from the formulas.
+               window columns at the moment their cotangent is complete, alpha of the tick), plant_param_adjoint in place of
+               plant_adjoint (every sub-step: mass, I_B^-1, the jet map, the push, alpha of the sub-step).  Written from the
+               formulas.
   central      central differences of rollout_adjoint_model.forward along directions in the parameters and the tracks,
                Richardson extrapolated as rollout_adjoint_model.central.
 
 The derivative is taken with the tick state at the start of the taped run held fixed, except at a reset (`first`), where the
 window is built from the tracks and is differentiated.  DIST_T0, DIST_T1 and TICK0 are structural: +0.0.
-rollout_adjoint_model, rollout_model, tick_model and adjoint_record_model are imported and not changed.  `mutation` (one of
-MUTATIONS) plants one defect, for the mutation tests only.
+rollout_model, tick_model and adjoint_record_model are imported and not changed.  The state recursion of the sub-steps is
+rollout_adjoint_model.plant_adjoint's, the one copy: plant_param_adjoint calls it and builds its shares from the per-sub-step
+quantities it hands over, so a defect planted in the recursion reaches the state and the parameter gradients alike.
+`mutation` (one of MUTATIONS) plants one defect, for the mutation tests only.
 """
 from __future__ import annotations
-
-import math
 
 import numpy as np
 
@@ -90,45 +91,18 @@ def push_sample(cfg, n_traj, tk):
 
 
 def plant_param_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next, substeps, gp, galpha, mutation=None):
-    """The parameter and alpha shares of rollout_model.advance at (s, fm, status), added to gp [249] and galpha [n_alpha] in
-    place; sbar_next [40] as rollout_adjoint_model.plant_adjoint takes it.  Returns lam [20] in front of the first sub-step
-    (plant_adjoint's out[0:20])."""
-    s = np.array(s, dtype=float)
-    if status == L.STATUS_SOLVED:
-        s[L.PS_Q:L.PS_Q + 8] += fm[L.FM_DQ:L.FM_DQ + 8]
-        s[L.PS_U:L.PS_U + 4] = fm[L.FM_THROTTLE:L.FM_THROTTLE + 4]
-    tk = tick + int(p[L.PP_TICK0])
+    """rollout_adjoint_model.plant_adjoint at (s, fm, status) -- its arguments, its result (direct part of dL/d s_t [40],
+    fmbar [24]) -- with the parameter and alpha shares of rollout_model.advance added to gp [249] and galpha [n_alpha] in
+    place.  The shares are built from the quantities the one state recursion hands over, sub-step by sub-step."""
+    trace = {}
+    out = ram.plant_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar_next, substeps, mutation, trace)
     m = p[L.PP_MASS]
-    IB = p[L.PP_INERTIA_B:L.PP_INERTIA_B + 9].reshape(3, 3)
-    IBi = np.linalg.inv(IB)
-    A, DJ = pm.amom_of_q(s, p)
-    vthr = np.array([pm._JET.compute_v(pm._JET.standardizeThrottle_u2T(v)) for v in s[L.PS_U:L.PS_U + 4]])
-    co, (muT, sgT, _, _) = ref.JET_COEFF, ref.JET_NORM
-    h = cfg.period_mpc / substeps
+    IBi = np.linalg.inv(p[L.PP_INERTIA_B:L.PP_INERTIA_B + 9].reshape(3, 3))
+    h, Abar = trace["h"], trace["Abar"]
     gw = np.array([0.0, 0.0, -GRAV])
     n_alpha = len(alpha_track)
-    xs, x = [], s[0:20].copy()
-    for ss in range(substeps):
-        xs.append(x.copy())
-        x = pm.substep(cfg, x, p, tk, ss, substeps, A, IB, vthr, alpha_track, alpha_dt)
-    lam = np.array(sbar_next[0:20], dtype=float)
-    Abar = np.zeros((6, 4))
-    for ss in range(substeps - 1, -1, -1):
-        x = xs[ss]
-        t = (tk + ss / substeps) * cfg.period_mpc
-        alpha = pm.interp_clamped(alpha_track, t / alpha_dt)
-        dist = p[L.PP_DIST_T0] <= t < p[L.PP_DIST_T1]
-        R, dR = ram.drot(x[6:9])
-        om = IBi @ x[9:12]
-        lp, ll, lr, la = lam[0:3], lam[3:6], lam[6:9], lam[9:12]
-        hl, ha, T = x[3:6], x[9:12], x[12:16]
-        sr, cr, sp, cp = math.sin(x[6]), math.cos(x[6]), math.sin(x[7]), math.cos(x[7])
-        tp = sp / cp
-        E = np.array([[1.0, sr * tp, cr * tp], [0.0, cr, -sr], [0.0, sr / cp, cr / cp]])
-        dEr = np.array([[0.0, cr * tp, -sr * tp], [0.0, -sr, -cr], [0.0, cr / cp, -sr / cp]])
-        dEp = np.array([[0.0, sr / cp ** 2, cr / cp ** 2], [0.0, 0.0, 0.0], [0.0, sr * tp / cp, cr * tp / cp]])
-        ombar = np.cross(ll, hl) + np.cross(la, ha) + E.T @ lr
-        # ---- the parameters of this sub-step, at the cotangent behind it ----
+    for x, lam, R, _, om, ombar, alpha, dist, t in trace["steps"]:   # the parameters of a sub-step, at the cotangent behind it
+        lp, ll, la, hl = lam[0:3], lam[3:6], lam[9:12], x[3:6]
         gp[L.PP_MASS] += h * (alpha * (ll @ (R.T @ gw)) - lp @ (R @ hl) / m ** 2)        # alpha m R^T g; p' = R h_lin / m
         if mutation != "ibi_record_only":                                               # omega = I_B^-1 h_ang
             gp[L.PP_INERTIA_B:L.PP_INERTIA_B + 9] -= h * np.outer(IBi.T @ ombar, om).reshape(-1)
@@ -138,33 +112,12 @@ def plant_param_adjoint(cfg, s, p, tick, fm, status, alpha_track, alpha_dt, sbar
             gp[L.PP_DIST_TAU:L.PP_DIST_TAU + 3] += h * la
         for i, wgt in interp_samples(n_alpha, t / alpha_dt, mutation):
             galpha[i] += wgt * h * m * (ll @ (R.T @ gw))
-        # ---- the state, as rollout_adjoint_model.plant_adjoint ----
-        fw = alpha * m * gw
-        if dist:
-            fw = fw + p[L.PP_DIST_F:L.PP_DIST_F + 3]
-        g = np.zeros(20)
-        g[3:6] = R.T @ lp / m + np.cross(om, ll)
-        g[9:12] = np.cross(om, la) + IBi.T @ ombar
-        for a in range(3):
-            g[6 + a] = lp @ (dR[a] @ hl) / m + (dR[a] @ ll) @ fw
-        g[6] += lr @ (dEr @ om)
-        g[7] += lr @ (dEp @ om)
-        g[12:16] = A[0:3].T @ ll + A[3:6].T @ la
-        for j in range(4):
-            Tb, Tdb = (x[12 + j] - muT) / sgT, x[16 + j] / sgT
-            dfT, dfTd = co[1] + co[3] * Tdb + 2 * co[4] * Tb, co[2] + co[3] * Tb + 2 * co[5] * Tdb
-            dgT, dgTd = co[7] + co[9] * Tdb + 2 * co[10] * Tb, co[8] + co[9] * Tb + 2 * co[11] * Tdb
-            g[12 + j] += lam[16 + j] * (dfT + dgT * vthr[j])
-            g[16 + j] = lam[12 + j] + lam[16 + j] * (dfTd + dgTd * vthr[j])
-        Abar[0:3] += h * np.outer(ll, T)
-        Abar[3:6] += h * np.outer(la, T)
-        lam = lam + h * g
     # A_mom(q) = A_mom0 + sum_j DJ[j] (q_j - q_ref0_j), q the joints after the move
-    dq = s[L.PS_Q:L.PS_Q + 8] - p[L.PP_QREF0:L.PP_QREF0 + 8]
+    dq = trace["q"] - p[L.PP_QREF0:L.PP_QREF0 + 8]
     gp[L.PP_AMOM0:L.PP_AMOM0 + 24] += Abar.reshape(-1)
     gp[L.PP_DJ:L.PP_DJ + 192] += np.outer(dq, Abar.reshape(-1)).reshape(-1)
-    gp[L.PP_QREF0:L.PP_QREF0 + 8] -= DJ.reshape(8, 24) @ Abar.reshape(-1)
-    return lam
+    gp[L.PP_QREF0:L.PP_QREF0 + 8] -= trace["DJ"].reshape(8, 24) @ Abar.reshape(-1)
+    return out
 
 
 def record_param_adjoint(cfg, s, p, tk, first, traj, gin, wbar, gp, gpos, gvel, galpha, mutation=None, diag=None):
@@ -242,9 +195,7 @@ def backward(cfg, tape, p, traj, log_bar, state_bar, substeps=None, first=True, 
             sbar[6:9] += log_bar[t, 3:6]
             sbar[12:16] += log_bar[t, 6:10]
             sbar[L.PS_U:L.PS_U + 4] += log_bar[t, 10:14]
-        lam = plant_param_adjoint(cfg, s, p, tick_base + t, fm, status, alpha, alpha_dt, sbar, substeps, gp, galpha, mutation)
-        sbar, fmbar = ram.plant_adjoint(cfg, s, p, tick_base + t, fm, status, alpha, alpha_dt, sbar, substeps)
-        assert np.array_equal(lam, sbar[0:20])                     # the two copies of the state recursion agree
+        sbar, fmbar = plant_param_adjoint(cfg, s, p, tick_base + t, fm, status, alpha, alpha_dt, sbar, substeps, gp, galpha, mutation)
         if status == L.STATUS_SOLVED:
             adj = am.condensed_adjoint(cfg, rec, xbar0, fmbar)
             gin = arm.condensed_record_adjoint(cfg, rec, xbar0, fmbar)["grad_in"]

@@ -6,7 +6,8 @@ rollout_adjoint_model / rollout_param_adjoint_model with the tree's one smooth m
 in place of the parametric plant's A_mom0 + DJ (q - q_ref0), DJ T and constant I_B.  Mirror of the tree instantiations of
 advance_adjoint_kernel (csrc/vsmpc_rollout_adjoint.hip) behind tree_jacobian_kernel.
 
-How it is built on the two models, which are imported and not changed.  At the state between two ticks the tree plant IS a
+How it is built on the two models, which are imported and not changed (they share one state recursion,
+rollout_adjoint_model.plant_adjoint, which rollout_param_adjoint_model.plant_param_adjoint calls).  At the state between two ticks the tree plant IS a
 parametric plant whose record holds A_mom0 = A_mom(q), I_B = I_B(q) and DJ = 0 -- for everything but the dependence of
 those numbers on (q, T).  So both halves of a tick run the imported transposes on that local record, with the parametric
 branch of rollout_model selected for the length of the call; rollout_param_adjoint_model's parameter shares of A_mom0 and
@@ -118,9 +119,7 @@ def backward(cfg, tape, p, traj, log_bar, state_bar, tree, selector=None, subste
         pl = _local(p, tau)
         gl = np.zeros(NP)
         with _parametric():
-            lam = rpm.plant_param_adjoint(cfg, s, pl, tick_base + t, fm, status, alpha, alpha_dt, sbar, substeps, gl, galpha)
-            sbar, fmbar = ram.plant_adjoint(cfg, s, pl, tick_base + t, fm, status, alpha, alpha_dt, sbar, substeps)
-        assert np.array_equal(lam, sbar[0:20])
+            sbar, fmbar = rpm.plant_param_adjoint(cfg, s, pl, tick_base + t, fm, status, alpha, alpha_dt, sbar, substeps, gl, galpha)
         gp[keep] += gl[keep]
         tbar = np.zeros(TT.TT_SIZE)
         if mutation != "drop_damom_dq_plant":

@@ -5,12 +5,19 @@
 
 dump runs, on the library of `--tree` (default: the tree this file lies in) and on the inputs of THIS tree's tests/:
   the ten cases of tests/rollout_adjoint_edge_cases.py and the four loops of tests/rollout_adjoint_cases.py at both of its
-      horizons, each run plain (log, final state, next records), taped (the same) and swept backward (grad_state0, grad_gains,
-      flags);
+      horizons, each run plain (log, final state, next records), taped (the same) and swept backward twice: plain
+      (backward/: grad_state0, grad_gains, flags) and with the parameter and track gradients (backward_full/: those and
+      grad_params, grad_traj_pos, grad_traj_vel, grad_traj_alpha) -- the two instantiations of advance_adjoint_kernel;
+  the kinematic-tree plant with set_tree(tree, adjoint=True), as tests/test_gpu_rollout_tree_adjoint.py builds its rollouts:
+      the five loops of tests/rollout_tree_adjoint_cases.py at HORIZONS[0], SELECTED under its joint selector, and
+      TUNED_LOOPS at HORIZONS[1], each run plain, taped and swept plain and full -- the two instantiations of
+      advance_tree_adjoint_kernel behind tree_jacobian_kernel;
   hover, take-off and Monte-Carlo at batch 6 for 30 ticks at the paper horizon: one replay of the captured 25 ticks and five
       direct ticks;
   one kinematic-tree loop and one jet-plant loop as tests/test_gpu_rollout.py builds them, 6 ticks each.
-Every array is compared with np.array_equal, NaN patterns included."""
+Every array is compared with np.array_equal, NaN patterns included.  The tool runs on the inputs and with the cases of the
+tree it lies in whatever `--tree` names, so a dump of an earlier commit comes from this file with `--tree` on a checkout of
+that commit that has been built."""
 from __future__ import annotations
 
 import argparse
@@ -29,7 +36,7 @@ def _mod(name):
 
 
 def _swept(make, ticks, lb, sb):
-    """plain run, then taped run and sweep, each on a rollout of its own from make()"""
+    """plain run, then taped run and the two sweeps of its tape, each run on a rollout of its own from make()"""
     out = {}
     r = make()
     try:
@@ -41,6 +48,8 @@ def _swept(make, ticks, lb, sb):
         out["taped/log"], out["taped/state"], out["taped/next_records"] = r.run(ticks, tape=True), r.state(), r.next_records()
         for k, v in r.backward(lb, sb).items():
             out[f"backward/{k}"] = np.asarray(v)
+        for k, v in r.backward(lb, sb, params=True, traj=True).items():
+            out[f"backward_full/{k}"] = np.asarray(v)
     finally:
         r.close()
     return out
@@ -49,6 +58,7 @@ def _swept(make, ticks, lb, sb):
 def dump(path):
     import rollout_adjoint_cases as rc
     import rollout_adjoint_edge_cases as ec
+    import rollout_tree_adjoint_cases as tc
     L, ro, ag = _mod("layout"), _mod("rollout"), _mod("autograd")
     out = {}
 
@@ -74,6 +84,30 @@ def dump(path):
         for k, v in _swept(lambda: rollout(cfg, rows, st, pa, rc.trajectory(), runtime), rc.TICKS, lb, sb).items():
             out[f"four_loops_{'_'.join(map(str, hz))}/{k}"] = v
         print(f"four loops at {hz}: {rc.TICKS} ticks", flush=True)
+
+    def tree_rollout(hz, idx, selector):
+        cfg, (st, pa) = tc.config(L.MPCConfig, hz), tc.plants()
+        pos, vel, alpha, adt = tc.trajectory()
+        r = ro.ClosedLoopRollout(cfg, len(idx), pos, vel, alpha, adt, device=0, runtime="always" if hz == tc.HORIZONS[0] else "never",
+                                 adjoint=True)
+        try:
+            if selector is not None:
+                r.mpc.set_kinematics_options(selector)
+            r.set_tree(tc.tree(), adjoint=True)
+            r.set_tunables(configs=ag.configs_of(cfg, tc.gains(L.MPCConfig, hz)[idx]))
+            r.reset(st[idx], pa[idx])
+        except Exception:
+            r.close()
+            raise
+        return r
+
+    for name, hz, idx, selector in (("tree_loops", tc.HORIZONS[0], list(range(tc.B)), None),
+                                    ("tree_selected", tc.HORIZONS[0], [tc.SELECTED[0]], tc.SELECTED[1]),
+                                    ("tree_tuned", tc.HORIZONS[1], list(tc.TUNED_LOOPS), None)):
+        lb, sb = tc.loss_weights()
+        for k, v in _swept(lambda: tree_rollout(hz, idx, selector), tc.TICKS, lb[:, idx], sb[idx]).items():
+            out[f"{name}_{'_'.join(map(str, hz))}/{k}"] = v
+        print(f"tree plant, loops {idx} at {hz}{'' if selector is None else ' under ' + str(selector)}: {tc.TICKS} ticks", flush=True)
 
     cfg = L.paper_config()
     for workload in ("hover", "takeoff", "montecarlo"):
@@ -113,8 +147,11 @@ def dump(path):
     print("tree plant and jet plant: 6 ticks each", flush=True)
     np.savez_compressed(path, **out)
     solved = sum(int((v[:, :, 14] == L.STATUS_SOLVED).sum()) for k, v in out.items() if k.endswith("/log"))
-    print(f"{len(out)} arrays; {solved} solved ticks in the logs; gradients finite: "
-          f"{all(np.isfinite(v).all() for k, v in out.items() if '/backward/grad' in k)}")
+    # (the tree plant's loop that is never Solved carries NaN thrust references: NaN where the final state's cotangent meets them)
+    grads = {k: np.delete(v, tc.UNSOLVED, axis=0) if k.startswith("tree_loops_") else v
+             for k, v in out.items() if "/backward/grad" in k or "/backward_full/grad" in k}
+    print(f"{len(out)} arrays; {solved} solved ticks in the logs; {len(grads)} gradient arrays, finite: "
+          f"{all(np.isfinite(v).all() for v in grads.values())}")
     return 0
 
 
