@@ -599,6 +599,16 @@ int vsmpc_rollout_run(vsmpc_rollout* r, int ticks, double* log, void* stream);
  * track, angular-momentum reference = I_G W RPYDot at the attitude of the push), [n_traj][3] each, at the position
  * trajectory's rate; NULL = all zero (the shipped files).  Call before vsmpc_rollout_reset. */
 int vsmpc_rollout_set_attitude_tracks(vsmpc_rollout* r, const double* traj_rpy, const double* traj_rpy_dot);
+/* The same with flags; vsmpc_rollout_set_attitude_tracks is this call with flags 0.  Unknown bits: VSMPC_ERR_INVALID_ARG, and
+ * the rollout stays as it was.
+ *   VSMPC_ATTITUDE_ADJOINT   the rollout then accepts vsmpc_rollout_run_taped, vsmpc_rollout_backward[_device] and
+ *                            vsmpc_rollout_backward_full[_device] with an RPYDot track too (without one as before), and
+ *                            vsmpc_rollout_backward_attitude[_device] returns the gradient to both attitude tracks (below,
+ *                            "Adjoint of the rollout: attitude tracks").  The sweep then runs the attitude instantiations
+ *                            of its kernel.  The forward loop is the same with and without the flag, bit for bit.
+ * Without the flag a rollout with an RPYDot track keeps refusing the taped run and the sweep. */
+#define VSMPC_ATTITUDE_ADJOINT 1u
+int vsmpc_rollout_set_attitude_tracks_ex(vsmpc_rollout* r, const double* traj_rpy, const double* traj_rpy_dot, unsigned flags);
 /* Kinematic-tree plant: with a tree set, the plant's joint vectoring IS the kinematics the MPC linearises -- every tick the
  * batched kinematics provider (vsmpc_provider_batch's device code) is evaluated on the plant's own joint state, in the body
  * frame, and A_mom,body(q), the locked inertia I_B(q) and Lambda_lin,B / Lambda_ang,B (through vsmpc_kinematics_batch's
@@ -645,8 +655,10 @@ int vsmpc_rollout_get_records(vsmpc_rollout* r, double* records);
  * returns VSMPC_ERR_ALLOC and leaves the rollout runnable, without a tape.  A later vsmpc_rollout_reset, _set_tree,
  * _set_tunables, _set_attitude_tracks, _set_jet_plant or untaped vsmpc_rollout_run invalidates the tape.
  * Supported: the parametric plant, and the kinematic-tree plant when the tree was set with VSMPC_TREE_ADJOINT
- * (vsmpc_rollout_set_tree_ex), both with the polynomial jet model.  A rollout with a tree set without that flag
- * (vsmpc_rollout_set_tree), with the jet plant option or with an RPYDot track -- alone or beside such a tree -- is refused:
+ * (vsmpc_rollout_set_tree_ex), both with the polynomial jet model, with or without an RPY track; with an RPYDot track when
+ * the attitude tracks were set with VSMPC_ATTITUDE_ADJOINT (vsmpc_rollout_set_attitude_tracks_ex).  A rollout with a tree set
+ * without VSMPC_TREE_ADJOINT (vsmpc_rollout_set_tree), with the jet plant option, or with an RPYDot track set without
+ * VSMPC_ATTITUDE_ADJOINT (vsmpc_rollout_set_attitude_tracks) -- alone or beside each other -- is refused:
  * VSMPC_ERR_UNSUPPORTED_CONFIG, and vsmpc_strerror names the option.
  * On the tree plant the sweep sees the tree through tau = terms(q, T) of vsmpc_tree_jacobian_batch at the state between two
  * ticks: one launch of tree_jacobian_kernel per launch of advance_adjoint_kernel gives tau and d tau / d(q | T), and the tree
@@ -712,7 +724,9 @@ int vsmpc_rollout_backward_device(vsmpc_rollout* r, const double* d_log_bar, con
  * nothing through its solve, and still through its plant half and the window.  The first call that asks for either output
  * allocates batch x (VSMPC_PLANT_PARAMS + 6 n_traj + n_alpha) doubles, kept until vsmpc_rollout_destroy; a failure returns
  * VSMPC_ERR_ALLOC and leaves the rollout and its tape usable.  Refusals as vsmpc_rollout_backward's; a rollout with a tree set
- * without VSMPC_TREE_ADJOINT, the jet plant option or an RPYDot track is refused by name (VSMPC_ERR_UNSUPPORTED_CONFIG).
+ * without VSMPC_TREE_ADJOINT, with the jet plant option, or with an RPYDot track set without VSMPC_ATTITUDE_ADJOINT is refused
+ * by name (VSMPC_ERR_UNSUPPORTED_CONFIG).  With VSMPC_ATTITUDE_ADJOINT the rollout is accepted with or without an RPYDot
+ * track; grad_params[INERTIA_B] and grad_state0 then hold the shares of the window columns' angular-momentum reference too.
  */
 int vsmpc_rollout_backward_full(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0,
                                 double* grad_cfg, double* grad_params, double* grad_traj, int* flags, void* stream);
@@ -720,6 +734,34 @@ int vsmpc_rollout_backward_full_device(vsmpc_rollout* r, const double* d_log_bar
                                        double* d_grad_cfg, double* d_grad_params, double* d_grad_traj, int* d_flags, void* stream);
 /* 6 n_traj + n_alpha: doubles in one row of grad_traj */
 int vsmpc_rollout_traj_grad_size(const vsmpc_rollout* r);
+
+/*
+ * Adjoint of the rollout: attitude tracks (the section of that name; executable model:
+ * tests/rollout_attitude_adjoint_model.py).  On a rollout whose attitude tracks were set with VSMPC_ATTITUDE_ADJOINT the sweep
+ * also pulls back rows 9..11 of every window column, the angular-momentum reference R I_B R^T W(roll, pitch) RPYDot[idx]
+ * frozen with the attitude and the locked inertia of the tick that pushed it (I_B: the parameter block, or the tree's I_B(q)):
+ * to rpy through R and W, to I_B -- grad_params[INERTIA_B] on the parametric plant, through d tau / dq to the joints on the
+ * tree plant -- and to the RPYDot sample; rows 6..8, RPYINIT + RPY[idx], go to the RPY sample.  A release tick does this for
+ * the column it pushed, the first tick after a reset for every column of the fill.
+ *   grad_att[batch][6 n_traj]   dL/d(traj_rpy [n_traj][3] | traj_rpy_dot [n_traj][3]), in that order
+ *                               (vsmpc_rollout_att_grad_size doubles), one row per loop, the caller sums.  A sample that no
+ *                               window column of the run holds is +0.0.  A track that is NULL reads as zeros: its gradient is
+ *                               still returned (at a zero RPYDot track it is W^T R I_B^T R^T w, not zero).
+ * The other arguments and outputs are vsmpc_rollout_backward_full's; with grad_att == NULL the call runs what
+ * vsmpc_rollout_backward_full runs, and the outputs the three entries share are bit-identical among them on such a rollout.
+ * One lane sums a sample's columns in column order: repeated and permuted batches are bit-identical.  The first call that asks
+ * for grad_att allocates batch x 6 n_traj doubles, kept until vsmpc_rollout_destroy; a failure returns VSMPC_ERR_ALLOC and
+ * leaves the rollout and its tape usable.  Without VSMPC_ATTITUDE_ADJOINT: VSMPC_ERR_UNSUPPORTED_CONFIG, and vsmpc_strerror
+ * names the flag.  Still refused under the flag: the jet plant option, and a tree set without VSMPC_TREE_ADJOINT.
+ */
+int vsmpc_rollout_backward_attitude(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0,
+                                    double* grad_cfg, double* grad_params, double* grad_traj, double* grad_att, int* flags,
+                                    void* stream);
+int vsmpc_rollout_backward_attitude_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar,
+                                           double* d_grad_state0, double* d_grad_cfg, double* d_grad_params, double* d_grad_traj,
+                                           double* d_grad_att, int* d_flags, void* stream);
+/* 6 n_traj: doubles in one row of grad_att */
+int vsmpc_rollout_att_grad_size(const vsmpc_rollout* r);
 /* New values for the rollout's tracks, of the lengths given at vsmpc_rollout_create (host; NULL keeps a track): a loop that
  * optimises the trajectory need not re-create the rollout.  Written into the device buffers the rollout already holds, which
  * the captured tick graph reads too: it is not rebuilt.  Invalidates the tape and requires vsmpc_rollout_reset before the next

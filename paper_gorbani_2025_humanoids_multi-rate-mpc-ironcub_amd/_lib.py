@@ -57,6 +57,10 @@ SIGNATURES = {
     "vsmpc_rollout_backward_full": [vp, dp, dp, dp, dp, dp, dp, vp, vp],
     "vsmpc_rollout_backward_full_device": [vp, dp, dp, dp, dp, dp, dp, vp, vp],
     "vsmpc_rollout_traj_grad_size": [vp],
+    # r, log_bar, state_bar, grad_state0, grad_cfg, grad_params, grad_traj, grad_att, flags, stream
+    "vsmpc_rollout_backward_attitude": [vp, dp, dp, dp, dp, dp, dp, dp, vp, vp],
+    "vsmpc_rollout_backward_attitude_device": [vp, dp, dp, dp, dp, dp, dp, dp, vp, vp],
+    "vsmpc_rollout_att_grad_size": [vp],
     "vsmpc_rollout_set_trajectories": [vp, dp, dp, dp],
     "vsmpc_alloc_host": ([ctypes.c_size_t], vp),
     "vsmpc_free_host": ([vp], None),
@@ -67,6 +71,7 @@ SIGNATURES = {
     # h, tree, q, thrust, batch, terms, jac (, stream)
     "vsmpc_tree_jacobian_batch": [vp, vp, dp, dp, c_int, dp, dp], "vsmpc_tree_jacobian_batch_device": [vp, vp, dp, dp, c_int, dp, dp, vp],
     "vsmpc_rollout_set_attitude_tracks": [vp, dp, dp],
+    "vsmpc_rollout_set_attitude_tracks_ex": [vp, dp, dp, ctypes.c_uint],
     "vsmpc_rollout_set_tree": [vp, vp],
     "vsmpc_rollout_set_tree_ex": [vp, vp, ctypes.c_uint],
     "vsmpc_tick": [vp, dp, dp, c_int, dp, dp, vp, vp, vp],

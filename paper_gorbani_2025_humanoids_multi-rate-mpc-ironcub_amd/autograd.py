@@ -26,6 +26,11 @@ and so are its plant parameters and its reference tracks ("Adjoint of
     log, final_state = rollout(ro, state0, gains, params.requires_grad_(), ticks, traj=(pos, vel, alpha))
     loss(log, final_state).backward()                            # params.grad [B, PLANT_PARAMS]; pos.grad, vel.grad, alpha.grad
 
+and the attitude tracks of the reference ("Adjoint of the rollout: attitude tracks"):
+
+    log, final_state = rollout(ro, state0, gains, params, ticks, att=(rpy, rpy_dot))
+    loss(log, final_state).backward()                            # rpy.grad, rpy_dot.grad [n_traj, 3]
+
 All numerics run in libvsmpc.so (HIP); there is no CPU path.
 """
 from __future__ import annotations
@@ -132,22 +137,26 @@ NS_LIVE = 40   # entries of the plant state the parametric plant uses (the jet-p
 
 
 class RolloutFunction(torch.autograd.Function):
-    """forward(ro, state0, gains, params, ticks, info, traj_pos, traj_vel, traj_alpha) -> (log [ticks, B, 14], final_state [B, 40])
+    """forward(ro, state0, gains, params, ticks, info, traj_pos, traj_vel, traj_alpha, traj_rpy, traj_rpy_dot, att)
+    -> (log [ticks, B, 14], final_state [B, 40])
 
     Forward: the rollout `ro` (a ClosedLoopRollout created with adjoint=True) is reset to `state0` [B, 40] (CUDA or CPU,
     float64; the jet-plant slots of the plant state are zero) with the plant parameters `params` [B, PLANT_PARAMS] (numpy or
     tensor) and, when `gains` [B, L.GRAD_SIZE] is given, one row of tunables per loop; then `ticks` taped ticks run.  The three
     tracks (tensors of the rollout's own shapes, or None: the rollout's tracks as they are) are written into the rollout with
-    set_trajectories first.  reset, set_tunables, set_trajectories and the log go through the HOST, as ClosedLoopRollout's own
-    methods do.
+    set_trajectories first; with `att` the two attitude tracks ([n_traj, 3] tensors, or None: all zero) are written with
+    set_attitude_tracks(.., adjoint=True), without it the rollout's attitude tracks stay as they are.  reset, set_tunables,
+    set_trajectories, set_attitude_tracks and the log go through the HOST, as ClosedLoopRollout's own methods do.
     Backward: ONE sweep with the incoming cotangents of the log columns 0..13 and of the final state:
-    vsmpc_rollout_backward_device, or vsmpc_rollout_backward_full_device when `params` or a track requires grad.  `params` gets
+    vsmpc_rollout_backward_device, vsmpc_rollout_backward_full_device when `params` or a track requires grad, or
+    vsmpc_rollout_backward_attitude_device when an attitude track does.  `params` gets
     its row per loop (structural columns zero); a track, shared by all loops, gets the sum of the loops' rows (torch.sum over
     the batch: a reduction whose order the shape fixes).  `info` (a dict, or None) receives "flags" (OR over the ticks of
     L.ADJ_*) as a CUDA tensor."""
 
     @staticmethod
-    def forward(ctx, ro, state0, gains, params, ticks, info, traj_pos, traj_vel, traj_alpha):
+    def forward(ctx, ro, state0, gains, params, ticks, info, traj_pos, traj_vel, traj_alpha, traj_rpy=None, traj_rpy_dot=None,
+                att=False):
         B = ro.batch
         assert tuple(state0.shape) == (B, NS_LIVE) and state0.dtype == torch.float64
         st = np.zeros((B, L.PLANT_STATE))
@@ -161,12 +170,15 @@ class RolloutFunction(torch.autograd.Function):
         tracks = [None if t is None else t.detach().cpu().numpy() for t in (traj_pos, traj_vel, traj_alpha)]
         if any(t is not None for t in tracks):
             ro.set_trajectories(*tracks)
+        if att:
+            ro.set_attitude_tracks(*[None if t is None else t.detach().cpu().numpy() for t in (traj_rpy, traj_rpy_dot)], adjoint=True)
         ro.reset(st, pa)
         log = ro.run(int(ticks), tape=True)
         dev = state0.device if state0.is_cuda else torch.device("cuda", ro.mpc.device)
         ctx.ro, ctx.info, ctx.dev, ctx.ticks = ro, info, dev, int(ticks)
         ctx.out_dev = state0.device
         ctx.track_devs = [None if t is None else t.device for t in (traj_pos, traj_vel, traj_alpha)]
+        ctx.att_devs = [None if t is None else t.device for t in (traj_rpy, traj_rpy_dot)]
         ctx.params_dev = params.device if isinstance(params, torch.Tensor) else None
         return (torch.from_numpy(log[:, :, :14].copy()).to(state0.device),
                 torch.from_numpy(ro.state()[:, :NS_LIVE].copy()).to(state0.device))
@@ -182,14 +194,16 @@ class RolloutFunction(torch.autograd.Function):
             sb = torch.zeros((B, L.PLANT_STATE), dtype=torch.float64, device=dev)
             sb[:, :NS_LIVE] = gfinal.to(dev)
         if lb is None and sb is None:
-            return (None,) * 9
+            return (None,) * 12
         g0 = torch.empty((B, L.PLANT_STATE), dtype=torch.float64, device=dev)
         gg = torch.empty((B, L.GRAD_SIZE), dtype=torch.float64, device=dev)
         flags = torch.empty(B, dtype=torch.int32, device=dev)
         want_p, want_t = ctx.needs_input_grad[3], any(ctx.needs_input_grad[6:9])
         gp = torch.empty((B, L.PLANT_PARAMS), dtype=torch.float64, device=dev) if want_p else None
         gt = torch.empty((B, ro.traj_grad_size), dtype=torch.float64, device=dev) if want_t else None
-        ro.backward_device(lb, sb, g0, gg, flags, d_grad_params=gp, d_grad_traj=gt)
+        want_a = any(ctx.needs_input_grad[9:11])
+        ga = torch.empty((B, ro.att_grad_size), dtype=torch.float64, device=dev) if want_a else None
+        ro.backward_device(lb, sb, g0, gg, flags, d_grad_params=gp, d_grad_traj=gt, d_grad_att=ga)
         if ctx.info is not None:
             ctx.info["flags"] = flags
         tracks = [None, None, None]
@@ -198,18 +212,30 @@ class RolloutFunction(torch.autograd.Function):
             for k, (off, n, shape) in enumerate(L.traj_grad_blocks(ro.n_traj, ro.n_alpha).values()):
                 if ctx.needs_input_grad[6 + k]:
                     tracks[k] = total[off:off + n].reshape(shape).to(ctx.track_devs[k])
+        atts = [None, None]
+        if want_a:
+            total = ga.sum(dim=0)
+            for k, (off, n, shape) in enumerate(L.att_grad_blocks(ro.n_traj).values()):
+                if ctx.needs_input_grad[9 + k]:
+                    atts[k] = total[off:off + n].reshape(shape).to(ctx.att_devs[k])
         return (None, g0[:, :NS_LIVE].to(ctx.out_dev) if ctx.needs_input_grad[1] else None,
                 gg.to(ctx.out_dev) if ctx.needs_input_grad[2] else None, gp.to(ctx.params_dev) if want_p else None, None, None,
-                tracks[0], tracks[1], tracks[2])
+                tracks[0], tracks[1], tracks[2], atts[0], atts[1], None)
 
 
-def rollout(ro, state0, gains, params, ticks: int, info: dict | None = None, traj=None):
+def rollout(ro, state0, gains, params, ticks: int, info: dict | None = None, traj=None, att=None):
     """(log [ticks, B, 14], final_state [B, 40]) of `ticks` closed-loop ticks from `state0`, differentiable with respect to
     `state0` and `gains`, to `params` when it is a tensor that requires grad ([B, PLANT_PARAMS]), and to the tracks when
     traj = (pos [n_traj, 3], vel [n_traj, 3], alpha [n_alpha]) is given as tensors that require grad (any of the three may be
     None: that track of the rollout stays as it is) (RolloutFunction).
     Plants: the parametric plant, and the kinematic-tree plant when the rollout's tree was set with set_tree(tree, adjoint=True)
     -- `params` then gets +0.0 in the blocks that plant does not read (INERTIA_B, AMOM0, DJ); the tree's own geometry is not
-    differentiated.  The jet plant option, an RPYDot track and a tree set without adjoint=True are refused by the taped run."""
+    differentiated.
+    att = (rpy [n_traj, 3], rpy_dot [n_traj, 3]), tensors, either may be None (that track is all zero): the attitude tracks of
+    the reference, written with set_attitude_tracks(.., adjoint=True) and differentiable where they require grad.  Without
+    `att` the rollout's attitude tracks stay as they are.
+    The jet plant option, a tree set without adjoint=True and an RPYDot track set without adjoint=True are refused by the
+    taped run."""
     pos, vel, alpha = (None, None, None) if traj is None else traj
-    return RolloutFunction.apply(ro, state0, gains, params, ticks, info, pos, vel, alpha)
+    rpy, rpy_dot = (None, None) if att is None else att
+    return RolloutFunction.apply(ro, state0, gains, params, ticks, info, pos, vel, alpha, rpy, rpy_dot, att is not None)

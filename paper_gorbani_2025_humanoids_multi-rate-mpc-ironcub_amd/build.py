@@ -13,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libvsmpc.so")
 SOLVE = "vsmpc_kernels.hip"     # the per-horizon unit: production / diagnostic / per-instance-tunables instantiations
-SOURCES = [SOLVE, "vsmpc_dispatch.hip", "vsmpc_rollout.hip", "vsmpc_rollout_adjoint.hip", "vsmpc_rollout_tree_adjoint.hip", "vsmpc_capi.hip", "vsmpc_capi_solve.hip", "vsmpc_capi_debug.hip",
+SOURCES = [SOLVE, "vsmpc_dispatch.hip", "vsmpc_rollout.hip", "vsmpc_rollout_adjoint.hip", "vsmpc_rollout_tree_adjoint.hip",
+           "vsmpc_rollout_attitude_adjoint.hip", "vsmpc_rollout_attitude_tree_adjoint.hip", "vsmpc_capi.hip", "vsmpc_capi_solve.hip", "vsmpc_capi_debug.hip",
            "vsmpc_capi_rollout.hip", "vsmpc_jet.hip", "vsmpc_provider.hip", "vsmpc_tree_jacobian.hip", "vsmpc_runtime.hip", "vsmpc_certify.hip"]
 HEADERS = ["vsmpc_device.hpp", "vsmpc_launch.hpp", "vsmpc_host.hpp", "vsmpc_p0.hpp", "vsmpc_smem.hpp", "vsmpc_p1_syrk.hpp", "vsmpc_p1_struct.hpp",
            "vsmpc_p3.hpp", "vsmpc_p4.hpp", "vsmpc_p5.hpp", "vsmpc_panel_asm.inc",

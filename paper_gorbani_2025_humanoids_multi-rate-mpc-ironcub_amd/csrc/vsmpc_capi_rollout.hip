@@ -128,8 +128,13 @@ int vsmpc_rollout_reset(vsmpc_rollout* r, const double* state, const double* par
 }
 
 int vsmpc_rollout_set_attitude_tracks(vsmpc_rollout* r, const double* traj_rpy, const double* traj_rpy_dot) {
-    if (r == nullptr) return invalid_arg();
+    return vsmpc_rollout_set_attitude_tracks_ex(r, traj_rpy, traj_rpy_dot, 0u);
+}
+
+int vsmpc_rollout_set_attitude_tracks_ex(vsmpc_rollout* r, const double* traj_rpy, const double* traj_rpy_dot, unsigned flags) {
+    if (r == nullptr || (flags & ~VSMPC_ATTITUDE_ADJOINT) != 0u) return invalid_arg();
     ON_DEVICE(r->h->device);
+    r->attitude_adjoint = (flags & VSMPC_ATTITUDE_ADJOINT) != 0u ? 1 : 0;
     const size_t bytes = size_t(r->rd.n_traj) * 3 * sizeof(double);
     // whatever happens below, the captured ticks and the record of the next tick refer to the old tracks: drop them first
     invalidate(r);
@@ -330,6 +335,7 @@ hipError_t grow_tape(vsmpc_rollout* r, int ticks) {
 }
 
 size_t traj_grad_size(const vsmpc_rollout* r) { return size_t(6) * size_t(r->rd.n_traj) + size_t(r->rd.n_alpha); }
+size_t att_grad_size(const vsmpc_rollout* r) { return size_t(6) * size_t(r->rd.n_traj); }
 
 // The two rows per instance of vsmpc_rollout_backward_full, on first request.  A failure leaves neither, and the tape as it was.
 hipError_t grow_full(vsmpc_rollout* r) {
@@ -341,12 +347,21 @@ hipError_t grow_full(vsmpc_rollout* r) {
     return e;
 }
 
+// The row per instance of vsmpc_rollout_backward_attitude, on first request.  A failure leaves the tape as it was.
+hipError_t grow_att(vsmpc_rollout* r) {
+    vsmpc_rollout::Tape& tp = r->tape;
+    if (tp.gatt != nullptr) return hipSuccess;
+    return tp.gatt.alloc(size_t(r->batch) * att_grad_size(r));
+}
+
 // The backward sweep over the tape, last tick to first, in stream order: tape.sbar holds dL/d(final state) on entry and
 // dL/d(state at the start of the taped run) on exit; tape.gcfg and tape.flags receive the sums over the ticks.  Launch k of
 // advance_adjoint_kernel is the record half of tick k behind the plant half of tick k - 1, with the record adjoint of tick
 // k - 1 (the `_device` body of vsmpc_adjoint_record_batch: xbar = 0, fmbar = the plant half's) between launches k and k - 1.
 // `full`: tape.gpar and tape.gtraj (grow_full) receive the sums over the ticks too, through the kernel's second instantiation.
-int enqueue_sweep(vsmpc_rollout* r, const double* d_log_bar, hipStream_t s, bool full = false) {
+// `att` (with `full`, on a rollout with VSMPC_ATTITUDE_ADJOINT): tape.gatt (grow_att) likewise; such a rollout's launches are
+// of the ATT kernels whatever the entry asked for.
+int enqueue_sweep(vsmpc_rollout* r, const double* d_log_bar, hipStream_t s, bool full = false, bool att = false) {
     vsmpc_handle* h = r->h;
     vsmpc_rollout::Tape& tp = r->tape;
     const size_t B = size_t(r->batch);
@@ -360,6 +375,11 @@ int enqueue_sweep(vsmpc_rollout* r, const double* d_log_bar, hipStream_t s, bool
         HIP_TRY(hipMemsetAsync(tp.gtraj, 0, B * traj_grad_size(r) * sizeof(double), s));
         a.gpar = tp.gpar;
         a.gtraj = tp.gtraj;
+    }
+    a.attitude = r->attitude_adjoint;
+    if (att) {
+        HIP_TRY(hipMemsetAsync(tp.gatt, 0, B * att_grad_size(r) * sizeof(double), s));
+        a.gatt = tp.gatt;
     }
     a.batch = r->batch;
     a.substeps = r->substeps;
@@ -409,7 +429,7 @@ int run(vsmpc_rollout* r, int ticks, double* log, void* stream, bool taped) {
         if (r->use_tree && !r->tree_adjoint)
             return unsupported("vsmpc_rollout_run_taped: no adjoint of the kinematic-tree plant (vsmpc_rollout_set_tree)");
         if (r->rd.jet_nn) return unsupported("vsmpc_rollout_run_taped: no adjoint of the jet plant option (vsmpc_rollout_set_jet_plant)");
-        if (r->rd.traj_rpyd != nullptr)
+        if (r->rd.traj_rpyd != nullptr && !r->attitude_adjoint)
             return unsupported("vsmpc_rollout_run_taped: no adjoint of an RPYDot track (vsmpc_rollout_set_attitude_tracks)");
         r->tape.ticks = 0;
     }
@@ -461,24 +481,34 @@ int full_refusal(const vsmpc_rollout* r) {
     if (r->use_tree && !r->tree_adjoint)
         return unsupported("vsmpc_rollout_backward_full: no adjoint of the kinematic-tree plant (vsmpc_rollout_set_tree)");
     if (r->rd.jet_nn) return unsupported("vsmpc_rollout_backward_full: no adjoint of the jet plant option (vsmpc_rollout_set_jet_plant)");
-    if (r->rd.traj_rpyd != nullptr)
+    if (r->rd.traj_rpyd != nullptr && !r->attitude_adjoint)
         return unsupported("vsmpc_rollout_backward_full: no adjoint of an RPYDot track (vsmpc_rollout_set_attitude_tracks)");
     return VSMPC_OK;
 }
 
-// Both device entries (gpar == gtraj == nullptr: the plain one) and both host entries, `what` the entry's name.
+// what the `_attitude` entries refuse in front of that
+int attitude_refusal(const vsmpc_rollout* r, const char* why) {
+    if (r == nullptr) return invalid_arg();
+    if (!r->attitude_adjoint) return unsupported(why);
+    return full_refusal(r);
+}
+
+// The device entries (gpar == gtraj == gatt == nullptr: the plain one) and the host entries, `what` the entry's name.  gatt rides
+// the kernel's second instantiation: asking for it alone runs the `_full` sweep.
 int backward_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar, double* d_grad_state0, double* d_grad_cfg,
-                    double* d_gpar, double* d_gtraj, int* d_flags, void* stream, const char* what) {
+                    double* d_gpar, double* d_gtraj, double* d_gatt, int* d_flags, void* stream, const char* what) {
     if (const int rc = backward_refusal(r, d_log_bar, d_state_bar); rc != VSMPC_OK) return rc;
     ON_DEVICE(r->h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);   // the caller's, the null stream too: its tensors are ordered on it
     const size_t B = size_t(r->batch);
     vsmpc_rollout::Tape& tp = r->tape;
-    const bool full = d_gpar != nullptr || d_gtraj != nullptr;
+    const bool att = d_gatt != nullptr, full = d_gpar != nullptr || d_gtraj != nullptr || att;
     if (full)
         if (const hipError_t e = grow_full(r); e != hipSuccess) return alloc_fail(e, what);
+    if (att)
+        if (const hipError_t e = grow_att(r); e != hipSuccess) return alloc_fail(e, what);
     HIP_TRY(seed_sbar(r, d_state_bar, hipMemcpyDeviceToDevice, s));
-    if (const int rc = enqueue_sweep(r, d_log_bar, s, full); rc != VSMPC_OK) return rc;
+    if (const int rc = enqueue_sweep(r, d_log_bar, s, full, att); rc != VSMPC_OK) return rc;
     auto out = [&](void* dst, const void* src, size_t bytes) {
         return dst != nullptr ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
     };
@@ -487,28 +517,32 @@ int backward_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_s
     HIP_TRY(out(d_flags, tp.flags, B * sizeof(int)));
     HIP_TRY(out(d_gpar, tp.gpar, B * VSMPC_PLANT_PARAMS * sizeof(double)));
     HIP_TRY(out(d_gtraj, tp.gtraj, B * traj_grad_size(r) * sizeof(double)));
+    HIP_TRY(out(d_gatt, tp.gatt, B * att_grad_size(r) * sizeof(double)));
     return VSMPC_OK;
 }
 
 int backward_host(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0, double* grad_cfg,
-                  double* gpar, double* gtraj, int* flags, void* stream, const char* what) {
+                  double* gpar, double* gtraj, double* gatt, int* flags, void* stream, const char* what) {
     if (const int rc = backward_refusal(r, log_bar, state_bar); rc != VSMPC_OK) return rc;
     ON_DEVICE(r->h->device);
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->own_stream.h;
     const size_t B = size_t(r->batch);
     vsmpc_rollout::Tape& tp = r->tape;
-    const bool full = gpar != nullptr || gtraj != nullptr;
+    const bool att = gatt != nullptr, full = gpar != nullptr || gtraj != nullptr || att;
     if (full)
         if (const hipError_t e = grow_full(r); e != hipSuccess) return alloc_fail(e, what);
+    if (att)
+        if (const hipError_t e = grow_att(r); e != hipSuccess) return alloc_fail(e, what);
     HIP_TRY(upload_rows(tp.log_bar.get(), log_bar, 0, size_t(tp.ticks), B * VSMPC_ROLLOUT_LOG, s));
     HIP_TRY(seed_sbar(r, state_bar, hipMemcpyHostToDevice, s));
-    int rc = enqueue_sweep(r, log_bar ? tp.log_bar.get() : nullptr, s, full);
+    int rc = enqueue_sweep(r, log_bar ? tp.log_bar.get() : nullptr, s, full, att);
     hipError_t e = hipSuccess;
     if (rc == VSMPC_OK) e = download_rows(grad_state0, tp.sbar.get(), 0, B, VSMPC_PLANT_STATE, s);
     if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(grad_cfg, tp.gcfg.get(), 0, B, VSMPC_GRAD_SIZE, s);
     if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(flags, tp.flags.get(), 0, B, 1, s);
     if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(gpar, tp.gpar.get(), 0, B, VSMPC_PLANT_PARAMS, s);
     if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(gtraj, tp.gtraj.get(), 0, B, traj_grad_size(r), s);
+    if (rc == VSMPC_OK && e == hipSuccess) e = download_rows(gatt, tp.gatt.get(), 0, B, att_grad_size(r), s);
     const hipError_t e2 = hipStreamSynchronize(s);   // nothing returns while copies from the caller's buffers are queued
     if (rc != VSMPC_OK) return rc;
     if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, what);
@@ -525,28 +559,50 @@ int vsmpc_rollout_run_taped(vsmpc_rollout* r, int ticks, double* log, void* stre
 
 int vsmpc_rollout_backward_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar, double* d_grad_state0,
                                   double* d_grad_cfg, int* d_flags, void* stream) {
-    return backward_device(r, d_log_bar, d_state_bar, d_grad_state0, d_grad_cfg, nullptr, nullptr, d_flags, stream,
+    return backward_device(r, d_log_bar, d_state_bar, d_grad_state0, d_grad_cfg, nullptr, nullptr, nullptr, d_flags, stream,
                            "vsmpc_rollout_backward_device");
 }
 
 int vsmpc_rollout_backward(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0,
                            double* grad_cfg, int* flags, void* stream) {
-    return backward_host(r, log_bar, state_bar, grad_state0, grad_cfg, nullptr, nullptr, flags, stream, "vsmpc_rollout_backward");
+    return backward_host(r, log_bar, state_bar, grad_state0, grad_cfg, nullptr, nullptr, nullptr, flags, stream, "vsmpc_rollout_backward");
 }
 
 int vsmpc_rollout_backward_full_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar, double* d_grad_state0,
                                        double* d_grad_cfg, double* d_grad_params, double* d_grad_traj, int* d_flags, void* stream) {
     if (const int rc = full_refusal(r); rc != VSMPC_OK) return rc;
-    return backward_device(r, d_log_bar, d_state_bar, d_grad_state0, d_grad_cfg, d_grad_params, d_grad_traj, d_flags, stream,
+    return backward_device(r, d_log_bar, d_state_bar, d_grad_state0, d_grad_cfg, d_grad_params, d_grad_traj, nullptr, d_flags, stream,
                            "vsmpc_rollout_backward_full_device");
 }
 
 int vsmpc_rollout_backward_full(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0,
                                 double* grad_cfg, double* grad_params, double* grad_traj, int* flags, void* stream) {
     if (const int rc = full_refusal(r); rc != VSMPC_OK) return rc;
-    return backward_host(r, log_bar, state_bar, grad_state0, grad_cfg, grad_params, grad_traj, flags, stream,
+    return backward_host(r, log_bar, state_bar, grad_state0, grad_cfg, grad_params, grad_traj, nullptr, flags, stream,
                          "vsmpc_rollout_backward_full");
 }
+
+int vsmpc_rollout_backward_attitude_device(vsmpc_rollout* r, const double* d_log_bar, const double* d_state_bar,
+                                           double* d_grad_state0, double* d_grad_cfg, double* d_grad_params, double* d_grad_traj,
+                                           double* d_grad_att, int* d_flags, void* stream) {
+    if (const int rc = attitude_refusal(r, "vsmpc_rollout_backward_attitude_device needs attitude tracks set with "
+                                           "VSMPC_ATTITUDE_ADJOINT (vsmpc_rollout_set_attitude_tracks_ex)"); rc != VSMPC_OK)
+        return rc;
+    return backward_device(r, d_log_bar, d_state_bar, d_grad_state0, d_grad_cfg, d_grad_params, d_grad_traj, d_grad_att, d_flags,
+                           stream, "vsmpc_rollout_backward_attitude_device");
+}
+
+int vsmpc_rollout_backward_attitude(vsmpc_rollout* r, const double* log_bar, const double* state_bar, double* grad_state0,
+                                    double* grad_cfg, double* grad_params, double* grad_traj, double* grad_att, int* flags,
+                                    void* stream) {
+    if (const int rc = attitude_refusal(r, "vsmpc_rollout_backward_attitude needs attitude tracks set with VSMPC_ATTITUDE_ADJOINT "
+                                           "(vsmpc_rollout_set_attitude_tracks_ex)"); rc != VSMPC_OK)
+        return rc;
+    return backward_host(r, log_bar, state_bar, grad_state0, grad_cfg, grad_params, grad_traj, grad_att, flags, stream,
+                         "vsmpc_rollout_backward_attitude");
+}
+
+int vsmpc_rollout_att_grad_size(const vsmpc_rollout* r) { return r == nullptr ? invalid_arg() : int(att_grad_size(r)); }
 
 int vsmpc_rollout_traj_grad_size(const vsmpc_rollout* r) { return r == nullptr ? invalid_arg() : int(traj_grad_size(r)); }
 

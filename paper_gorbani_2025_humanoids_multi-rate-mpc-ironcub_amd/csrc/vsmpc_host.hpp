@@ -157,6 +157,7 @@ struct vsmpc_rollout {
     vsmpc::DevBuf<int> d_tick;
     vsmpc::DevBuf<double> d_tpos, d_tvel, d_talpha;
     vsmpc::DevBuf<double> d_trpy, d_trpyd;   // vsmpc_rollout_set_attitude_tracks (or empty)
+    int attitude_adjoint;     // the tracks were set with VSMPC_ATTITUDE_ADJOINT: the sweep runs the ATT kernels
     vsmpc::DevBuf<double> d_log;
     int log_ticks;
     vsmpc::DevBuf<double> d_tstate;  // per-instance tick state: reference window FIFO, RPY unwrap (see vsmpc_rollout.hip)
@@ -197,6 +198,9 @@ struct vsmpc_rollout {
         // vsmpc_rollout_backward_full: dL/d(plant parameters) [batch][VSMPC_PLANT_PARAMS] and dL/d(tracks) [batch][6 n_traj +
         // n_alpha], allocated by the first call that asks for either (gtraj last: its presence says that both are there)
         vsmpc::DevBuf<double> gpar, gtraj;
+        // vsmpc_rollout_backward_attitude: dL/d(traj_rpy | traj_rpy_dot) [batch][6 n_traj], allocated by the first call that
+        // asks for it
+        vsmpc::DevBuf<double> gatt;
     } tape;
 };
 

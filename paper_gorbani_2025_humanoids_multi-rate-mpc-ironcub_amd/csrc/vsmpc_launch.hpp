@@ -257,9 +257,18 @@ struct RolloutAdj {
     // tick_plant) and its Jacobian [VSMPC_TT_SIZE][VSMPC_TT_NDIR] (launch_tree_jacobian on that state)
     const double* tree_terms;
     const double* tree_jac;
+    // attitude tracks (vsmpc_rollout_set_attitude_tracks_ex with VSMPC_ATTITUDE_ADJOINT): the launch runs the ATT kernels, which
+    // also pull back rows 9..11 of the window columns (rd.traj_rpyd, nullptr: zeros); gatt, with gpar and gtraj only, or nullptr:
+    // dL/d(traj_rpy | traj_rpy_dot) [6 n_traj], one row per instance, accumulated over the ticks
+    int attitude;
+    double* gatt;
 };
 hipError_t launch_advance_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream);
 // the tree instantiations (vsmpc_rollout_tree_adjoint.hip): what launch_advance_adjoint launches when a.tree_terms is given
 hipError_t launch_advance_tree_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream);
+// the ATT instantiations (vsmpc_rollout_attitude_adjoint.hip, vsmpc_rollout_attitude_tree_adjoint.hip): what
+// launch_advance_adjoint launches when a.attitude is set, the second when a.tree_terms is given too
+hipError_t launch_advance_attitude_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream);
+hipError_t launch_advance_attitude_tree_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream);
 
 }  // namespace vsmpc

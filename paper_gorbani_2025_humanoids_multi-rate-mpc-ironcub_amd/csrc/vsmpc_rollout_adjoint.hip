@@ -23,7 +23,12 @@
 //                   (p' = R h_lin / m, alpha m R^T g), I_B^-1 through omega, the push where push_active holds, alpha of the
 //                   sub-step to its two samples; behind the sub-steps A_mom0, DJ and q_ref0 from the cotangent of A_mom(q).
 //
-// Layout: the device code is csrc/vsmpc_rollout_adjoint_device.hpp -- advance_adjoint_body<PT, TREE>, a driver over one function
+//   attitude tracks (the ATT instantiations, vsmpc_rollout_set_attitude_tracks_ex with VSMPC_ATTITUDE_ADJOINT): rows 6..11 of
+//                   the window columns too, at the same two moments -- the h_ang entry R I_B R^T W(roll, pitch) RPYDot to rpy,
+//                   to I_B and to the RPYDot sample, the RPY entry to its sample (vsmpc_rollout_attitude_adjoint.hip,
+//                   vsmpc_rollout_attitude_tree_adjoint.hip: launch_advance_adjoint hands a launch with a.attitude to them).
+//
+// Layout: the device code is csrc/vsmpc_rollout_adjoint_device.hpp -- advance_adjoint_body<PT, TREE, ATT>, a driver over one function
 // per phase (stage-in; record half: set-up, pull-back to the state, to the parameters, FIFO shift, `first` fill; plant half:
 // set-up, forward sub-steps, backward sub-steps, what follows them; write-out), each with its contract above it.  This unit
 // holds the parametric plant's kernel template and the launcher; vsmpc_rollout_tree_adjoint.hip holds the tree plant's.
@@ -41,6 +46,7 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_adjoint_kernel(RolloutDev rd
 }
 
 hipError_t launch_advance_adjoint(const RolloutDev& rd, const RolloutAdj& a, hipStream_t stream) {
+    if (a.attitude) return launch_advance_attitude_adjoint(rd, a, stream);
     if (a.tree_terms != nullptr && a.tree_jac != nullptr) return launch_advance_tree_adjoint(rd, a, stream);
     if (a.gpar != nullptr && a.gtraj != nullptr)
         hipLaunchKernelGGL(advance_adjoint_kernel<true>, dim3(a.batch), dim3(RO_BLOCK), 0, stream, rd, a);

@@ -1,8 +1,9 @@
-// Device code of the rollout's backward sweep: advance_adjoint_body<PT, TREE>, the body of advance_adjoint_kernel<PT>
-// (vsmpc_rollout_adjoint.hip, TREE off: the parametric plant) and of advance_tree_adjoint_kernel<PT>
-// (vsmpc_rollout_tree_adjoint.hip, TREE on: the kinematic-tree plant), as a driver over one function per phase.  Two units,
-// because a second kernel family in one code object moves the first one's code (LDS and address arithmetic are laid out per
-// module).
+// Device code of the rollout's backward sweep: advance_adjoint_body<PT, TREE, ATT>, the body of advance_adjoint_kernel<PT>
+// (vsmpc_rollout_adjoint.hip, TREE off: the parametric plant), of advance_tree_adjoint_kernel<PT>
+// (vsmpc_rollout_tree_adjoint.hip, TREE on: the kinematic-tree plant) and, with ATT on, of advance_attitude_adjoint_kernel<PT>
+// and advance_attitude_tree_adjoint_kernel<PT> (vsmpc_rollout_attitude_adjoint.hip, vsmpc_rollout_attitude_tree_adjoint.hip),
+// as a driver over one function per phase.  One unit per family, because a second kernel family in one code object moves the
+// first one's code (LDS and address arithmetic are laid out per module).
 //
 // One wavefront per instance, as advance_kernel.  Every global load is requested in front of the first barrier.
 // PT (vsmpc_rollout_backward_full) also accumulates dL/d(plant parameters) and dL/d(tracks) of the instance: the parameter row
@@ -13,6 +14,11 @@
 // J = d tau / d(q | T) (a.tree_jac): Lambda's to the thrusts in front of the sub-steps, everything to the joints, where the
 // move shares it when the tick was Solved.  The parameter blocks the tree plant does not read get nothing.  Without TREE
 // nothing of that is compiled in.
+// ATT (vsmpc_rollout_set_attitude_tracks_ex with VSMPC_ATTITUDE_ADJOINT): rows 9..11 of a window column, the angular-momentum
+// reference R I_B R^T W(roll, pitch) RPYDot[idx] frozen at the tick that pushed it, are pulled back too (att_column) -- to rpy
+// through R and W, to I_B (PT: the parameter block; TREE: tau_bar's I_B rows and on through J to the joints) and, PT, to the
+// RPYDot sample; rows 6..8 go to the RPY sample.  The attitude samples ride the slots of slot_sample, six more doubles each.
+// Without ATT nothing of that is compiled in.
 //
 // The phases share the instance's LDS (AdjLds, which each of them forms itself with adj_lds) and, in registers, what the
 // stage-in parked (AdjTracks, AdjPlantRows).  Above each phase: what it reads, what it leaves, the barriers it contains.
@@ -101,6 +107,7 @@ constexpr int ADJ_KT = (6 * (MAX_STAGES + 1) + RO_BLOCK - 1) / RO_BLOCK;
 struct AdjTracks {
     int tkr = -1, tkp = -1, ai0 = 0;
     double tpre[ADJ_KT] = {}, apre = 0.0;
+    double qpre[ADJ_KT] = {};   // ATT: the running sums of grad_att's samples, the slot entries as tpre
 };
 // The one walk over what this lane owns of grad_traj: on_slot(k, ws, c, idx) for component c of slot ws, the lane's k-th slot
 // entry, where slot ws owns its sample idx; on_alpha(idx) where alpha element `lane` owns its sample idx
@@ -141,10 +148,14 @@ struct AdjLds {
     double *s, *p, *f, *sb, *gi, *wb, *R, *dR, *IBi, *Aq, *Ab, *vb, *vthr, *alpha_s, *xs, *lam, *sc, *omv, *omb;
     double *gp, *tc, *ac;     // PT: cotangent of the parameters; of the window slots' trajectory samples (6 per slot); of the alpha elements
     double *tt, *tj, *tib;    // TREE: tau, J, and the sub-steps' cotangent of I_B
+    // ATT: cotangent of the window slots' attitude samples (rpy | rpy_dot, 6 per slot); per slot what att_column leaves for the
+    // reductions over the columns: the shares of roll, pitch, yaw | ybar | v
+    double *atc, *acs;
 };
+constexpr int ATT_COL = 9;   // doubles per slot of acs
 // Every phase forms the carve-up itself: the arrays are one set per instantiation, their addresses constants wherever they
 // are used; an array of an option that the instantiation does not have is never named and takes no LDS.
-template <bool PT, bool TREE>
+template <bool PT, bool TREE, bool ATT>
 VS_DEV AdjLds adj_lds() {
     __shared__ double s[VSMPC_PLANT_STATE], p[VSMPC_PLANT_PARAMS + 1], f[VSMPC_FM_SIZE], sb[VSMPC_PLANT_STATE];
     __shared__ double gi[VSMPC_IN_XREF + 12 * MAX_STAGES], wb[12 * MAX_STAGES];
@@ -152,7 +163,58 @@ VS_DEV AdjLds adj_lds() {
     __shared__ double xs[16 * 20], lam[20], sc[6], omv[3], omb[3];
     __shared__ double gp[PT ? VSMPC_PLANT_PARAMS + 1 : 1], tc[PT ? 6 * (MAX_STAGES + 1) : 1], ac[PT ? ALPHA_ELEMS + 1 : 1];
     __shared__ double tt[TREE ? VSMPC_TT_SIZE + 1 : 1], tj[TREE ? VSMPC_TT_SIZE * VSMPC_TT_NDIR : 1], tib[TREE ? 9 : 1];
-    return {s, p, f, sb, gi, wb, R, dR, IBi, Aq, Ab, vb, vthr, alpha_s, xs, lam, sc, omv, omb, gp, tc, ac, tt, tj, tib};
+    __shared__ double atc[ATT && PT ? 6 * (MAX_STAGES + 1) : 1], acs[ATT ? ATT_COL * (MAX_STAGES + 1) : 1];
+    return {s, p, f, sb, gi, wb, R, dR, IBi, Aq, Ab, vb, vthr, alpha_s, xs, lam, sc, omv, omb, gp, tc, ac, tt, tj, tib, atc, acs};
+}
+
+// ---- ATT: the h_ang entry of a window column ----------------------------------------------------------------------------------
+// Rows 9..11 of a column built from sample idx at the taped state: d = RPYDot[idx] (zeros without a track), u = W(roll, pitch) d,
+// v = R^T u, y = I_B v, h = R y (assemble_record's column_entry).  With their cotangent w: ybar = R^T w, vbar = I_B^T ybar,
+// ubar = R vbar; dbar = W^T ubar; I_B_bar = ybar v^T; rpy_a gets <dR_a, w y^T + u vbar^T>, roll and pitch ubar . (dW d) besides.
+// Reads R, dR, sc (sin, cos of roll | pitch, as adj_record_setup leaves them) and I_B.  Leaves in acs + ATT_COL k the three
+// shares of rpy | ybar | v; PT: in atc + 6 k the column's attitude samples, rows 6..8 of cw | dbar.  One lane, no barrier.
+template <bool PT, bool TREE>
+VS_DEV void att_column(const AdjLds& L, const double* __restrict__ cw, const double* __restrict__ traj_rpyd, int idx, int k) {
+    const double* R = L.R;
+    const double* IB;
+    if constexpr (TREE) IB = L.tt + VSMPC_TT_IB;
+    else IB = L.p + VSMPC_PP_INERTIA_B;
+    const double sr = L.sc[0], cr = L.sc[1], sp = L.sc[2], cp = L.sc[3];
+    const double* w = cw + 9;
+    double d[3] = {0.0, 0.0, 0.0};
+    if (traj_rpyd != nullptr) { d[0] = traj_rpyd[3 * idx]; d[1] = traj_rpyd[3 * idx + 1]; d[2] = traj_rpyd[3 * idx + 2]; }
+    const double u[3] = {d[0] - sp * d[2], cr * d[1] + cp * sr * d[2], -sr * d[1] + cr * cp * d[2]};
+    double v[3], y[3], yb[3], vb[3], ub[3];
+    for (int c = 0; c < 3; ++c) v[c] = R[c] * u[0] + R[3 + c] * u[1] + R[6 + c] * u[2];
+    for (int r = 0; r < 3; ++r) y[r] = rot_row(IB, v, r);
+    for (int c = 0; c < 3; ++c) yb[c] = R[c] * w[0] + R[3 + c] * w[1] + R[6 + c] * w[2];
+    for (int c = 0; c < 3; ++c) vb[c] = IB[c] * yb[0] + IB[3 + c] * yb[1] + IB[6 + c] * yb[2];
+    for (int r = 0; r < 3; ++r) ub[r] = rot_row(R, vb, r);
+    double* o = L.acs + ATT_COL * k;
+    for (int a = 0; a < 3; ++a) {
+        const double* dRa = L.dR + 9 * a;
+        double g = 0.0;
+        for (int r = 0; r < 3; ++r) g += rot_row(dRa, y, r) * w[r] + rot_row(dRa, vb, r) * u[r];
+        o[a] = g;
+    }
+    o[0] += ub[1] * (-sr * d[1] + cp * cr * d[2]) + ub[2] * (-cr * d[1] - sr * cp * d[2]);   // ubar . (dW/droll d)
+    o[1] -= (cp * ub[0] + sp * sr * ub[1] + cr * sp * ub[2]) * d[2];                           // ubar . (dW/dpitch d)
+    for (int c = 0; c < 3; ++c) { o[3 + c] = yb[c]; o[6 + c] = v[c]; }
+    if constexpr (PT) {
+        double* t = L.atc + 6 * k;
+        t[0] = cw[6]; t[1] = cw[7]; t[2] = cw[8];
+        t[3] = ub[0];
+        t[4] = cr * ub[1] - sr * ub[2];
+        t[5] = -sp * ub[0] + cp * sr * ub[1] + cr * cp * ub[2];
+    }
+}
+// cotangent of I_B[u][v] from slot k's column: (ybar v^T)[u][v]
+VS_DEV double att_ib_bar(const AdjLds& L, int k, int u, int v) { return L.acs[ATT_COL * k + 3 + u] * L.acs[ATT_COL * k + 6 + v]; }
+// TREE: acc + that cotangent, as tau_bar's I_B rows, contracted with column c of J
+VS_DEV double att_tau_bar_col(const AdjLds& L, double acc, int c, int k) {
+    for (int u = 0; u < 3; ++u)
+        for (int v = 0; v < 3; ++v) acc += L.tj[(VSMPC_TT_IB + 3 * u + v) * VSMPC_TT_NDIR + c] * att_ib_bar(L, k, u, v);
+    return acc;
 }
 
 // the plant half's rows, in registers until the record half is through with `s`
@@ -165,9 +227,9 @@ struct AdjPlantRows {
 // Reads: every global row of instance b that the launch needs.  Leaves: sb, p, wb (and gp, tt, tj) in LDS; with a record half
 // s, gi, and the tick's grad_cfg and flags accumulated; tr (PT: ticks and the running sums of the owned samples) and pr (the
 // plant half's rows) in registers.  Ends with the launch's first barrier.
-template <bool PT, bool TREE>
+template <bool PT, bool TREE, bool ATT>
 VS_DEV void adj_stage_in(const RolloutDev& rd, const RolloutAdj& a, int b, int lane, AdjTracks& tr, AdjPlantRows& pr) {
-    const AdjLds L = adj_lds<PT, TREE>();
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const bool rec = a.tick_rec >= 0, plant = a.tick_plant >= 0;
     const int nwin = 12 * rd.n_ref;
     if constexpr (PT) {
@@ -182,7 +244,11 @@ VS_DEV void adj_stage_in(const RolloutDev& rd, const RolloutAdj& a, int b, int l
             tr.ai0 = interp_lerp(rd.n_alpha, substep_time(rd, tr.tkp, 0, a.substeps) / rd.alpha_dt).i0;
         }
         for_owned_samples(rd, a, tr, lane,
-                          [&](int k, int, int c, int idx) { tr.tpre[k] = gt[traj_entry(rd, idx, c)]; },
+                          [&](int k, int, int c, int idx) {
+                              tr.tpre[k] = gt[traj_entry(rd, idx, c)];
+                              if constexpr (ATT)   // grad_att's rows are laid out as grad_traj's first two blocks
+                                  if (a.gatt != nullptr) tr.qpre[k] = a.gatt[size_t(b) * size_t(6 * rd.n_traj) + traj_entry(rd, idx, c)];
+                          },
                           [&](int idx) { tr.apre = gt[6 * rd.n_traj + idx]; });
     }
     if constexpr (TREE) {
@@ -221,14 +287,17 @@ VS_DEV double ib_bar(const AdjLds& L, int u, int v) {
 
 // Reads: s, p (tt), gi, wb.  Leaves: R, dR of the taped attitude and IBi; in wb the window's cotangent with grad_in's share
 // (XREF, and what X0[20:26] and PREF read of column 0).  Two barriers, the second behind its last write.
-template <bool PT, bool TREE>
-VS_DEV void adj_record_setup(const RolloutDev& rd, int lane) {
-    const AdjLds L = adj_lds<PT, TREE>();
+// ATT: also sc (sin, cos of the taped roll | pitch | yaw) and, on a release tick, slot n_ref of acs (atc): the column this tick
+// pushed, complete in front of the shift (att_column), behind a third barrier.
+template <bool PT, bool TREE, bool ATT>
+VS_DEV void adj_record_setup(const RolloutDev& rd, int tk, int lane) {
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const int nwin = 12 * rd.n_ref;
     if (lane == 0) {
         double sr, cr, sp, cp, sy, cy;
         sincos(L.s[VSMPC_PS_RPY], &sr, &cr); sincos(L.s[VSMPC_PS_RPY + 1], &sp, &cp); sincos(L.s[VSMPC_PS_RPY + 2], &sy, &cy);
         rot_partials({sr, cr, sp, cp, sy, cy}, L.R, L.dR);
+        if constexpr (ATT) { L.sc[0] = sr; L.sc[1] = cr; L.sc[2] = sp; L.sc[3] = cp; L.sc[4] = sy; L.sc[5] = cy; }
     } else if (lane == 1) {
         if constexpr (TREE) inv3(L.tt + VSMPC_TT_IB, L.IBi);
         else inv3(L.p + VSMPC_PP_INERTIA_B, L.IBi);
@@ -240,13 +309,18 @@ VS_DEV void adj_record_setup(const RolloutDev& rd, int lane) {
         L.wb[6 + lane] -= L.gi[VSMPC_IN_X0 + 23 + lane];
     }
     __syncthreads();
+    if constexpr (ATT)
+        if (release_tick(rd, tk)) {
+            if (lane == 0) att_column<PT, TREE>(L, L.wb + 12 * (rd.n_ref - 1), rd.traj_rpyd, window_push_sample(rd, tk), rd.n_ref);
+            __syncthreads();
+        }
 }
 
 // Reads: what adj_record_setup left, and s, p (tt, tj), gi.  Returns what the record hands to state entry `lane` (< 40), the
-// column a release tick pushed included.  No barrier, no write.
-template <bool PT, bool TREE>
+// column a release tick pushed included (ATT: its h_ang entry too, from slot n_ref of acs).  No barrier, no write.
+template <bool PT, bool TREE, bool ATT>
 VS_DEV double adj_record_to_state(const RolloutDev& rd, const RolloutAdj& a, int tk, double m, int lane) {
-    const AdjLds L = adj_lds<PT, TREE>();
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const double* gi = L.gi;
     const double* DJ = L.p + VSMPC_PP_DJ;
     double add = 0.0;
@@ -274,6 +348,7 @@ VS_DEV double adj_record_to_state(const RolloutDev& rd, const RolloutAdj& a, int
         if (release_tick(rd, tk)) {   // the column this tick pushed, at this tick's R
             const int idx = window_push_sample(rd, tk);
             add += hlin_to_rpy(dRa, L.wb + 12 * (rd.n_ref - 1) + 3, a.traj_vel + 3 * idx, m);
+            if constexpr (ATT) add += L.acs[ATT_COL * rd.n_ref + c];   // and its h_ang entry
         }
     } else if (lane >= 9 && lane < 12) {
         const int c = lane - 9;
@@ -298,6 +373,8 @@ VS_DEV double adj_record_to_state(const RolloutDev& rd, const RolloutAdj& a, int
                                                  {VSMPC_TT_LANG, gi + VSMPC_IN_LANG}});
             for (int u = 0; u < 3; ++u)
                 for (int v = 0; v < 3; ++v) add += L.tj[(VSMPC_TT_IB + 3 * u + v) * VSMPC_TT_NDIR + j] * ib_bar(L, u, v);
+            if constexpr (ATT)      // and I_B's of the pushed column's h_ang entry
+                if (release_tick(rd, tk)) add = att_tau_bar_col(L, add, j, rd.n_ref);
         } else {
             for (int l = 0; l < 24; ++l) add += DJ[24 * j + l] * gi[VSMPC_IN_AMOM + l];
         }
@@ -313,11 +390,12 @@ VS_DEV double adj_record_to_state(const RolloutDev& rd, const RolloutAdj& a, int
 
 // PT.  Reads: as adj_record_to_state.  Adds to gp the record's entries that are parameters or are built from them, at the
 // taped state, and the share of the column this tick pushed, whose cotangent is complete here, in front of the shift: its
-// position, attitude and h_lin entries; leaves that column's trajectory sample in tc[6 n_ref ..] and alpha of the tick in
-// ac[0..1].  No barrier.
-template <bool TREE>
+// position, attitude and h_lin entries (ATT, parametric plant: and what its h_ang entry hands to I_B, as adj_record_setup left
+// it in slot n_ref of acs); leaves that column's trajectory sample in tc[6 n_ref ..] and alpha of the tick in ac[0..1].  No
+// barrier.
+template <bool TREE, bool ATT>
 VS_DEV void adj_record_to_params(const RolloutDev& rd, const RolloutAdj& a, int tk, double m, int lane) {
-    const AdjLds L = adj_lds<true, TREE>();
+    const AdjLds L = adj_lds<true, TREE, ATT>();
     const double* gi = L.gi;
     const double* DJ = L.p + VSMPC_PP_DJ;
     const int nref = rd.n_ref;
@@ -335,6 +413,8 @@ VS_DEV void adj_record_to_params(const RolloutDev& rd, const RolloutAdj& a, int 
             if (rel) g += hlin_to_mass(L.R, wp + 3, vp);
         } else if (e < VSMPC_PP_AMOM0) {                 // I_G = R I_B R^T, and omega = I_B^-1 h_ang
             g = ib_bar(L, (e - VSMPC_PP_INERTIA_B) / 3, (e - VSMPC_PP_INERTIA_B) % 3);
+            if constexpr (ATT)                           // and the pushed column's h_ang entry R I_B R^T W d
+                if (rel) g += att_ib_bar(L, nref, (e - VSMPC_PP_INERTIA_B) / 3, (e - VSMPC_PP_INERTIA_B) % 3);
         } else if (e < VSMPC_PP_DJ) {
             g = gi[VSMPC_IN_AMOM + e - VSMPC_PP_AMOM0];
         } else if (e < VSMPC_PP_QREF0) {                 // A_mom(q), and Lambda column j = DJ[j] T
@@ -365,9 +445,9 @@ VS_DEV void adj_record_to_params(const RolloutDev& rd, const RolloutAdj& a, int 
 
 // The transpose of the window FIFO's shift at a release tick: wb shifts back one column, column 0 was new to the shift.
 // Called behind a barrier; two barriers, the second behind its last write.
-template <bool PT, bool TREE>
+template <bool PT, bool TREE, bool ATT>
 VS_DEV void adj_window_shift_back(const RolloutDev& rd, int lane) {
-    const AdjLds L = adj_lds<PT, TREE>();
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const int nwin = 12 * rd.n_ref;
     constexpr int KMAX = (12 * MAX_STAGES + RO_BLOCK - 1) / RO_BLOCK;
     double keep[KMAX];
@@ -388,10 +468,28 @@ VS_DEV void adj_window_shift_back(const RolloutDev& rd, int lane) {
 // The tick that filled the window froze every column with its R.  Reads: wb, R, dR (PT: gp).  Returns `add` with the columns'
 // h_lin entries handed to rpy; PT: every column's cotangent is complete, so its sample goes to tc and its share of PINIT,
 // RPYINIT and the mass to gp, column by column.  Leaves wb zero.  One barrier, in front of that.
-template <bool PT, bool TREE>
+// ATT: in front of all that lane j runs att_column on column j, and behind one more barrier the columns' h_ang entries are
+// summed in column order: to rpy, and I_B's to gp (PT) or, as tau_bar's rows, through J to the joints (TREE).
+template <bool PT, bool TREE, bool ATT>
 VS_DEV double adj_window_first_fill(const RolloutDev& rd, const RolloutAdj& a, int tk, double m, int lane, double add) {
-    const AdjLds L = adj_lds<PT, TREE>();
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const int nref = rd.n_ref, nwin = 12 * rd.n_ref;
+    if constexpr (ATT) {
+        if (lane < nref) att_column<PT, TREE>(L, L.wb + 12 * lane, rd.traj_rpyd, window_fill_sample(rd, tk, lane), lane);
+        __syncthreads();
+        if (lane >= 6 && lane < 9)
+            for (int j = 0; j < nref; ++j) add += L.acs[ATT_COL * j + lane - 6];
+        if constexpr (TREE) {
+            if (lane >= 20 && lane < 28)
+                for (int j = 0; j < nref; ++j) add = att_tau_bar_col(L, add, lane - 20, j);
+        } else if constexpr (PT) {
+            if (lane >= 48 && lane < 57) {
+                double acc = 0.0;
+                for (int j = 0; j < nref; ++j) acc += att_ib_bar(L, j, (lane - 48) / 3, (lane - 48) % 3);
+                L.gp[VSMPC_PP_INERTIA_B + lane - 48] += acc;
+            }
+        }
+    }
     if (lane >= 6 && lane < 9)
         for (int j = 0; j < nref; ++j) {
             const int idx = window_fill_sample(rd, tk, j);
@@ -421,16 +519,16 @@ VS_DEV double adj_window_first_fill(const RolloutDev& rd, const RolloutAdj& a, i
 // Transpose of assemble_record at the taped state, then of the window FIFO.  Reads: s, p, gi, wb, sb (tt, tj) as staged.
 // Leaves: sb with the record's share added, wb as the tick in front of this one left the window (PT: gp, tc, ac).  Barriers:
 // those of its pieces, one between the pull-backs and the FIFO, one at its end.
-template <bool PT, bool TREE>
+template <bool PT, bool TREE, bool ATT>
 VS_DEV void adj_record_half(const RolloutDev& rd, const RolloutAdj& a, double m, int lane) {
-    const AdjLds L = adj_lds<PT, TREE>();
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const int tk = a.tick_rec + int(L.p[VSMPC_PP_TICK0]);
-    adj_record_setup<PT, TREE>(rd, lane);
-    double add = adj_record_to_state<PT, TREE>(rd, a, tk, m, lane);
-    if constexpr (PT) adj_record_to_params<TREE>(rd, a, tk, m, lane);
+    adj_record_setup<PT, TREE, ATT>(rd, tk, lane);
+    double add = adj_record_to_state<PT, TREE, ATT>(rd, a, tk, m, lane);
+    if constexpr (PT) adj_record_to_params<TREE, ATT>(rd, a, tk, m, lane);
     __syncthreads();
-    if (release_tick(rd, tk)) adj_window_shift_back<PT, TREE>(rd, lane);
-    if (a.first) add = adj_window_first_fill<PT, TREE>(rd, a, tk, m, lane, add);
+    if (release_tick(rd, tk)) adj_window_shift_back<PT, TREE, ATT>(rd, lane);
+    if (a.first) add = adj_window_first_fill<PT, TREE, ATT>(rd, a, tk, m, lane, add);
     if (lane < 40) L.sb[lane] += add;
     __syncthreads();
 }
@@ -439,9 +537,9 @@ VS_DEV void adj_record_half(const RolloutDev& rd, const RolloutAdj& a, double m,
 // Reads: pr, sb, p (tt).  Leaves: the log row's cotangent added to sb; in s the taped state with the move consumed when the
 // tick was Solved, f the move; alpha_s, Aq, IBi, vthr of the tick; xs[0..20) the 20-vector in front of sub-step 0.  Four
 // barriers, the first in front of its first write, the last behind its last.
-template <bool PT, bool TREE>
+template <bool PT, bool TREE, bool ATT>
 VS_DEV void adj_plant_setup(const RolloutDev& rd, const RolloutAdj& a, const AdjPlantRows& pr, int tk, bool solved, int lane) {
-    const AdjLds L = adj_lds<PT, TREE>();
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const int substeps = a.substeps;
     __syncthreads();
     if (lane < 14) L.sb[log_entry_state(lane)] += pr.lbar;
@@ -468,9 +566,9 @@ VS_DEV void adj_plant_setup(const RolloutDev& rd, const RolloutAdj& a, const Adj
 
 // The sub-steps of advance_kernel but the last, every one's 20-vector kept: xs + 20 ss is the state IN FRONT of sub-step ss.
 // Reads: what adj_plant_setup left.  Uses sc, omv, R.  Three barriers per sub-step, the last behind its write.
-template <bool PT, bool TREE>
+template <bool PT, bool TREE, bool ATT>
 VS_DEV void adj_plant_forward(const RolloutDev& rd, int substeps, int tk, double m, int lane) {
-    const AdjLds L = adj_lds<PT, TREE>();
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const double h = rd.period_mpc / double(substeps);
     for (int ss = 0; ss + 1 < substeps; ++ss) {
         const double* x = L.xs + 20 * ss;
@@ -495,9 +593,9 @@ struct AdjSubstepSums { double abar = 0.0, pacc = 0.0, al0 = 0.0, al1 = 0.0, al2
 // The sub-steps backwards: lam = dL/d(the 20-vector behind sub-step ss), one component per lane.  Reads: xs, sb, and what
 // adj_plant_setup left; ai0 (PT): the lower alpha sample of sub-step 0.  Leaves: lam in front of sub-step 0, the lanes' sums in
 // `sum`.  Uses sc, omv, omb, R, dR.  One barrier in front of the loop, four per sub-step, the last behind its write.
-template <bool PT, bool TREE>
+template <bool PT, bool TREE, bool ATT>
 VS_DEV void adj_plant_backward(const RolloutDev& rd, int substeps, int tk, int ai0, double m, int lane, AdjSubstepSums& sum) {
-    const AdjLds L = adj_lds<PT, TREE>();
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const double* lam = L.lam;
     const double* R = L.R;
     const double* omv = L.omv;
@@ -596,9 +694,9 @@ VS_DEV void adj_plant_backward(const RolloutDev& rd, int substeps, int tk, int a
 // leaves out the blocks it does not read), the alpha elements to ac[2..4].  Returns the new sbar of entry `lane` (0 behind the
 // 40) and writes the first move's cotangent; Solved: the move overwrote the latched entries and was added to q, otherwise it was
 // not consumed.  Leaves Ab, vb (tib), and sb[20..40) the move's cotangent.  Two barriers, the second in front of the write of fmbar.
-template <bool PT, bool TREE>
+template <bool PT, bool TREE, bool ATT>
 VS_DEV double adj_plant_tail(const RolloutAdj& a, int b, bool solved, int lane, const AdjSubstepSums& sum) {
-    const AdjLds L = adj_lds<PT, TREE>();
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const double* DJ = L.p + VSMPC_PP_DJ;
     if constexpr (TREE)
         if (lane >= 21 && lane < 30) L.tib[lane - 21] = sum.pacc;
@@ -663,24 +761,25 @@ VS_DEV double adj_plant_tail(const RolloutAdj& a, int b, bool solved, int lane, 
 
 // Transpose of advance_kernel at the taped (state, first move, status) of tick_plant.  Reads: pr, tr.ai0, sb, p (tt, tj).
 // Returns the new sbar of entry `lane`; writes fmbar (PT: gp, ac[2..4]).  Barriers: those of its four pieces.
-template <bool PT, bool TREE>
+template <bool PT, bool TREE, bool ATT>
 VS_DEV double adj_plant_half(const RolloutDev& rd, const RolloutAdj& a, const AdjTracks& tr, const AdjPlantRows& pr, double m, int b, int lane) {
-    const AdjLds L = adj_lds<PT, TREE>();
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const bool solved = pr.st == VSMPC_STATUS_SOLVED;
     const int tk = a.tick_plant + int(L.p[VSMPC_PP_TICK0]);
     AdjSubstepSums sum;
-    adj_plant_setup<PT, TREE>(rd, a, pr, tk, solved, lane);
-    adj_plant_forward<PT, TREE>(rd, a.substeps, tk, m, lane);
-    adj_plant_backward<PT, TREE>(rd, a.substeps, tk, tr.ai0, m, lane, sum);
-    return adj_plant_tail<PT, TREE>(a, b, solved, lane, sum);
+    adj_plant_setup<PT, TREE, ATT>(rd, a, pr, tk, solved, lane);
+    adj_plant_forward<PT, TREE, ATT>(rd, a.substeps, tk, m, lane);
+    adj_plant_backward<PT, TREE, ATT>(rd, a.substeps, tk, tr.ai0, m, lane, sum);
+    return adj_plant_tail<PT, TREE, ATT>(a, b, solved, lane, sum);
 }
 
 // ---- write-out --------------------------------------------------------------------------------------------------------------
 // Reads: out0, wb (PT: gp, tc, ac, tr).  Writes sbar (the jet-plant slots carry nothing) and wbar; PT: behind one barrier, gpar
-// and the owned samples of gtraj, each its running sum plus the slots (elements) of that sample in order.
-template <bool PT, bool TREE>
+// and the owned samples of gtraj, each its running sum plus the slots (elements) of that sample in order; ATT: the same lane,
+// the same order for the attitude samples of gatt (when the caller asked for it).
+template <bool PT, bool TREE, bool ATT>
 VS_DEV void adj_write_out(const RolloutDev& rd, const RolloutAdj& a, const AdjTracks& tr, double out0, int b, int lane) {
-    const AdjLds L = adj_lds<PT, TREE>();
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const int nwin = 12 * rd.n_ref;
     a.sbar[size_t(b) * VSMPC_PLANT_STATE + lane] = out0;
     if (lane + RO_BLOCK < VSMPC_PLANT_STATE) a.sbar[size_t(b) * VSMPC_PLANT_STATE + lane + RO_BLOCK] = 0.0;
@@ -691,10 +790,16 @@ VS_DEV void adj_write_out(const RolloutDev& rd, const RolloutAdj& a, const AdjTr
         double* gt = a.gtraj + size_t(b) * size_t(6 * rd.n_traj + rd.n_alpha);
         for_owned_samples(rd, a, tr, lane,
                           [&](int k, int ws, int c, int idx) {
-                              double sum = tr.tpre[k];
+                              double sum = tr.tpre[k], asum = 0.0;
+                              if constexpr (ATT) asum = tr.qpre[k];
                               for (int w2 = ws; w2 <= rd.n_ref; ++w2)
-                                  if (slot_sample(rd, tr.tkr, a.first, w2) == idx) sum += L.tc[6 * w2 + c];
+                                  if (slot_sample(rd, tr.tkr, a.first, w2) == idx) {
+                                      sum += L.tc[6 * w2 + c];
+                                      if constexpr (ATT) asum += L.atc[6 * w2 + c];
+                                  }
                               gt[traj_entry(rd, idx, c)] = sum;
+                              if constexpr (ATT)
+                                  if (a.gatt != nullptr) a.gatt[size_t(b) * size_t(6 * rd.n_traj) + traj_entry(rd, idx, c)] = asum;
                           },
                           [&](int idx) {
                               double sum = tr.apre;
@@ -707,19 +812,19 @@ VS_DEV void adj_write_out(const RolloutDev& rd, const RolloutAdj& a, const AdjTr
 
 // ---- the driver -------------------------------------------------------------------------------------------------------------
 // second half of tick a.tick_rec, then first half of tick a.tick_plant (either may be absent)
-template <bool PT, bool TREE>
+template <bool PT, bool TREE, bool ATT = false>
 VS_DEV void advance_adjoint_body(const RolloutDev& rd, const RolloutAdj& a) {
-    const AdjLds L = adj_lds<PT, TREE>();
+    const AdjLds L = adj_lds<PT, TREE, ATT>();
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= a.batch) return;
     AdjTracks tr;
     AdjPlantRows pr;
-    adj_stage_in<PT, TREE>(rd, a, b, lane, tr, pr);
+    adj_stage_in<PT, TREE, ATT>(rd, a, b, lane, tr, pr);
     const double m = L.p[VSMPC_PP_MASS];
-    if (a.tick_rec >= 0) adj_record_half<PT, TREE>(rd, a, m, lane);
+    if (a.tick_rec >= 0) adj_record_half<PT, TREE, ATT>(rd, a, m, lane);
     double out0 = lane < 40 ? L.sb[lane] : 0.0;   // the new sbar of this lane's entry
-    if (a.tick_plant >= 0) out0 = adj_plant_half<PT, TREE>(rd, a, tr, pr, m, b, lane);
-    adj_write_out<PT, TREE>(rd, a, tr, out0, b, lane);
+    if (a.tick_plant >= 0) out0 = adj_plant_half<PT, TREE, ATT>(rd, a, tr, pr, m, b, lane);
+    adj_write_out<PT, TREE, ATT>(rd, a, tr, out0, b, lane);
 }
 
 }  // namespace vsmpc

@@ -58,6 +58,7 @@ TT_IB = 72
 TT_SIZE = 81
 TT_NDIR = 12
 TREE_ADJOINT = 0x1   # vsmpc_rollout_set_tree_ex flag (VSMPC_TREE_ADJOINT)
+ATTITUDE_ADJOINT = 0x1   # vsmpc_rollout_set_attitude_tracks_ex flag (VSMPC_ATTITUDE_ADJOINT)
 
 # first-move block (24 doubles): dq(8) v0(4) throttle%(4) T1(4) Tdot1(4)
 FM_DQ = 0
@@ -145,6 +146,12 @@ def traj_grad_blocks(n_traj: int, n_alpha: int) -> dict:
     traj_pos | traj_vel | traj_alpha, 6 n_traj + n_alpha doubles"""
     return {"pos": (0, 3 * n_traj, (n_traj, 3)), "vel": (3 * n_traj, 3 * n_traj, (n_traj, 3)),
             "alpha": (6 * n_traj, n_alpha, (n_alpha,))}
+
+
+def att_grad_blocks(n_traj: int) -> dict:
+    """name -> (offset, length, shape) of the two blocks of one row of grad_att (vsmpc_rollout_backward_attitude):
+    traj_rpy | traj_rpy_dot, 6 n_traj doubles"""
+    return {"rpy": (0, 3 * n_traj, (n_traj, 3)), "rpy_dot": (3 * n_traj, 3 * n_traj, (n_traj, 3))}
 
 # per-instance status (mirrors the OsqpEigen::Status values the reference distinguishes,
 # IMPCProblem.cpp:285-294, variableSamplingMPC.cpp:91)

@@ -206,15 +206,22 @@ class ClosedLoopRollout:
             raise ValueError("state / params shape does not match the rollout batch")
         _lib.check(self.lib.vsmpc_rollout_reset(self._r, _ptr(state), _ptr(params)), "vsmpc_rollout_reset")
 
-    def set_attitude_tracks(self, traj_rpy=None, traj_rpy_dot=None):
+    def set_attitude_tracks(self, traj_rpy=None, traj_rpy_dot=None, adjoint: bool = False):
         """RPY / RPYDot tracks of the position trajectory (vsmpc_rollout_set_attitude_tracks; costsVSMPC.cpp:110-112,
-        141-146), [n_traj, 3] each or None (all zero, the shipped files).  Call reset() afterwards."""
+        141-146), [n_traj, 3] each or None (all zero, the shipped files).  Call reset() afterwards.
+        adjoint: vsmpc_rollout_set_attitude_tracks_ex with VSMPC_ATTITUDE_ADJOINT -- run(tape=True) and backward() then work
+        with an RPYDot track too, and backward(att=True) returns the gradient to both tracks; without it a rollout with an
+        RPYDot track refuses them."""
         a = None if traj_rpy is None else np.ascontiguousarray(traj_rpy, dtype=np.float64)
         b = None if traj_rpy_dot is None else np.ascontiguousarray(traj_rpy_dot, dtype=np.float64)
         for t in (a, b):
             if t is not None and t.shape != (self.n_traj, 3):
                 raise ValueError(f"attitude tracks must be [{self.n_traj}, 3]")
-        _lib.check(self.lib.vsmpc_rollout_set_attitude_tracks(self._r, _ptr(a), _ptr(b)), "vsmpc_rollout_set_attitude_tracks")
+        if adjoint:
+            _lib.check(self.lib.vsmpc_rollout_set_attitude_tracks_ex(self._r, _ptr(a), _ptr(b), L.ATTITUDE_ADJOINT),
+                       "vsmpc_rollout_set_attitude_tracks_ex")
+        else:
+            _lib.check(self.lib.vsmpc_rollout_set_attitude_tracks(self._r, _ptr(a), _ptr(b)), "vsmpc_rollout_set_attitude_tracks")
 
     def set_tree(self, tree: dict | None, adjoint: bool = False):
         """Kinematic-tree plant (vsmpc_rollout_set_tree): `tree` = a robot_tree dictionary (None = the parametric plant).
@@ -285,7 +292,12 @@ class ClosedLoopRollout:
         """doubles in one row of grad_traj: 6 n_traj + n_alpha (L.traj_grad_blocks names its three blocks)"""
         return int(self.lib.vsmpc_rollout_traj_grad_size(self._r))
 
-    def backward(self, log_bar=None, state_bar=None, params: bool = False, traj: bool = False) -> dict:
+    @property
+    def att_grad_size(self) -> int:
+        """doubles in one row of grad_att: 6 n_traj (L.att_grad_blocks names its two blocks)"""
+        return int(self.lib.vsmpc_rollout_att_grad_size(self._r))
+
+    def backward(self, log_bar=None, state_bar=None, params: bool = False, traj: bool = False, att: bool = False) -> dict:
         """vsmpc_rollout_backward over the last run(ticks, tape=True): the gradient of a loss on the flown trajectory, given
         as log_bar [ticks, batch, ROLLOUT_LOG] = dL/d(log rows) (columns 14, 15 ignored) and / or state_bar [batch,
         PLANT_STATE] = dL/d(final plant state).  Returns grad_state0 [batch, PLANT_STATE] (dL/d the plant state at the start
@@ -293,7 +305,9 @@ class ClosedLoopRollout:
         per loop under its own row with set_tunables) and flags [batch] (OR over the ticks of L.ADJ_*).  Needs adjoint=True.
         params / traj (vsmpc_rollout_backward_full): also grad_params [batch, PLANT_PARAMS] (L.PP_* order; the structural
         entries are zero) and / or grad_traj_pos, grad_traj_vel [batch, n_traj, 3] and grad_traj_alpha [batch, n_alpha], each
-        per loop: the tracks are shared, their gradient is the sum over the loops."""
+        per loop: the tracks are shared, their gradient is the sum over the loops.
+        att (vsmpc_rollout_backward_attitude; needs set_attitude_tracks(.., adjoint=True)): also grad_traj_rpy and
+        grad_traj_rpy_dot [batch, n_traj, 3], per loop like the other tracks."""
         ticks = getattr(self, "_taped", 0)
         lb = None if log_bar is None else np.ascontiguousarray(log_bar, dtype=np.float64)
         sb = None if state_bar is None else np.ascontiguousarray(state_bar, dtype=np.float64)
@@ -303,15 +317,23 @@ class ClosedLoopRollout:
             raise ValueError(f"state_bar must be [{self.batch}, {L.PLANT_STATE}]")
         out = {"grad_state0": np.empty((self.batch, L.PLANT_STATE)), "grad_gains": np.empty((self.batch, L.GRAD_SIZE)),
                "flags": np.empty(self.batch, dtype=np.int32)}
-        if not params and not traj:
+        if not params and not traj and not att:
             _lib.check(self.lib.vsmpc_rollout_backward(self._r, _ptr(lb), _ptr(sb), _ptr(out["grad_state0"]),
                                                        _ptr(out["grad_gains"]), _ptr(out["flags"]), None), "vsmpc_rollout_backward")
             return out
         gp = np.empty((self.batch, L.PLANT_PARAMS)) if params else None
         gt = np.empty((self.batch, self.traj_grad_size)) if traj else None
-        _lib.check(self.lib.vsmpc_rollout_backward_full(self._r, _ptr(lb), _ptr(sb), _ptr(out["grad_state0"]),
-                                                        _ptr(out["grad_gains"]), _ptr(gp), _ptr(gt), _ptr(out["flags"]), None),
-                   "vsmpc_rollout_backward_full")
+        if att:
+            ga = np.empty((self.batch, 6 * self.n_traj))
+            _lib.check(self.lib.vsmpc_rollout_backward_attitude(self._r, _ptr(lb), _ptr(sb), _ptr(out["grad_state0"]),
+                                                                _ptr(out["grad_gains"]), _ptr(gp), _ptr(gt), _ptr(ga),
+                                                                _ptr(out["flags"]), None), "vsmpc_rollout_backward_attitude")
+            for name, (off, n, shape) in L.att_grad_blocks(self.n_traj).items():
+                out["grad_traj_" + name] = ga[:, off:off + n].reshape((self.batch,) + shape).copy()
+        else:
+            _lib.check(self.lib.vsmpc_rollout_backward_full(self._r, _ptr(lb), _ptr(sb), _ptr(out["grad_state0"]),
+                                                            _ptr(out["grad_gains"]), _ptr(gp), _ptr(gt), _ptr(out["flags"]), None),
+                       "vsmpc_rollout_backward_full")
         if params:
             out["grad_params"] = gp
         if traj:
@@ -320,14 +342,15 @@ class ClosedLoopRollout:
         return out
 
     def backward_device(self, d_log_bar, d_state_bar, d_grad_state0, d_grad_gains, d_flags, stream=None, d_grad_params=None,
-                        d_grad_traj=None):
+                        d_grad_traj=None, d_grad_att=None):
         """vsmpc_rollout_backward_device: backward() on contiguous CUDA tensors (None: not given / not wanted); only enqueues,
         on `stream` or torch's current stream.  d_grad_params [batch, PLANT_PARAMS] and / or d_grad_traj [batch,
-        traj_grad_size] given: vsmpc_rollout_backward_full_device."""
+        traj_grad_size] given: vsmpc_rollout_backward_full_device; d_grad_att [batch, att_grad_size] given:
+        vsmpc_rollout_backward_attitude_device."""
         from .solver import _assert_f64_device, _dptr, _stream
-        _assert_f64_device(d_log_bar, d_state_bar, d_grad_state0, d_grad_gains, d_grad_params, d_grad_traj)
+        _assert_f64_device(d_log_bar, d_state_bar, d_grad_state0, d_grad_gains, d_grad_params, d_grad_traj, d_grad_att)
         ref_t = d_log_bar if d_log_bar is not None else d_state_bar
-        if d_grad_params is None and d_grad_traj is None:
+        if d_grad_params is None and d_grad_traj is None and d_grad_att is None:
             _lib.check(self.lib.vsmpc_rollout_backward_device(self._r, _dptr(d_log_bar), _dptr(d_state_bar), _dptr(d_grad_state0),
                                                               _dptr(d_grad_gains), _dptr(d_flags), _stream(ref_t, stream)),
                        "vsmpc_rollout_backward_device")
@@ -336,6 +359,14 @@ class ClosedLoopRollout:
             raise ValueError(f"d_grad_params must be [{self.batch}, {L.PLANT_PARAMS}]")
         if d_grad_traj is not None and tuple(d_grad_traj.shape) != (self.batch, self.traj_grad_size):
             raise ValueError(f"d_grad_traj must be [{self.batch}, {self.traj_grad_size}] (6 n_traj + n_alpha)")
+        if d_grad_att is not None:
+            if tuple(d_grad_att.shape) != (self.batch, 6 * self.n_traj):
+                raise ValueError(f"d_grad_att must be [{self.batch}, {6 * self.n_traj}] (6 n_traj)")
+            _lib.check(self.lib.vsmpc_rollout_backward_attitude_device(
+                self._r, _dptr(d_log_bar), _dptr(d_state_bar), _dptr(d_grad_state0), _dptr(d_grad_gains), _dptr(d_grad_params),
+                _dptr(d_grad_traj), _dptr(d_grad_att), _dptr(d_flags), _stream(ref_t, stream)),
+                "vsmpc_rollout_backward_attitude_device")
+            return
         _lib.check(self.lib.vsmpc_rollout_backward_full_device(self._r, _dptr(d_log_bar), _dptr(d_state_bar), _dptr(d_grad_state0),
                                                                _dptr(d_grad_gains), _dptr(d_grad_params), _dptr(d_grad_traj),
                                                                _dptr(d_flags), _stream(ref_t, stream)),
