@@ -638,6 +638,54 @@ int vsmpc_rollout_set_tree_ex(vsmpc_rollout* r, const vsmpc_tree* tree, unsigned
  * (batch x VSMPC_TUNE_SIZE doubles, kept until vsmpc_rollout_destroy), as vsmpc_rollout_set_tree allocates on first use;
  * a call that fails leaves the rollout as it was, runnable without a reset. */
 int vsmpc_rollout_set_tunables(vsmpc_rollout* r, const double* tunables);
+/*
+ * Noise in the closed loop: seeded sensor noise on what the controller is handed, and gusts on the plant, drawn on the device
+ * by a counter-based generator ("Noise in the closed loop"; executable model: tests/rollout_noise_model.py).  The
+ * reference's own loop has the first: MujocoSim.simulate_noise adds np.random.normal(0, 0.015, 3) to the base linear and to the
+ * base angular velocity the controller receives (src/mujoco_lib/ironcub_mujoco_simulator.py:271-288), which is
+ * sigma_lin_vel = sigma_ang_vel = 0.015 here.
+ *
+ * Generator: Philox4x32-10, multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85.  Block j of loop b
+ * at tick k is the output (w0, w1, w2, w3) of
+ *     counter = (j, k, loop_lo, loop_hi)     key = (seed_lo, seed_hi)     loop = first_index + b  (64 bit)
+ * with k the ticks since vsmpc_rollout_reset (PP_TICK0 is not added) and `loop` the loop's GLOBAL index, so that any slice of a
+ * sharded batch draws what the whole batch would.  A block gives two standard normals, Box-Muller on 53-bit uniforms:
+ *     u1 = (((uint64)w0 << 21 | w1 >> 11) + 0.5) 2^-53,  u2 likewise from (w2, w3)
+ *     z[2j] = sqrt(-2 ln u1) cos(2 pi u2)     z[2j+1] = sqrt(-2 ln u1) sin(2 pi u2)
+ * (the device evaluates the pair as sincospi(2 u2): the same angle, without the rounding of the product 2 pi u2).
+ * A tick uses nine blocks: z[0:12] is the measurement of tick k, z[12:18] the gust held over tick k.  Nothing is stored: graph
+ * replay, split runs and sharded batches reproduce each other bit for bit.
+ *
+ * Measurement: the record of tick k is built from a measured state in place of the plant state (the plant state itself, the
+ * log rows and the integration stay the true ones), with R = R(rpy) of the true attitude and I_B the plant's (the parameter,
+ * or I_B(q) of the kinematic tree):
+ *     p     += sigma_pos z[0:3]          h_lin += m   R^T (sigma_lin_vel z[3:6])     (a world-frame velocity error)
+ *     rpy   += sigma_rpy z[6:9]          h_ang += I_B R^T (sigma_ang_vel z[9:12])
+ * and everything the record derives from these follows: X0, the position and attitude errors, omega, R, I_G, the window
+ * column pushed on a release tick, the RPY unwrap.  The thrusts are not touched.
+ * Gust: over the sub-steps of tick k the constant world force sigma_force z[12:15] and body torque sigma_torque z[15:18] act
+ * beside the push of PP_DIST_F / PP_DIST_TAU, whatever the push's window.
+ *
+ * vsmpc_rollout_set_noise validates before it touches the device: a negative or non-finite sigma, or a negative first_index, is
+ * VSMPC_ERR_INVALID_ARG with the field named in vsmpc_strerror's text, and the rollout stays as it was.  NULL switches the noise
+ * off, as if it had never been set: the rollout then launches the kernels it launched before.  Either way the captured ticks
+ * are dropped and vsmpc_rollout_reset is required before the next run, as after vsmpc_rollout_set_tree.  Noise combines with the
+ * tree plant, the jet plant option, attitude tracks and per-instance tunables.  With noise set vsmpc_rollout_run_taped and every
+ * vsmpc_rollout_backward* entry return VSMPC_ERR_UNSUPPORTED_CONFIG with a text that names the noise: the pathwise derivative
+ * would need the noise's own dependence on the attitude, the mass and I_B.
+ *
+ * vsmpc_rollout_noise_draws returns what ticks tick0 .. tick0 + ticks - 1 of this rollout's loops draw, computed by the device
+ * function the kernels call: z [ticks][batch][18] and, unless NULL, the generator's words [ticks][batch][9][4] (host buffers).
+ * Needs noise set; runs nothing of the loop.
+ */
+typedef struct vsmpc_noise {
+    unsigned long long seed;
+    long long first_index;                                        /* global index of loop 0 of this rollout */
+    double sigma_pos, sigma_lin_vel, sigma_rpy, sigma_ang_vel;    /* m, m/s, rad, rad/s */
+    double sigma_force, sigma_torque;                             /* N, Nm */
+} vsmpc_noise;
+int vsmpc_rollout_set_noise(vsmpc_rollout* r, const vsmpc_noise* n);
+int vsmpc_rollout_noise_draws(vsmpc_rollout* r, int tick0, int ticks, double* z, unsigned* words);
 int vsmpc_rollout_get_state(vsmpc_rollout* r, double* state);
 int vsmpc_rollout_get_records(vsmpc_rollout* r, double* records);
 

@@ -30,6 +30,8 @@ SIGNATURES = {
     "vsmpc_solve_batch_tuned": [vp, dp, dp, c_int, dp, dp, vp, vp, vp],
     "vsmpc_solve_batch_tuned_device": [vp, dp, dp, c_int, dp, dp, vp, vp, vp],
     "vsmpc_rollout_set_tunables": [vp, dp],
+    "vsmpc_rollout_set_noise": [vp, vp],                                 # r, vsmpc_noise* (layout.CNoise) or NULL
+    "vsmpc_rollout_noise_draws": [vp, c_int, c_int, dp, vp],             # r, tick0, ticks, z, words
     # h, in, x, tunables, batch, y, cert (, stream)
     "vsmpc_certify_batch": [vp, dp, dp, dp, c_int, dp, dp], "vsmpc_certify_batch_device": [vp, dp, dp, dp, c_int, dp, dp, vp],
     # h, in, batch, x, first_move, status, iters, dx_dx0, dfm_dx0, active, sens_flags, stream

@@ -18,7 +18,7 @@ SOURCES = [SOLVE, "vsmpc_dispatch.hip", "vsmpc_rollout.hip", "vsmpc_rollout_adjo
            "vsmpc_capi_rollout.hip", "vsmpc_jet.hip", "vsmpc_provider.hip", "vsmpc_tree_jacobian.hip", "vsmpc_runtime.hip", "vsmpc_certify.hip"]
 HEADERS = ["vsmpc_device.hpp", "vsmpc_launch.hpp", "vsmpc_host.hpp", "vsmpc_p0.hpp", "vsmpc_smem.hpp", "vsmpc_p1_syrk.hpp", "vsmpc_p1_struct.hpp",
            "vsmpc_p3.hpp", "vsmpc_p4.hpp", "vsmpc_p5.hpp", "vsmpc_panel_asm.inc",
-           "vsmpc_structure.hpp", "vsmpc_rt_core.hpp", "vsmpc_rt_sens.hpp", "vsmpc_rt_adjoint.hpp", "vsmpc_rt_adjoint_record.hpp", "vsmpc_solve_body.inc", "vsmpc_jet_device.hpp", "vsmpc_rollout_device.hpp", "vsmpc_rollout_adjoint_device.hpp", "vsmpc_horizons.def", os.path.join("..", "..", "include", "vsmpc.h"),
+           "vsmpc_structure.hpp", "vsmpc_rt_core.hpp", "vsmpc_rt_sens.hpp", "vsmpc_rt_adjoint.hpp", "vsmpc_rt_adjoint_record.hpp", "vsmpc_solve_body.inc", "vsmpc_jet_device.hpp", "vsmpc_rollout_device.hpp", "vsmpc_noise_device.hpp", "vsmpc_rollout_adjoint_device.hpp", "vsmpc_horizons.def", os.path.join("..", "..", "include", "vsmpc.h"),
            os.path.join("..", "..", "include", "vsmpc_jet.h")]
 
 

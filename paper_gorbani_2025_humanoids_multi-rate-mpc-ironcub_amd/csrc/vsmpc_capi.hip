@@ -100,6 +100,11 @@ int vsmpc::invalid_arg() {
     return VSMPC_ERR_INVALID_ARG;
 }
 
+int vsmpc::invalid_field(const char* entry, const char* field) {
+    snprintf(g_arg_msg, sizeof(g_arg_msg), "invalid argument (%s: invalid %s)", entry, field);
+    return VSMPC_ERR_INVALID_ARG;
+}
+
 int vsmpc::unsupported(const char* why) {
     g_unsupported_msg = why;
     return VSMPC_ERR_UNSUPPORTED_CONFIG;

@@ -45,6 +45,12 @@ void invalidate(vsmpc_rollout* r) {
     r->tape.ticks = 0;
 }
 
+const RolloutNoise* noise_of(const vsmpc_rollout* r) { return r->use_noise ? &r->noise : nullptr; }
+
+const char* const NOISE_NO_ADJOINT =
+    "vsmpc_rollout_run_taped / vsmpc_rollout_backward: no adjoint of a rollout with noise (vsmpc_rollout_set_noise): its derivative would need the noise's "
+    "own dependence on the attitude, the mass and I_B";
+
 }  // namespace
 
 extern "C" {
@@ -120,7 +126,7 @@ int vsmpc_rollout_reset(vsmpc_rollout* r, const double* state, const double* par
     // record of tick 0; from here on every tick's advance kernel leaves the record of the following tick
     r->valid = 0;
     if (r->use_tree) HIP_TRY(enqueue_tree(r, nullptr, nullptr, nullptr));
-    HIP_TRY(launch_record(r->rd, tick_record(r), nullptr));
+    HIP_TRY(launch_record(r->rd, tick_record(r), nullptr, noise_of(r)));
     if (r->use_tree) HIP_TRY(enqueue_tree_lambda(r, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     r->valid = 1;
@@ -208,6 +214,41 @@ int vsmpc_rollout_set_tunables(vsmpc_rollout* r, const double* tunables) {
     return VSMPC_OK;
 }
 
+int vsmpc_rollout_set_noise(vsmpc_rollout* r, const vsmpc_noise* n) {
+    if (n != nullptr) {   // first, what can be refused: a refused call leaves the rollout as it was, and touches no device
+        const struct { const char* name; double v; } sig[] = {
+            {"sigma_pos", n->sigma_pos}, {"sigma_lin_vel", n->sigma_lin_vel}, {"sigma_rpy", n->sigma_rpy},
+            {"sigma_ang_vel", n->sigma_ang_vel}, {"sigma_force", n->sigma_force}, {"sigma_torque", n->sigma_torque}};
+        for (const auto& f : sig)
+            if (!(f.v >= 0.0) || !std::isfinite(f.v)) return invalid_field("vsmpc_rollout_set_noise", f.name);
+        if (n->first_index < 0) return invalid_field("vsmpc_rollout_set_noise", "first_index");
+    }
+    if (r == nullptr) return invalid_arg();
+    ON_DEVICE(r->h->device);
+    invalidate(r);   // the captured ticks have the other launches, the record of the next tick the other measurement
+    r->use_noise = n != nullptr;
+    if (n != nullptr)
+        r->noise = {n->seed, static_cast<unsigned long long>(n->first_index), n->sigma_pos, n->sigma_lin_vel, n->sigma_rpy,
+                    n->sigma_ang_vel, n->sigma_force, n->sigma_torque};
+    return VSMPC_OK;
+}
+
+int vsmpc_rollout_noise_draws(vsmpc_rollout* r, int tick0, int ticks, double* z, unsigned* words) {
+    if (r == nullptr || z == nullptr || tick0 < 0 || ticks <= 0 || tick0 > INT_MAX - ticks) return invalid_arg();
+    if (!r->use_noise) return invalid_field("vsmpc_rollout_noise_draws", "rollout: no noise set (vsmpc_rollout_set_noise)");
+    ON_DEVICE(r->h->device);
+    const size_t blocks = size_t(ticks) * size_t(r->batch) * 9;
+    DevBuf<double> d_z;
+    DevBuf<unsigned> d_w;
+    hipError_t e = d_z.alloc(2 * blocks);
+    if (e == hipSuccess && words != nullptr) e = d_w.alloc(4 * blocks);
+    if (e != hipSuccess) return alloc_fail(e, "vsmpc_rollout_noise_draws");
+    HIP_TRY(launch_noise_draws(r->noise, r->batch, tick0, ticks, d_z, d_w, nullptr));
+    HIP_TRY(hipMemcpy(z, d_z, 2 * blocks * sizeof(double), hipMemcpyDeviceToHost));
+    if (words != nullptr) HIP_TRY(hipMemcpy(words, d_w, 4 * blocks * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return VSMPC_OK;
+}
+
 // include/vsmpc_jet.h
 int vsmpc_rollout_set_jet_plant(vsmpc_rollout* r, vsmpc_jet* j, const double* Q, const double* R) {
     if (r == nullptr || (j != nullptr && (Q == nullptr || R == nullptr))) return invalid_arg();
@@ -252,7 +293,7 @@ hipError_t enqueue_tick(vsmpc_rollout* r, hipStream_t s, int tape_row) {
     if (e == hipSuccess) e = keep(tp.fm + o * VSMPC_FM_SIZE, h->d_fm, B * VSMPC_FM_SIZE * sizeof(double));
     if (e == hipSuccess) e = keep(tp.status + o, h->d_status, B * sizeof(int));
     if (e == hipSuccess && r->use_tree) e = enqueue_tree(r, h->d_fm, h->d_status, s);   // A_mom, I_B of the joints after the move
-    if (e == hipSuccess) e = launch_advance(r->rd, tick_record(r), s);
+    if (e == hipSuccess) e = launch_advance(r->rd, tick_record(r), s, noise_of(r));
     if (e == hipSuccess && r->use_tree) e = enqueue_tree_lambda(r, s);
     return e;
 }
@@ -426,6 +467,7 @@ int run(vsmpc_rollout* r, int ticks, double* log, void* stream, bool taped) {
     if (r == nullptr || ticks < 0) return invalid_arg();
     if (!r->valid) return invalid_arg();   // never reset, or a previous run failed half-way: reset() first
     if (taped) {                           // what the backward sweep has no transpose of
+        if (r->use_noise) return unsupported(NOISE_NO_ADJOINT);
         if (r->use_tree && !r->tree_adjoint)
             return unsupported("vsmpc_rollout_run_taped: no adjoint of the kinematic-tree plant (vsmpc_rollout_set_tree)");
         if (r->rd.jet_nn) return unsupported("vsmpc_rollout_run_taped: no adjoint of the jet plant option (vsmpc_rollout_set_jet_plant)");
@@ -464,7 +506,9 @@ int run(vsmpc_rollout* r, int ticks, double* log, void* stream, bool taped) {
 
 // what both backward entries refuse, in this order
 int backward_refusal(const vsmpc_rollout* r, const double* log_bar, const double* state_bar) {
-    if (r == nullptr || (log_bar == nullptr && state_bar == nullptr) || r->tape.ticks == 0) return invalid_arg();
+    if (r == nullptr) return invalid_arg();
+    if (r->use_noise) return unsupported(NOISE_NO_ADJOINT);   // (it has no tape either: the caller learns why)
+    if ((log_bar == nullptr && state_bar == nullptr) || r->tape.ticks == 0) return invalid_arg();
     if (!r->h->adjoint_record.on) return unsupported(BACKWARD_NEEDS_FLAG);
     return VSMPC_OK;
 }

@@ -2,6 +2,7 @@
 // HIP resources, the handle structs, row copies, and the way a HIP failure becomes a return code.  No kernels.
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -67,6 +68,8 @@ hipError_t download_rows(T* host, const typename Same<T>::type* dev, size_t firs
 // (vsmpc_strerror describes the call that failed last on this thread).  Every return of that code in this library goes
 // through here: a site that returned the bare constant would leave the text of an earlier refusal standing.
 int unsupported(const char* why = nullptr);
+// VSMPC_ERR_INVALID_ARG with a text that names the entry and the argument's field it refuses (vsmpc_capi.hip)
+int invalid_field(const char* entry, const char* field);
 int hip_fail(hipError_t e, const char* what);   // VSMPC_ERR_HIP, through vsmpc_strerror's channel
 inline int hip_fail_into(char (&msg)[256], hipError_t e, const char* what) {
     snprintf(msg, sizeof(msg), "HIP error in %s: %s", what, hipGetErrorString(e));
@@ -182,6 +185,9 @@ struct vsmpc_rollout {
     // per-instance tunables (vsmpc_rollout_set_tunables)
     int use_tun;
     vsmpc::DevBuf<double> d_tun;  // rows [batch][VSMPC_TUNE_SIZE]
+    // sensor noise and gusts (vsmpc_rollout_set_noise): the record and advance launches are then of the noisy kernels
+    int use_noise;
+    vsmpc::RolloutNoise noise;
     // tape of the last vsmpc_rollout_run_taped and the scratch of vsmpc_rollout_backward: allocated or grown by run_taped
     struct Tape {
         int ticks = 0;        // ticks on the tape; 0: none (never taped, or invalidated by reset / set_* / an untaped run)

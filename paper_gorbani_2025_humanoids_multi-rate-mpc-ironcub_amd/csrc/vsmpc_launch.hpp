@@ -43,9 +43,9 @@ inline hipError_t allow_dynamic_lds(const void* kernel, std::atomic<bool> (&attr
     return hipSuccess;
 }
 
-// VSMPC_ERR_INVALID_ARG for every entry but vsmpc_pack_tunables (defined beside it in vsmpc_capi.hip; the other codes that
-// carry a text are declared in vsmpc_host.hpp): it also drops the text a refused pack left on this thread, so that
-// vsmpc_strerror describes the call that failed last
+// VSMPC_ERR_INVALID_ARG for every entry but vsmpc_pack_tunables and the fields vsmpc_rollout_set_noise refuses (defined beside
+// the first in vsmpc_capi.hip; the other codes that carry a text are declared in vsmpc_host.hpp): it also drops the text such a
+// refusal left on this thread, so that vsmpc_strerror describes the call that failed last
 int invalid_arg();
 
 enum Variant { VARIANT_NONE = 0 };  // 1.. = position in csrc/vsmpc_horizons.def
@@ -221,8 +221,22 @@ struct RolloutTick {
     const int* iters;
     const RolloutCtl* ctl;
 };
-hipError_t launch_record(const RolloutDev& rd, const RolloutTick& k, hipStream_t stream);
-hipError_t launch_advance(const RolloutDev& rd, const RolloutTick& k, hipStream_t stream);
+// Noise of the closed loop (vsmpc_rollout_set_noise; the generator and the draws: vsmpc_noise_device.hpp).  It rides behind the
+// other arguments of the two kernels' NOISE instantiations and is no part of RolloutDev: the code of a rollout without noise
+// stays as it is.
+struct RolloutNoise {
+    unsigned long long seed;
+    unsigned long long first_index;   // global index of loop 0 of this rollout
+    double sigma_pos, sigma_lin_vel, sigma_rpy, sigma_ang_vel;   // measurement: m, m/s, rad, rad/s
+    double sigma_force, sigma_torque;                            // gust: N, Nm
+};
+// nz == nullptr: record_kernel<false> / advance_kernel<false>, what the kernels were before they had a second instantiation;
+// given: their NOISE instantiations, with the measured state in the record and the gust beside the push
+hipError_t launch_record(const RolloutDev& rd, const RolloutTick& k, hipStream_t stream, const RolloutNoise* nz = nullptr);
+hipError_t launch_advance(const RolloutDev& rd, const RolloutTick& k, hipStream_t stream, const RolloutNoise* nz = nullptr);
+// noise_draws_kernel: what ticks tick0 .. tick0 + ticks - 1 of `batch` loops draw, z [ticks][batch][18] and (or nullptr) the
+// generator's words [ticks][batch][9][4] (device), through the device function the two noisy kernels call
+hipError_t launch_noise_draws(const RolloutNoise& nz, int batch, int tick0, int ticks, double* z, unsigned* words, hipStream_t stream);
 
 // One launch of the rollout's backward sweep (vsmpc_rollout_adjoint.hip): the record half of tick `tick_rec`, then the plant
 // half of tick `tick_plant` (ticks as the rollout counts them since its reset; -1: that half is absent).  All device pointers,

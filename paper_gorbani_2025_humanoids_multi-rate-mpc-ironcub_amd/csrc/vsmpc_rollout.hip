@@ -28,9 +28,12 @@
 // same centroidal-momentum model the MPC linearises, but with the non-linear rotation kinematics, the joint-dependent
 // (bilinear) jet map A_mom(q) T and the non-linear polynomial jet model (utils/src/JetModel.cpp:29-64), integrated
 // explicitly.
+#include <type_traits>
+
 #include "vsmpc_device.hpp"
 #include "vsmpc_jet_device.hpp"
 #include "vsmpc_launch.hpp"
+#include "vsmpc_noise_device.hpp"
 #include "vsmpc_rollout_device.hpp"
 
 namespace vsmpc {
@@ -210,11 +213,27 @@ VS_DEV void assemble_record(const RolloutDev& rd, const double* __restrict__ s, 
     __syncthreads();
 }
 
+// The rollout's two kernels have a NOISE instantiation each (vsmpc_rollout_set_noise): the record is assembled from the measured
+// state (measure_state, with the draws of the tick the record belongs to) and the gust of the tick acts beside the push; the
+// plant state in HBM, the log row and the integration stay the true ones.  Without NOISE the last argument is an empty struct
+// and the kernels are instruction for instruction what they were before they became templates.
+struct NoNoise {};
+template <bool NOISE> using NoiseArg = std::conditional_t<NOISE, RolloutNoise, NoNoise>;
+template <bool NOISE>
+VS_DEV double* noise_lds() {   // the draws of one tick in LDS; no LDS without NOISE
+    if constexpr (NOISE) {
+        __shared__ double zn[NOISE_LDS];
+        return zn;
+    } else {
+        return nullptr;
+    }
+}
+template <bool NOISE>
 __global__ __launch_bounds__(RO_BLOCK) void record_kernel(RolloutDev rd, int batch, const double* __restrict__ state,
                                                            const double* __restrict__ params, const int* __restrict__ tick,
                                                            const double* __restrict__ traj_pos, const double* __restrict__ traj_vel,
                                                            const double* __restrict__ traj_alpha, double* __restrict__ tstate,
-                                                           double* __restrict__ rec) {
+                                                           double* __restrict__ rec, NoiseArg<NOISE> nz) {
     __shared__ double s[VSMPC_PLANT_STATE], p[VSMPC_PLANT_PARAMS + 1], R[9], om[3], tIB[9], tAm[24];
     __shared__ double r[VSMPC_IN_XREF + 12 * MAX_STAGES], ts[12 * MAX_STAGES + 8];
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -226,6 +245,11 @@ __global__ __launch_bounds__(RO_BLOCK) void record_kernel(RolloutDev rd, int bat
         if (lane >= 32 && lane < 56) tAm[lane - 32] = rd.tree_ro[size_t(b) * VSMPC_RO_SIZE + VSMPC_RO_AMOMB + lane - 32];
     }
     __syncthreads();
+    if constexpr (NOISE) {
+        double* const zn = noise_lds<true>();
+        draw_measurement(nz, b, tick[b], zn, lane);
+        measure_state(nz, zn, p[VSMPC_PP_MASS], rd.tree ? tIB : p + VSMPC_PP_INERTIA_B, s, lane);
+    }
     assemble_record(rd, s, p, tick[b] + int(p[VSMPC_PP_TICK0]), traj_pos, traj_vel, traj_alpha, R, om, ts, r, lane, true,
                     rd.tree ? tIB : p + VSMPC_PP_INERTIA_B, tAm);
     double* out = rec + size_t(b) * rd.n_in;
@@ -237,6 +261,7 @@ __global__ __launch_bounds__(RO_BLOCK) void record_kernel(RolloutDev rd, int bat
 // One wavefront per instance: staging and the joint-dependent jet map in parallel, the short ODE integration in lane 0
 // on registers, coalesced write-back.  With `rec_next` the record of the NEXT tick is assembled from the advanced state
 // while it is still in LDS (one launch and one staging less per tick than a separate record_kernel).
+template <bool NOISE>
 __global__ __launch_bounds__(RO_BLOCK) void advance_kernel(RolloutDev rd, int batch, double* __restrict__ state,
                                                             const double* __restrict__ params, int* __restrict__ tick,
                                                             const double* __restrict__ fm, const int* __restrict__ status,
@@ -244,7 +269,7 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_kernel(RolloutDev rd, int ba
                                                             const RolloutCtl* __restrict__ ctl, int substeps,
                                                             const double* __restrict__ traj_pos,
                                                             const double* __restrict__ traj_vel, double* __restrict__ tstate,
-                                                            double* __restrict__ rec_next) {
+                                                            double* __restrict__ rec_next, NoiseArg<NOISE> nz) {
     __shared__ double s[VSMPC_PLANT_STATE], p[VSMPC_PLANT_PARAMS + 1], f[VSMPC_FM_SIZE], Aq[24], IBi[9], R[9], om[3], tIB[9];
     __shared__ double r[VSMPC_IN_XREF + 12 * MAX_STAGES], ts[12 * MAX_STAGES + 8];
     __shared__ float jw[17 * JET_HMAX + 1];   // LSTM weights of the jet plant option
@@ -264,6 +289,8 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_kernel(RolloutDev rd, int ba
     // every global load of this kernel is requested as early as possible: each dependent round trip costs ~1.5 us
     double* const log = ctl->log;
     const int tick_base = ctl->tick_base, log_rows = ctl->log_rows;
+    double* const zn = noise_lds<NOISE>();   // NOISE: the gust of this tick, the measurement of the next
+    if constexpr (NOISE) draw_tick(nz, b, tick_before, zn, lane);
     __syncthreads();
     __shared__ double alpha_s[16];   // alpha-gravity of every sub-step (one round trip instead of one per sub-step)
     if (lane >= 32 && lane < 32 + substeps && lane < 48) {
@@ -330,7 +357,8 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_kernel(RolloutDev rd, int ba
             const SinCos a = sincos_of(sc);
             if (lane == 0) rot_from_sincos(a, Rm);
             __syncthreads();
-            const double d = substep_rate(x, Rm, omv, a, Aq, vthr, p, m, alpha, dist, rd.jet_nn, lane);
+            double d = substep_rate(x, Rm, omv, a, Aq, vthr, p, m, alpha, dist, rd.jet_nn, lane);
+            if constexpr (NOISE) d += gust_rate(nz, zn, Rm, lane);
             __syncthreads();                                  // every lane has read x before anyone updates it
             if (lane < 20) x[lane] += h * d;
             __syncthreads();
@@ -359,6 +387,7 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_kernel(RolloutDev rd, int ba
     if (rd.tree && lane < 4)   // the thrusts the next tick's Lambda terms are formed with (kinematics kernel, next launch)
         rd.tree_kin[size_t(b) * VSMPC_KIN_SIZE + VSMPC_KIN_THRUST + lane] = rd.jet_nn ? s[VSMPC_PS_EST + 2 * lane] : s[VSMPC_PS_T + lane];
     if (rec_next != nullptr) {
+        if constexpr (NOISE) measure_state(nz, zn, p[VSMPC_PP_MASS], rd.tree ? tIB : p + VSMPC_PP_INERTIA_B, s, lane);
         assemble_record(rd, s, p, tick_before + 1 + int(p[VSMPC_PP_TICK0]), traj_pos, traj_vel, traj_alpha, R, om, ts, r, lane, false,
                         rd.tree ? tIB : p + VSMPC_PP_INERTIA_B, Aq);
         double* out = rec_next + size_t(b) * rd.n_in;
@@ -366,6 +395,29 @@ __global__ __launch_bounds__(RO_BLOCK) void advance_kernel(RolloutDev rd, int ba
         double* tso = tstate + size_t(b) * rd.n_ts;
         for (int e = lane; e < rd.n_ts; e += RO_BLOCK) tso[e] = ts[e];
     }
+}
+
+// One Philox block per thread, t = (tick, loop, block) in the order of the outputs: vsmpc_rollout_noise_draws
+__global__ __launch_bounds__(RO_BLOCK) void noise_draws_kernel(RolloutNoise nz, int batch, int tick0, long long n,
+                                                                double* __restrict__ z, unsigned* __restrict__ words) {
+    const long long t = static_cast<long long>(blockIdx.x) * RO_BLOCK + threadIdx.x;
+    if (t >= n) return;
+    const int j = int(t % NOISE_BLOCKS);
+    const long long tb = t / NOISE_BLOCKS;
+    unsigned w[4];
+    double za, zb;
+    noise_block(nz, int(tb % batch), tick0 + int(tb / batch), j, w, za, zb);
+    z[2 * t] = za;
+    z[2 * t + 1] = zb;
+    if (words != nullptr)
+        for (int i = 0; i < 4; ++i) words[4 * t + i] = w[i];
+}
+
+hipError_t launch_noise_draws(const RolloutNoise& nz, int batch, int tick0, int ticks, double* z, unsigned* words, hipStream_t stream) {
+    const long long n = static_cast<long long>(ticks) * batch * NOISE_BLOCKS;
+    hipLaunchKernelGGL(noise_draws_kernel, dim3(unsigned((n + RO_BLOCK - 1) / RO_BLOCK)), dim3(RO_BLOCK), 0, stream, nz, batch, tick0, n,
+                       z, words);
+    return hipGetLastError();
 }
 
 // Provider state of the tree plant, one thread per instance: the base frame is the body frame (origin, identity attitude,
@@ -392,15 +444,23 @@ hipError_t launch_tree_state(const RolloutDev& rd, int batch, const double* stat
     return hipGetLastError();
 }
 
-hipError_t launch_record(const RolloutDev& rd, const RolloutTick& k, hipStream_t stream) {
-    hipLaunchKernelGGL(record_kernel, dim3(k.batch), dim3(RO_BLOCK), 0, stream, rd, k.batch, k.state, k.params, k.tick,
-                       k.traj_pos, k.traj_vel, k.traj_alpha, k.tstate, k.rec);
+hipError_t launch_record(const RolloutDev& rd, const RolloutTick& k, hipStream_t stream, const RolloutNoise* nz) {
+    if (nz != nullptr)
+        hipLaunchKernelGGL(record_kernel<true>, dim3(k.batch), dim3(RO_BLOCK), 0, stream, rd, k.batch, k.state, k.params, k.tick,
+                           k.traj_pos, k.traj_vel, k.traj_alpha, k.tstate, k.rec, *nz);
+    else
+        hipLaunchKernelGGL(record_kernel<false>, dim3(k.batch), dim3(RO_BLOCK), 0, stream, rd, k.batch, k.state, k.params, k.tick,
+                           k.traj_pos, k.traj_vel, k.traj_alpha, k.tstate, k.rec, NoNoise{});
     return hipGetLastError();
 }
 
-hipError_t launch_advance(const RolloutDev& rd, const RolloutTick& k, hipStream_t stream) {
-    hipLaunchKernelGGL(advance_kernel, dim3(k.batch), dim3(RO_BLOCK), 0, stream, rd, k.batch, k.state, k.params, k.tick, k.fm,
-                       k.status, k.iters, k.traj_alpha, k.ctl, k.substeps, k.traj_pos, k.traj_vel, k.tstate, k.rec);
+hipError_t launch_advance(const RolloutDev& rd, const RolloutTick& k, hipStream_t stream, const RolloutNoise* nz) {
+    if (nz != nullptr)
+        hipLaunchKernelGGL(advance_kernel<true>, dim3(k.batch), dim3(RO_BLOCK), 0, stream, rd, k.batch, k.state, k.params, k.tick,
+                           k.fm, k.status, k.iters, k.traj_alpha, k.ctl, k.substeps, k.traj_pos, k.traj_vel, k.tstate, k.rec, *nz);
+    else
+        hipLaunchKernelGGL(advance_kernel<false>, dim3(k.batch), dim3(RO_BLOCK), 0, stream, rd, k.batch, k.state, k.params, k.tick, k.fm,
+                           k.status, k.iters, k.traj_alpha, k.ctl, k.substeps, k.traj_pos, k.traj_vel, k.tstate, k.rec, NoNoise{});
     return hipGetLastError();
 }
 

@@ -185,6 +185,24 @@ class CConfig(ctypes.Structure):
     ]
 
 
+class CNoise(ctypes.Structure):
+    """ctypes image of `vsmpc_noise` in include/vsmpc.h (vsmpc_rollout_set_noise)."""
+    _fields_ = [
+        ("seed", ctypes.c_ulonglong),
+        ("first_index", ctypes.c_longlong),
+        ("sigma_pos", ctypes.c_double),
+        ("sigma_lin_vel", ctypes.c_double),
+        ("sigma_rpy", ctypes.c_double),
+        ("sigma_ang_vel", ctypes.c_double),
+        ("sigma_force", ctypes.c_double),
+        ("sigma_torque", ctypes.c_double),
+    ]
+
+
+NOISE_DRAWS = 18   # normals per loop and tick: z[0:12] the measurement of the tick, z[12:18] the gust held over it
+NOISE_BLOCKS = 9   # Philox blocks behind them, two normals each
+
+
 @dataclasses.dataclass
 class MPCConfig:
     """Keys of VS_MPC_CONFIG (src/config/vs_mcp_config.xml:7-43); defaults are the paper values."""

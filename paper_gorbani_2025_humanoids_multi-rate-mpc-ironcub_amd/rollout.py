@@ -252,6 +252,29 @@ class ClosedLoopRollout:
             raise ValueError(f"one configuration / one row of {L.TUNE_SIZE} tunables per loop ({self.batch})")
         _lib.check(self.lib.vsmpc_rollout_set_tunables(self._r, _ptr(rows)), "vsmpc_rollout_set_tunables")
 
+    def set_noise(self, seed, first_index: int = 0, lin_vel: float = 0.015, ang_vel: float = 0.015, pos: float = 0.0,
+                  rpy: float = 0.0, force: float = 0.0, torque: float = 0.0):
+        """Seeded sensor noise and gusts (vsmpc_rollout_set_noise), drawn on the device by a counter-based generator: the
+        controller is handed p + pos z, h_lin + m R^T (lin_vel z), rpy + rpy z and h_ang + I_B R^T (ang_vel z) in place of the
+        plant's state (m, m/s, rad, rad/s), and a constant world force `force` z [N] and body torque `torque` z [Nm] act on
+        the plant over every tick.  The defaults are the reference's simulate_noise (ironcub_mujoco_simulator.py:271-288).
+        Loop b draws as loop first_index + b of the whole batch (sharding.rank_first_index).  seed=None turns the noise off.
+        Call reset() afterwards; run(tape=True) and backward() are refused while noise is set."""
+        if seed is None:
+            _lib.check(self.lib.vsmpc_rollout_set_noise(self._r, None), "vsmpc_rollout_set_noise")
+            return
+        n = L.CNoise(int(seed), int(first_index), float(pos), float(lin_vel), float(rpy), float(ang_vel), float(force), float(torque))
+        _lib.check(self.lib.vsmpc_rollout_set_noise(self._r, ctypes.byref(n)), "vsmpc_rollout_set_noise")
+
+    def noise_draws(self, tick0: int, ticks: int, words: bool = False):
+        """What ticks tick0 .. tick0 + ticks - 1 draw (vsmpc_rollout_noise_draws, the device function the kernels call):
+        z [ticks, batch, 18] -- z[..., 0:12] the measurement of the tick, z[..., 12:18] its gust -- and with words=True also
+        the generator's words [ticks, batch, 9, 4] (uint32)."""
+        z = np.empty((int(ticks), self.batch, L.NOISE_DRAWS))
+        w = np.empty((int(ticks), self.batch, L.NOISE_BLOCKS, 4), dtype=np.uint32) if words else None
+        _lib.check(self.lib.vsmpc_rollout_noise_draws(self._r, int(tick0), int(ticks), _ptr(z), _ptr(w)), "vsmpc_rollout_noise_draws")
+        return (z, w) if words else z
+
     def set_jet_plant(self, jet_model=None, Q=None, R=None):
         """Jet plant option (vsmpc_rollout_set_jet_plant): `jet_model` = a jet_plant.JetModelTotal (the LSTM thrust model;
         None = back to the polynomial jet plant); Q, R = EKF covariances, default 0.1 I / 0.5 I

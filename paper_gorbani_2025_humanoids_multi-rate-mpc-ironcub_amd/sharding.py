@@ -53,6 +53,11 @@ def gather_first_moves(first_move_local, total: int):
     return torch.cat([o[:c] for o, c in zip(out, counts)], dim=0)
 
 
+def rank_first_index(total: int, rank: int, world: int) -> int:
+    """`first_index` of a rank's ClosedLoopRollout.set_noise: its loops then draw what they draw in the whole batch"""
+    return shard_range(total, rank, world)[0]
+
+
 def rank_inputs(cfg, synth, total: int, rank: int, world: int, workload: str = "hover", seed0: int = 1234) -> np.ndarray:
     first, count = shard_range(total, rank, world)
     return synth.make_batch(cfg, count, workload=workload, seed0=seed0, first_index=first)

@@ -1,11 +1,15 @@
 """Instruction-for-instruction comparison of the GPU kernels of two builds (the objects under <pkg>/build/ of two trees).
 
-    python tools/isa_diff.py OLD_BUILD_DIR NEW_BUILD_DIR [-v]
+    python tools/isa_diff.py OLD_BUILD_DIR NEW_BUILD_DIR [-v] [--rename OLD=NEW ...]
 
 For every .o of either directory: the gfx950 code object (kernel_resources.code_object), `llvm-objdump -d`, split by
 kernel symbol, demangled.  Kernels are matched by demangled name over the whole build (which object holds a kernel, and in
 which order, is not compared), after one normalisation: a trailing `, false` / `, true` template argument of
-solve_kernel<...> that only the OLD build has (the retired PLDS parameter) is dropped.
+solve_kernel<...> that only the OLD build has (the retired PLDS parameter) is dropped.  --rename OLD=NEW pairs a kernel whose
+name changed: the one kernel of the old build whose demangled name contains OLD with the one of the new build whose name
+contains NEW (a kernel that became a template: --rename 'vsmpc::record_kernel(=vsmpc::record_kernel<false>(').  The s_nop
+padding behind a kernel's last s_endpgm, up to the next symbol's alignment, is no instruction of the kernel and is dropped:
+a template instantiation lies in a section of its own and has none.
 
 Compared per kernel: the instruction text (mnemonic and operands; encodings and addresses are not; branch operands are
 PC-relative and so position independent as they stand; the literal of a PC-relative address -- s_getpc_b64 followed by
@@ -111,13 +115,16 @@ def build_kernels(build_dir: str) -> dict:
             name = dem.get(sym, sym)
             if name in out:
                 raise SystemExit(f"kernel {name} appears twice in {build_dir} ({out[name][2]}, {os.path.basename(obj)})")
+            while len(ins) > 1 and ins[-1].startswith("s_nop") and any(i.startswith("s_endpgm") for i in ins):
+                ins.pop()
             out[name] = (ins, notes, os.path.basename(obj))
     return out
 
 
 def main(argv) -> int:
     verbose = "-v" in argv
-    dirs = [a for a in argv if a != "-v"]
+    renames = [argv[i + 1].split("=", 1) for i, a in enumerate(argv[:-1]) if a == "--rename"]
+    dirs = [a for i, a in enumerate(argv) if a not in ("-v", "--rename") and (i == 0 or argv[i - 1] != "--rename")]
     if len(dirs) != 2:
         print(__doc__)
         return 2
@@ -129,6 +136,13 @@ def main(argv) -> int:
     if not old or not new:
         print("no kernels found")
         return 1
+    for a, b in renames:
+        olds, news = [n for n in old if a in n], [n for n in new if b in n]
+        if len(olds) != 1 or len(news) != 1:
+            print(f"--rename {a}={b}: {len(olds)} kernels of the old build and {len(news)} of the new one match")
+            return 2
+        print(f"renamed: {olds[0]} -> {news[0]}")
+        old[news[0]] = old.pop(olds[0])
     bad, shown = 0, 0
     print("kernel | object | instructions | " + " ".join(n.replace("_count", "").replace("_fixed_size", "") for n in NOTES)
           + " | verdict")

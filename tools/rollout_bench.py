@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Closed-loop rollout throughput: `batch` resident loops advanced `ticks` MPC periods (3 kernels per tick).
-Usage: python tools/rollout_bench.py [batch] [ticks] [workload] [jetnn|tree]
+Usage: python tools/rollout_bench.py [batch] [ticks] [workload] [jetnn|tree] [--noise]
 `jetnn` selects the jet plant option (LSTM thrust dynamics + EKF, weights of tests/golden/jet_lstm.npz), `tree` the
-kinematic-tree plant (provider + kinematics kernels on the plant's joints every tick: six launches per tick)."""
+kinematic-tree plant (provider + kinematics kernels on the plant's joints every tick: six launches per tick).
+`--noise`: the cost of set_noise (all six sigmas on) -- windows of `ticks` ticks, alternately without and with noise, five of
+each on one rollout, every window from a reset and without a log (give enough ticks for a window of a few tenths of a
+second); prints every window and the ratio of the medians."""
 import importlib
 import json
 import os
@@ -14,7 +17,37 @@ sys.path.insert(0, ROOT)
 PKG = "paper_gorbani_2025_humanoids_multi-rate-mpc-ironcub_amd"
 
 
+NOISE = dict(seed=2025, pos=0.01, lin_vel=0.015, rpy=0.02, ang_vel=0.015, force=20.0, torque=5.0)
+
+
+def noise_windows(r, st, pa, batch, ticks, pairs=5):
+    """alternating windows on one rollout: us per tick without / with noise, and the ratio of the medians"""
+    import statistics
+    us = {False: [], True: []}
+    for on in (False, True):                      # both captured graphs and both kernel pairs warm
+        r.set_noise(**NOISE) if on else r.set_noise(None)
+        r.reset(st, pa)
+        r.run(50, log=False)
+    for w in range(2 * pairs):
+        on = w % 2 == 1
+        r.set_noise(**NOISE) if on else r.set_noise(None)
+        r.reset(st, pa)
+        log = r.run(25, log=True)                 # (set_noise dropped the captured ticks: capture outside the window)
+        t0 = time.perf_counter()
+        r.run(ticks, log=False)                   # returns after the last tick has completed
+        us[on].append(1e6 * (time.perf_counter() - t0) / ticks)
+        print(json.dumps({"window": w, "noise": on, "batch": batch, "ticks": ticks, "us_per_tick": us[on][-1],
+                          "solved_fraction_first_25": float((log[:, :, 14] == 1).mean()),
+                          "final_state_finite": bool(__import__("numpy").isfinite(r.state()).all())}))
+    plain, noisy = statistics.median(us[False]), statistics.median(us[True])
+    print(json.dumps({"what": "closed-loop rollout, noise against none", "batch": batch, "ticks": ticks,
+                      "us_per_tick_plain_median": plain, "us_per_tick_noise_median": noisy, "ratio": noisy / plain,
+                      "plain_spread": max(us[False]) / min(us[False]) - 1.0, "noise_spread": max(us[True]) / min(us[True]) - 1.0}))
+
+
 def main():
+    noise = "--noise" in sys.argv
+    sys.argv = [a for a in sys.argv if a != "--noise"]
     batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
     ticks = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
     workload = sys.argv[3] if len(sys.argv) > 3 else "hover"
@@ -42,6 +75,10 @@ def main():
         jm = importlib.import_module(PKG + ".jet_plant").JetModelTotal(g["w_ih"], g["w_hh"], g["b_ih"], g["b_hh"], g["fc_w"],
                                                                        g["fc_b"], g["norm"], device=0, max_series=64)
         r.set_jet_plant(jm)
+    if noise:
+        noise_windows(r, st, pa, batch, ticks)
+        r.close()
+        return
     r.reset(st, pa)
     r.run(50, log=False)
     r.reset(st, pa)
